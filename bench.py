@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py - env-steps/sec trained by the full-trajectory recurrent SAC update on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints one JSON line (`ms_per_step` = milliseconds per timed step).  `--full` adds
+everything else the benchmark measures: the per-kernel roofline of the graph-replayed update (eager updates of their own), the
+fp32-MFMA and bf16x3 product legs, the one-rank RCCL leg, the suite of other BASELINE configs and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed (its log scalars, the trained parameters) as DIR/<name>.npy.
 
 N > 1: one rank per GPU over RCCL.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the ranks are
 torchrun's; a plain `python bench.py --gpus N` starts its own N ranks as child processes (before this process touches a GPU),
@@ -15,8 +20,8 @@ gradient buffer per optimizer step; `--global-rows G` instead splits a FIXED glo
 (strong scaling, e.g. configs[3]: --global-rows 512 at N = 1, 2, 4, 8).  Rank 0 prints one JSON line.
 
     python bench.py --rnn <layer id> --algo sac|td3 --rows B --horizon T      other layer families / sizes (same JSON line)
-    python bench.py --mode rollout [--envs E]                                  the per-environment-step policy forward:
-                                                                               hipGraph replay vs eager vs CPU step, optionally E environments per replay
+    python bench.py --mode rollout [--envs E] [--full]                         the per-environment-step policy forward:
+                                                                               hipGraph replay (--full: vs eager vs CPU step), optionally E environments per replay
 """
 import argparse
 import json
@@ -80,6 +85,40 @@ def build_trainer(rnn, B, T, seed=0, algo='sac'):
     alg = alg_init(make_parameter(rnn, B, T, algo=algo))
     fill_synthetic(alg, 2 * B, T, seed)
     return alg
+
+
+DUMP_BYTES = 64 << 20                                   # --dump-outputs: all files together
+
+
+def update_outputs(alg, log):
+    """What a caller of `train_one_batch()` receives from one update: the log dict's numbers and the trained state (flat parameters of
+    the actor, critics and target critics, log alpha).  Copied to the host at once - later updates overwrite all of it."""
+    out = {}
+    for k, v in log.resolve().items():
+        try:
+            out['log_' + k] = np.asarray(v, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            pass                                          # a non-numeric entry
+    nets = [('policy', alg.policy)] + [(f'value{i}', v) for i, v in enumerate(alg.values)] + \
+           [(f'target_value{i}', v) for i, v in enumerate(alg.target_values)]
+    for name, net in nets:
+        out['param_' + name] = net.store.flat[:net.store.numel].detach().float().cpu().numpy()
+    out['param_log_sac_alpha'] = alg.log_sac_alpha.detach().float().cpu().numpy().reshape(-1)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """One DIR/<name>.npy per array (float32 / float64).  Past DUMP_BYTES in all, arrays of more than 4096 elements share what the
+    small ones leave of the budget, each as a seeded sample of its elements (the same positions in every run with the same arguments)."""
+    import re
+    os.makedirs(path, exist_ok=True)
+    small = sum(a.nbytes for a in arrays.values() if a.size <= 4096)
+    large = sum(a.nbytes for a in arrays.values() if a.size > 4096)
+    for name, a in arrays.items():
+        keep = a.size if a.size <= 4096 or small + large <= DUMP_BYTES else a.size * (DUMP_BYTES - small) // large
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, re.sub(r'[^\w.-]', '_', name) + '.npy'), a)
 
 
 def baseline_config(args):
@@ -230,9 +269,12 @@ def rollout_mode(args):
         dt = time.perf_counter() - t0
         alg.graph_step = keep
         assert np.isfinite(a).all()
-        return dt / args.steps
+        return dt / args.steps, a
 
-    eager, graph = run(False), run(True)
+    eager = run(False)[0] if args.full else None
+    graph, action = run(True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'action': np.asarray(action, dtype=np.float32)})
     batched = None
     if args.envs > 1:                                  # B independent environments advanced by ONE graph replay
         from offpolicy_rnn.hip.graph_step import GraphedPolicyStep
@@ -253,10 +295,10 @@ def rollout_mode(args):
            'dtype': 'f32', 'data': 'synthetic',
            'config': {'workload': f'{args.rnn} {args.algo.upper()} policy, one token per step, B=1, obs={OBS}, act={ACT}, D=256; '
                                   f'host numpy in -> sampled action on the host'},
-           'graph_us_per_step': 1e6 * graph, 'eager_us_per_step': 1e6 * eager}
+           'graph_us_per_step': 1e6 * graph, 'eager_us_per_step': 1e6 * eager if eager is not None else None}
     if batched is not None:
         out['batched'] = {'envs': args.envs, 'us_per_replay': 1e6 * batched, 'env_steps_per_s': args.envs / batched}
-    if not args.no_cpu_baseline and not args.rnn.startswith('cgpt'):
+    if args.full and not args.no_cpu_baseline and not args.rnn.startswith('cgpt'):
         import subprocess
         code = ("import json,sys; sys.path.insert(0, %r); from oracle.trainer import time_cpu_rollout; "
                 "print(json.dumps(time_cpu_rollout(%r, steps=500, threads=1)))") % (ROOT, args.rnn)
@@ -374,7 +416,8 @@ def rccl_one_rank_leg(args):
     env = dict(os.environ, RESEL_DP_FORCE_COLLECTIVES='1', RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1')
     env.pop('MASTER_PORT', None)
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '5', '--warmup', '2', '--rnn', args.rnn, '--algo', args.algo,
-           '--rows', str(args.rows), '--horizon', str(args.horizon), '--no-cpu-baseline', '--no-strict-leg', '--no-rccl-leg', '--no-suite', '--no-graph-leg']
+           '--rows', str(args.rows), '--horizon', str(args.horizon), '--full', '--no-cpu-baseline', '--no-strict-leg', '--no-rccl-leg', '--no-suite',
+           '--no-graph-leg']
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -396,8 +439,8 @@ def suite_legs(args):
     import subprocess
     out = {}
     for name, extra in SUITE:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-strict-leg',
-               '--no-rccl-leg', '--no-suite'] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '10', '--warmup', '3', '--full', '--no-cpu-baseline',
+               '--no-strict-leg', '--no-rccl-leg', '--no-suite'] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -432,7 +475,13 @@ def main():
                     help='launcher check without GPUs: every rank reports its rendezvous environment and row split over a gloo group, no kernels')
     ap.add_argument('--no-suite', action='store_true', help='default workload at N = 1: skip the child runs of BASELINE configs[2] and configs[4]')
     ap.add_argument('--no-rccl-leg', action='store_true', help='N = 1: skip the child run that issues the data-parallel collectives in a one-rank RCCL group')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline (roofline eager updates, product-mode legs, RCCL leg, suite, CPU baselines); '
+                         'the --no-* options above pick from these')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.mode == 'rollout':
         return rollout_mode(args)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -488,16 +537,19 @@ def main():
     t0 = time.perf_counter()
     trained = 0
     for _ in range(args.steps):
-        trained += step_fn()['real_batch_size']
+        log = step_fn()
+        trained += log['real_batch_size']
         alg.grad_num += 1
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, update_outputs(alg, log))
     coll = {k: v / args.steps for k, v in alg.grad_sync.calls.items() if k != 'broadcast'}
     coll_bytes = {k: v / args.steps for k, v in alg.grad_sync.bytes.items() if k != 'broadcast'}
     eager_ms = None
     if gu is not None:
         gu.close()                                       # the eager legs below draw their dropout offsets from torch's generator again
-    if args.graph_update:
+    if args.graph_update and args.full:
         # Events cannot be bound to dispatches inside a graph replay: the per-kernel times of the roofline objects come from the SAME
         # update launched eagerly right behind the timed region (same kernels, same shapes, same stream), which also gives the
         # eager time per update reported beside the headline.
@@ -531,10 +583,10 @@ def main():
         sync()
         ops.GEMM_SPLIT = keep
         return 1e3 * (time.perf_counter() - t1) / 3
-    if gemm_mode != 0 and not args.no_strict_leg:
+    if gemm_mode != 0 and args.full and not args.no_strict_leg:
         # the same update with the GEMM products formed by the fp32 MFMA instruction (reported beside the headline, never as it)
         strict_ms = leg_with_products(0)
-    if gemm_mode != 3 and not args.no_strict_leg:
+    if gemm_mode != 3 and args.full and not args.no_strict_leg:
         # ... and with two bf16 planes per operand ("bf16x3" = torch.set_float32_matmul_precision('high'), SURVEY 8(d)'s 'TF32-class'
         # option): NOT the reference's precision setting, so never the headline either
         high_ms = leg_with_products(3)
@@ -632,14 +684,14 @@ def main():
     if len(lines) > 1:
         out['roofline_other'] = lines[1:]
     out['kernels'] = kern
-    if world == 1 and not alg.grad_sync.active and not args.no_rccl_leg:
+    if world == 1 and not alg.grad_sync.active and args.full and not args.no_rccl_leg:
         out['rccl_one_rank_leg'] = rccl_one_rank_leg(args)
     default_workload = args.rnn == 'smamba_s32_c16_b2_nln' and args.rows == 64 and args.horizon == 1024 and args.algo == 'sac'
-    if world == 1 and default_workload and not args.no_suite:
+    if world == 1 and default_workload and args.full and not args.no_suite:
         del alg
         torch.cuda.empty_cache()
         out['suite'] = suite_legs(args)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline('gru')      # of record: north_star's CPU GRU trainer at the full B=64, T=1024
         if args.rnn != 'gru':
             out['cpu_baseline_same_stack'] = cpu_baseline(args.rnn, args.algo)

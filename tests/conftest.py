@@ -31,6 +31,18 @@ def nested(d, prefix):
     return out
 
 
+@pytest.fixture(scope='session', autouse=True)
+def private_log_dir(tmp_path_factory):
+    """The trainer's logger writes under RESEL_LOG_DIR (default /tmp/resel_logs, one folder for every user of the machine): a test
+    session that did not choose one gets its own, inherited by the bench.py runs it starts."""
+    if 'RESEL_LOG_DIR' in os.environ:
+        yield
+        return
+    os.environ['RESEL_LOG_DIR'] = str(tmp_path_factory.mktemp('resel_logs'))
+    yield
+    del os.environ['RESEL_LOG_DIR']
+
+
 @pytest.fixture(scope='session')
 def golden_dir():
     return GOLDEN
