@@ -262,7 +262,13 @@ int resel_tanh_gaussian_bwd(const float* out2, const float* noise, const float* 
  * done (already timeout-corrected), reward, mask: [M].  guard: device fp32[4] = {min, max, initialised, decay}:
  *   if !initialised: min/max <- extrema of v (first call, q_value_guard.py:23-26);  y = r + (1-d) gamma clamp(v)
  *   then the running update of q_value_guard.py:29-38 with y*mask - all on device, no host sync.
- * target: [M].  stats (optional) fp32[2]: max |target|, sum(mask). */
+ * target: [M].  stats (optional) fp32[2]: max |target|, sum(mask).
+ * NaN: a NaN in a SELECTED member's next-Q (or in next_logp) makes target[i] NaN, as q.min(dim=0) and clamp of the reference
+ * do, so that the critic loss shows it.  The guard does not follow the reference there (its .item() extrema would turn NaN for
+ * good): the extrema behind the first-call initialisation, the running update and stats[0] are taken with fminf / fmaxf and
+ * skip NaN elements, so the guard keeps describing the finite rows of the batch.  A batch without a single finite row has the
+ * extrema {+inf, -inf}: it leaves an initialised guard as it is at decay 1 and makes it infinite at a decay below 1.  The same
+ * holds for the data-parallel forms below. */
 int resel_sac_target(const float* q, const int32_t* subset, int m, const float* next_logp, const float* log_alpha,
                      const float* reward, const float* done, const float* mask, float gamma, float* guard,
                      float* target, float* stats, void* workspace, int E, int M, resel_stream_t stream);

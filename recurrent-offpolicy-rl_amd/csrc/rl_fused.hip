@@ -88,8 +88,14 @@ __global__ __launch_bounds__(256) void target_v_kernel(const float* __restrict__
     float mn = INFINITY, mx = -INFINITY;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
         float val = INFINITY;
-        for (int k = 0; k < m; ++k) val = fminf(val, q[(int64_t)subset[k] * M + i]);
+        bool bad = false;                             // fminf drops a NaN operand; q.min(dim=0) of the reference hands it on
+        for (int k = 0; k < m; ++k) {
+            const float x = q[(int64_t)subset[k] * M + i];
+            bad |= x != x;
+            val = fminf(val, x);
+        }
         if (next_logp) val -= alpha * next_logp[i];
+        if (bad) val = NAN;
         v[i] = val;
         mn = fminf(mn, val); mx = fmaxf(mx, val);
     }
@@ -111,7 +117,8 @@ __global__ __launch_bounds__(256) void target_y_kernel(const float* __restrict__
     const float lo = ready ? guard[0] : -INFINITY, hi = ready ? guard[1] : INFINITY;
     float mn = INFINITY, mx = -INFINITY, ma = 0.f, sm = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
-        const float c = fminf(fmaxf(v[i], lo), hi);
+        const float vi = v[i];
+        const float c = vi != vi ? vi : fminf(fmaxf(vi, lo), hi);      // torch.clamp propagates NaN; fmaxf / fminf alone would return lo
         const float y = reward[i] + (1.f - done[i]) * gamma * c;
         target[i] = y;
         const float mk = mask ? mask[i] : 1.f;
