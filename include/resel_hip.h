@@ -199,6 +199,23 @@ int resel_gru_seq_bwd(const float* w_hh, const float* h0, const float* h_all, co
                       const float* dh_all, float* dgi, float* dgh, void* workspace,
                       int B, int L, int H, resel_stream_t stream);
 
+/* N independent GRU recurrences (1 <= n_net <= 4, same B, L, H; each with its own gi, W_hh, b_hh, h0 and outputs) in ONE launch
+ * sequence on one stream: one layout launch, one memset, and either one persistent launch over all L steps (network = outermost
+ * part of the workgroup index) or, when n_net x (H/16) x ceil(B/4) workgroups are not co-resident or RESEL_GRU_PERSISTENT=0, L
+ * launches with the network in grid.z.  resel_gru_multi_form() tells which: 1 persistent, 0 per step.
+ * gi, w_hh, b_hh, h0, h_all, gates are HOST arrays of n_net device pointers, read during the call and handed to the kernels by
+ * value (no device-side table, no copy: the call is capturable).  h0 and gates may be NULL as arrays or per entry (zero initial
+ * state / nothing saved for a backward).  The per-step arithmetic of a network is that of resel_gru_seq_fwd: its outputs are
+ * bit-identical to a call for that network alone.  workspace: resel_gru_multi_workspace_bytes(); behind the n_net re-laid-out
+ * W_hh copies (3 H H floats each) every network has ceil(B/4) * 8 H exchange granules (8 bytes) and a 64-byte block whose
+ * first int is its error word (non-zero: a bounded spin ran out, that network's output is poisoned with NaN).
+ * There is no backward twin: the backward recurrences of an update belong to different optimizer steps (resel_gru_seq_bwd). */
+size_t resel_gru_multi_workspace_bytes(int n_net, int B, int L, int H);
+int resel_gru_multi_fwd(int n_net, const float* const* gi, const float* const* w_hh, const float* const* b_hh,
+                        const float* const* h0, float* const* h_all, float* const* gates, void* workspace,
+                        int B, int L, int H, resel_stream_t stream);
+int resel_gru_multi_form(int n_net, int B, int H);
+
 /* ------------------------------------------------------------------------------------------------------
  * cgpt attention core: packed var-len causal attention with ALiBi, bf16 MFMA (v_mfma_f32_32x32x16_bf16), fp32 softmax.
  * Replaces the flash-attn varlen kernels reached through `flash_attn.modules.mha.MHA(causal=True, use_alibi=True)`
@@ -318,6 +335,13 @@ int resel_soft_update(float* target, const float* online, float tau, int64_t n, 
 int resel_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
                      const float* seg_lr, const float* seg_wd, int nseg, float beta1, float beta2, float eps,
                      int step, const float* grad_scale, resel_stream_t stream);
+/* The same step with the step-dependent factors taken BY VALUE: bc1 = 1 - beta1^t, bc2_sqrt = sqrt(1 - beta2^t) as the caller formed
+ * them.  The eager update passes the values FlatAdamW.prepare_step() writes for the captured one (fp64 on the host, rounded once), so
+ * that an eagerly launched and a replayed update take bit-identical steps; resel_adamw_flat forms them in fp32 from `step`, where
+ * 1 - beta2^t loses up to 6e-5 / t of its value to cancellation. */
+int resel_adamw_flat_bc(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
+                        const float* seg_lr, const float* seg_wd, int nseg, float beta1, float beta2, float eps,
+                        float bc1, float bc2_sqrt, const float* grad_scale, resel_stream_t stream);
 /* The same step with the step-dependent factors read from DEVICE memory: bias_corrections[0] = 1 - beta1^t,
  * bias_corrections[1] = sqrt(1 - beta2^t).  For updates replayed from a hipGraph, where a by-value step would be frozen at capture. */
 int resel_adamw_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,

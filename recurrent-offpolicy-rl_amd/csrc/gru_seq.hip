@@ -12,6 +12,10 @@
 //   that piece of W_hh for all three gates IN REGISTERS (3H/16 <= 96 floats, fetched with fully coalesced float4 loads
 //   from a copy laid out once per call as [slice][float4 chunk][thread]); the 4 rows of h_{t-1} (forward) / of the gate
 //   gradients (backward) sit in LDS and are read as broadcast float4s; the 16 partial sums of an output meet in LDS.
+// A third entry, resel_gru_multi_fwd, runs up to four INDEPENDENT recurrences of equal shape through the same two drivers in one launch
+// (network = outermost grid index; residency rule of its own, see multi_resident_cap): the trainer's concurrent embedding passes share the
+// chip without a stream each, so that the update is a single-stream launch sequence.  The step bodies are device functions shared by the
+// single- and multi-network kernels.  The backward has no multi form (the backward recurrences of an update sit in different optimizer steps).
 // All arithmetic is exact fp32 FMA (parity target 1e-4 against ATen's CPU GRU).  [First version: 64 workgroups with
 // the W slice and 16 rows in LDS, every thread a full-length dot product - LDS-read bound at 9 us (fwd) / 23 us (bwd)
 // per step.]  Neither roofline is tight for this layer; the reported figure is the achieved step rate.
@@ -35,7 +39,7 @@ constexpr int HMAX = 512;
 
 // forward copy: thread (kq, j) of slice s needs W_hh[g*H + s*16 + j][kq*KC + i], g < 3, i < KC = H/16, as 3*KC/4 float4s
 //   wf[((s * NC + c) * NT + tid) * 4 + e]   with chunk c = g * (KC/4) + i/4, e = i % 4, tid = kq * 16 + j, NT = 16 KQ
-__global__ void gru_layout_fwd_kernel(const float* __restrict__ w_hh, float* __restrict__ wf, int H, int KQ) {
+__device__ __forceinline__ void gru_layout_fwd_elem(const float* __restrict__ w_hh, float* __restrict__ wf, int H, int KQ) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)3 * H * H) return;
     const int KC = H / KQ, NC = 3 * KC / 4, NT = 16 * KQ;
@@ -47,6 +51,17 @@ __global__ void gru_layout_fwd_kernel(const float* __restrict__ w_hh, float* __r
     const int g = c / (KC / 4), i4 = c % (KC / 4);
     const int kq = tid >> 4, j = tid & 15;
     wf[i] = w_hh[((int64_t)g * H + s * 16 + j) * H + kq * KC + i4 * 4 + e];
+}
+__global__ void gru_layout_fwd_kernel(const float* __restrict__ w_hh, float* __restrict__ wf, int H, int KQ) {
+    gru_layout_fwd_elem(w_hh, wf, H, KQ);
+}
+constexpr int NNET = 4;   // networks one multi launch takes
+struct GruLayoutMulti {
+    const float* w_hh[NNET];
+    float* wf[NNET];
+};
+__global__ void gru_layout_fwd_multi_kernel(GruLayoutMulti m, int H, int KQ) {    // network in grid.y
+    gru_layout_fwd_elem(m.w_hh[blockIdx.y], m.wf[blockIdx.y], H, KQ);
 }
 // backward copy: thread (kq, j) needs W_hh[q][s*16 + j] for the kq-th 1/16 of the 3H gate rows q: RC = 3H/16 values
 //   wb[((s * NC + c) * NT + tid) * 4 + e]   with q = kq * RC + c * 4 + e
@@ -69,13 +84,14 @@ struct GruFwd {
     int B, L, H, t;
 };
 
+// One step of one network for the workgroup (unit slice s, rows b0 .. b0 + RG): the body of the launch-per-step kernels, single
+// and multi-network alike.
 template <int KC>                                    // KC = H / 16: reduction elements per thread and gate
-__global__ __launch_bounds__(256) void gru_fwd_step_kernel(GruFwd p) {
+__device__ __forceinline__ void gru_fwd_step_body(const GruFwd& p, const int s, const int b0) {
     constexpr int NC = 3 * KC / 4;
     __shared__ __attribute__((aligned(16))) float s_h[RG][KC * KQMAX];
     __shared__ float s_p[KQMAX][RG * 3][US + 1];
     const int tid = threadIdx.x, NT = blockDim.x, KQ = NT >> 4, H = p.H;
-    const int s = blockIdx.x, b0 = blockIdx.y * RG;
     const int j = tid & 15, kq = tid >> 4;
     // this thread's piece of W_hh (registers) and the gate inputs of its output (issued first: longest latency)
     float4 w[NC];
@@ -149,18 +165,23 @@ typedef unsigned long long u64;
 #define RESEL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 constexpr unsigned SPIN_LIMIT = 1u << 22;
 
+// ids congruent mod 8 share an XCD (round-robin dispatch): give a row group's slices one XCD when the grid allows it
+__device__ __forceinline__ int gru_xcd_remap(int id, const int total) {
+    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
+    return id;
+}
+
+// All L steps of one network for the workgroup with (remapped) index `id` inside that network's H/16 x ceil(B/4) workgroups: the
+// body of the single-network persistent kernel and of the multi-network one (which picks the network from the outermost part
+// of the index), so that a network's arithmetic does not depend on how many others share the launch.
 template <int KC>
-__global__ __launch_bounds__(256) void gru_fwd_persistent_kernel(GruFwd p, u64* __restrict__ xchg, int* __restrict__ err) {
+__device__ __forceinline__ void gru_fwd_persistent_body(const GruFwd& p, u64* __restrict__ xchg, int* __restrict__ err, const int id) {
     constexpr int NC = 3 * KC / 4;
     __shared__ __attribute__((aligned(16))) float s_h[RG][KC * KQMAX];
     __shared__ float s_p[KQMAX][RG * 3][US + 1];
     __shared__ int s_fail;
     const int tid = threadIdx.x, NT = blockDim.x, KQ = NT >> 4, H = p.H;
     const int nslice = H / US;
-    // ids congruent mod 8 share an XCD (round-robin dispatch): give a row group's slices one XCD when the grid allows it
-    int id = blockIdx.x;
-    const int total = gridDim.x;
-    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
     const int s = id % nslice, rg = id / nslice, b0 = rg * RG;
     const int j = tid & 15, kq = tid >> 4;
     float4 w[NC];
@@ -275,6 +296,39 @@ __global__ __launch_bounds__(256) void gru_fwd_persistent_kernel(GruFwd p, u64* 
         __syncthreads();
 #endif
     }
+}
+
+template <int KC>
+__global__ __launch_bounds__(256) void gru_fwd_step_kernel(GruFwd p) {
+    gru_fwd_step_body<KC>(p, blockIdx.x, blockIdx.y * RG);
+}
+template <int KC>
+__global__ __launch_bounds__(256) void gru_fwd_persistent_kernel(GruFwd p, u64* __restrict__ xchg, int* __restrict__ err) {
+    gru_fwd_persistent_body<KC>(p, xchg, err, gru_xcd_remap(blockIdx.x, gridDim.x));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// N independent recurrences (same B, L, H) in ONE launch: what three streams bought the gru trainer - latency-bound recurrences
+// sharing the chip - as a property of the kernel, so that the update is a single-stream launch sequence a hipGraph capture
+// takes.  The argument struct holds every network's pointers BY VALUE (host arrays are read by the C entry: no device-side
+// pointer table, no copy).  Persistent form: grid = n_net x (H/16) x ceil(B/4) workgroups, network = outermost part of the
+// XCD-remapped index (a row group's 16 slices stay on one XCD while total / 8 is a multiple of H/16); every network has its own
+// granules and error word.  Per-step form: network in grid.z.
+struct GruFwdMulti {
+    GruFwd net[NNET];
+    u64* xchg[NNET];
+    int* err[NNET];
+    int per_net;                                     // workgroups per network (persistent form)
+};
+template <int KC>
+__global__ __launch_bounds__(256) void gru_fwd_multi_step_kernel(GruFwdMulti m) {
+    gru_fwd_step_body<KC>(m.net[blockIdx.z], blockIdx.x, blockIdx.y * RG);
+}
+template <int KC>
+__global__ __launch_bounds__(256) void gru_fwd_multi_persistent_kernel(GruFwdMulti m) {
+    const int id = gru_xcd_remap(blockIdx.x, gridDim.x);
+    const int n = id / m.per_net;
+    gru_fwd_persistent_body<KC>(m.net[n], m.xchg[n], m.err[n], id - n * m.per_net);
 }
 
 struct GruBwd {
@@ -507,6 +561,7 @@ inline bool persistent_ok(int B, int H) {
     static const int mode = getenv("RESEL_GRU_PERSISTENT") ? atoi(getenv("RESEL_GRU_PERSISTENT")) : 1;
     return mode != 0 && (H / US) * ((B + RG - 1) / RG) <= 256;
 }
+// (the multi-network forward below has its own residency rule: its grid is up to four times as large)
 
 extern "C" int resel_gru_seq_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0,
                                  float* h_all, float* gates, void* workspace, int B, int L, int H, resel_stream_t stream) {
@@ -548,6 +603,122 @@ extern "C" int resel_gru_seq_fwd(const float* gi, const float* w_hh, const float
             default: return RESEL_EINVAL;
         }
     }
+    return launch_status();
+}
+
+// ---- multi-network forward ------------------------------------------------------------------------------------------
+// workspace: [n x W copy (3 H H floats each) | n x (exchange granules, error word in 64 bytes) | slack], n x the single-network size
+// (rounded to 16 bytes) in all, so that a caller may size either way.  The granule / error blocks of all networks are contiguous:
+// one memset clears them.
+inline size_t multi_sync_bytes(int B, int H) { return xchg_granules(B, H) * sizeof(u64) + 64; }
+
+extern "C" size_t resel_gru_multi_workspace_bytes(int n_net, int B, int L, int H) {
+    if (n_net < 1) n_net = 1;
+    return (size_t)n_net * ((resel_gru_workspace_bytes(B, L, H) + 15) & ~(size_t)15);
+}
+
+// Workgroups of gru_fwd_multi_persistent_kernel<KC> the device keeps resident at once.  Chosen source: the kernel's OWN resource
+// numbers (hipFuncGetAttributes: registers per lane, static LDS), not hipOccupancyMaxActiveBlocksPerMultiprocessor - that call is
+// advisory and over-reports by one block per CU for 256-thread kernels with 82+ SGPRs (this one: 87-95), and "API minus one"
+// would be a correction that is right only while that quirk lasts.  A SIMD holds 512 registers per lane in 8-register granules
+// and at most 8 waves; a workgroup here has at most 4 waves, one per SIMD, so workgroups per CU = waves per SIMD, further bounded
+// by 160 KB of LDS and by 7 (the SGPR rule for 82-96 SGPRs).  gfx950 build of this file: KC 4 / 8 / 12 / 16 / 24 / 32 use
+// 60 / 78 / 98 / 124 / 154 / 184 VGPRs, 73-84 SGPRs, no scratch, 14-21 KB of LDS -> 7 / 6 / 4 / 4 / 3 / 2 workgroups per CU (H = 256: 4,
+// H = 384: 3, H = 512: 2; the compiler's own `Occupancy [waves/SIMD]` remark says 8 / 6 / 4 / 4 / 3 / 2).
+// Cached per instantiation; 0 when no device answers (the per-step form needs no residency).
+template <int KC>
+inline int multi_resident_cap() {
+    static const int cap = [] {
+        hipFuncAttributes fa;
+        hipDeviceProp_t prop;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
+            hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(gru_fwd_multi_persistent_kernel<KC>)) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        const int regs = ((fa.numRegs > 0 ? fa.numRegs : 512) + 7) & ~7;
+        int per_cu = 512 / regs;
+        const int lds = (int)fa.sharedSizeBytes > 0 ? (160 * 1024) / (int)fa.sharedSizeBytes : 8;
+        if (per_cu > lds) per_cu = lds;
+        if (per_cu > 7) per_cu = 7;
+        return per_cu * prop.multiProcessorCount;
+    }();
+    return cap;
+}
+inline int multi_cap(int KC) {
+    switch (KC) {
+        case 4: return multi_resident_cap<4>();
+        case 8: return multi_resident_cap<8>();
+        case 12: return multi_resident_cap<12>();
+        case 16: return multi_resident_cap<16>();
+        case 24: return multi_resident_cap<24>();
+        case 32: return multi_resident_cap<32>();
+    }
+    return 0;
+}
+inline bool gru_persistent_allowed() {               // RESEL_GRU_PERSISTENT=0 forces the launch-per-step form (read once per process)
+    static const int mode = getenv("RESEL_GRU_PERSISTENT") ? atoi(getenv("RESEL_GRU_PERSISTENT")) : 1;
+    return mode != 0;
+}
+inline bool multi_persistent_ok(int n_net, int B, int H) {
+    if (!gru_persistent_allowed()) return false;
+    return n_net * (H / US) * ((B + RG - 1) / RG) <= multi_cap(pick_kc(H));
+}
+
+extern "C" int resel_gru_multi_form(int n_net, int B, int H) {
+    if (n_net < 1 || n_net > NNET || !gru_ok(B, 1, H)) return RESEL_EINVAL;
+    return multi_persistent_ok(n_net, B, H) ? 1 : 0;
+}
+
+extern "C" int resel_gru_multi_fwd(int n_net, const float* const* gi, const float* const* w_hh, const float* const* b_hh,
+                                   const float* const* h0, float* const* h_all, float* const* gates, void* workspace,
+                                   int B, int L, int H, resel_stream_t stream) {
+    if (n_net < 1 || n_net > NNET || !gi || !w_hh || !b_hh || !h_all || !workspace || !gru_ok(B, L, H)) return RESEL_EINVAL;
+    if (!aligned16(workspace)) return RESEL_EINVAL;
+    for (int n = 0; n < n_net; ++n) {
+        if (!gi[n] || !w_hh[n] || !b_hh[n] || !h_all[n] || !aligned16(h_all[n]) || (h0 && h0[n] && !aligned16(h0[n]))) return RESEL_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nw = (int64_t)3 * H * H;
+    const int KC = pick_kc(H), KQ = H / KC;
+    const int per_net = (H / US) * ((B + RG - 1) / RG);
+    char* sync = (char*)workspace + (size_t)n_net * wlayout_floats(H) * sizeof(float);
+    GruLayoutMulti lay{};
+    GruFwdMulti m{};
+    for (int n = 0; n < n_net; ++n) {
+        float* wf = (float*)workspace + (size_t)n * wlayout_floats(H);
+        char* base = sync + (size_t)n * multi_sync_bytes(B, H);
+        lay.w_hh[n] = w_hh[n];
+        lay.wf[n] = wf;
+        m.net[n] = GruFwd{gi[n], wf, b_hh[n], h0 ? h0[n] : nullptr, h_all[n], gates ? gates[n] : nullptr, B, L, H, 0};
+        m.xchg[n] = (u64*)base;
+        m.err[n] = (int*)(base + xchg_granules(B, H) * sizeof(u64));
+    }
+    m.per_net = per_net;
+    hipLaunchKernelGGL(gru_layout_fwd_multi_kernel, dim3((unsigned)((nw + 255) / 256), n_net), dim3(256), 0, s, lay, H, KQ);
+    // the error words are cleared in either form: callers read them after the pass
+    if (hipMemsetAsync(sync, 0, (size_t)n_net * multi_sync_bytes(B, H), s) != hipSuccess) return RESEL_ELAUNCH;
+#define RESEL_GRU_MULTI_CASE(KCV, KERNEL, GRID)                                                              \
+    case KCV: launch_timed(RESEL_PROF_GRU_FWD, KERNEL<KCV>, GRID, dim3(16 * KQ), 0, s, m); break;
+#define RESEL_GRU_MULTI_SWITCH(KERNEL, GRID)                                                                 \
+    switch (KC) {                                                                                            \
+        RESEL_GRU_MULTI_CASE(4, KERNEL, GRID) RESEL_GRU_MULTI_CASE(8, KERNEL, GRID) RESEL_GRU_MULTI_CASE(12, KERNEL, GRID) \
+        RESEL_GRU_MULTI_CASE(16, KERNEL, GRID) RESEL_GRU_MULTI_CASE(24, KERNEL, GRID) RESEL_GRU_MULTI_CASE(32, KERNEL, GRID) \
+        default: return RESEL_EINVAL;                                                                        \
+    }
+    if (multi_persistent_ok(n_net, B, H)) {
+        const dim3 pgrid((unsigned)(n_net * per_net));
+        RESEL_GRU_MULTI_SWITCH(gru_fwd_multi_persistent_kernel, pgrid)
+        return launch_status();
+    }
+    const dim3 grid(H / US, (B + RG - 1) / RG, n_net);
+    for (int t = 0; t < L; ++t) {
+        for (int n = 0; n < n_net; ++n) m.net[n].t = t;
+        RESEL_GRU_MULTI_SWITCH(gru_fwd_multi_step_kernel, grid)
+    }
+#undef RESEL_GRU_MULTI_SWITCH
+#undef RESEL_GRU_MULTI_CASE
     return launch_status();
 }
 

@@ -348,6 +348,15 @@ extern "C" int resel_adamw_flat(float* p, const float* g, float* m, float* v, in
     return launch_status();
 }
 
+extern "C" int resel_adamw_flat_bc(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
+                                   const float* seg_lr, const float* seg_wd, int nseg, float beta1, float beta2, float eps,
+                                   float bc1, float bc2_sqrt, const float* grad_scale, resel_stream_t stream) {
+    if (!p || !g || !m || !v || n <= 0 || !seg_end || !seg_lr || !seg_wd || nseg <= 0 || !(bc1 > 0.f) || !(bc2_sqrt > 0.f)) return RESEL_EINVAL;
+    hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                       seg_end, seg_lr, seg_wd, nseg, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, (const float*)nullptr);
+    return launch_status();
+}
+
 extern "C" int resel_adamw_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
                                     const float* seg_lr, const float* seg_wd, int nseg, float beta1, float beta2, float eps,
                                     const float* bias_corrections, const float* grad_scale, resel_stream_t stream) {

@@ -39,10 +39,8 @@ class FlatAdamW:
         """Host side of one captured step: count it and send (1 - beta1^t, sqrt(1 - beta2^t)) to the device (stream-ordered copy).
         `stage`: a pinned 2-float block that no queued copy reads any more (a caller that runs ahead of the device hands out its own)."""
         self.step_count += 1
-        t = float(self.step_count)
         host = self._bc_host if stage is None else stage
-        host[0] = 1.0 - self.betas[0] ** t
-        host[1] = (1.0 - self.betas[1] ** t) ** 0.5
+        host[0], host[1] = ops.adamw_bias_corrections(self.betas[0], self.betas[1], self.step_count)
         self._bc_dev.copy_(host, non_blocking=True)
 
     def step(self, grad_scale: torch.Tensor = None):

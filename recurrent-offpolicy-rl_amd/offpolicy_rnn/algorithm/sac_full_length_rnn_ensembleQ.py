@@ -25,6 +25,7 @@ import torch
 
 from ..buffers.transition_buffer.nested_replay_memory import NestedMemoryArray as NestedTransitionMemoryArray
 from ..hip import ops
+from ..models.contextual_model import ContextualModel
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
 from ..parallel.data_parallel import GradSync
 from ..policy_value_models.make_models import make_policy_model
@@ -171,6 +172,10 @@ class SACFullLengthRNNEnsembleQ(SAC):
         self.share_policy_pass = self._policy_pass_shareable()
         if self.share_policy_pass:              # the shared pass records an autograd graph inside the target computation: keep that on one stream
             self.overlap_value_embedding = False
+        # RESEL_GRU_BATCH (default on): instead of a stream per pass, the independent embedding passes of a phase walk their towers in
+        # lockstep and their gru recurrences share ONE launch (ContextualModel.prefetch_embeddings) - the update is then a single-stream
+        # launch sequence, which GraphedUpdate captures.  0: the side-stream form (eager only).
+        self.gru_batch = self.overlap_value_embedding and os.environ.get('RESEL_GRU_BATCH', '1') != '0'
 
     step = property(lambda self: self.train_one_batch)          # north_star's "algorithm.step()" alias
     device_replay = True        # keep a device mirror of the replay ring and assemble sampled batches on the GPU (CUDA only)
@@ -288,7 +293,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
 
     # ------------------------------------------------------------------------------------------ target
     def _prefetch_value_embedding(self, model, args, hidden):
-        if not self.overlap_value_embedding:
+        if not self.overlap_value_embedding or self.gru_batch:       # (batched form: the phase's embeddings were produced together)
             return
         # one side stream PER FORK of an update (two: the target critic's and the actor step's embedding): a stream that has been forked,
         # joined and is forked again inside one hipGraph capture ends hipStreamEndCapture with a segmentation fault on this ROCm build
@@ -527,7 +532,18 @@ class SACFullLengthRNNEnsembleQ(SAC):
             self._share_this_update = self.share_policy_pass and actor_due
             self.policy.eval()
             target_done = None
-            if self.overlap_value_embedding:
+            if self.gru_batch:
+                # latency-bound layers, one stream: the three embedding passes of this phase - (target) policy and target critic on the
+                # shifted inputs without a graph, the critic with one - run in lockstep, their recurrences in ONE launch; the target
+                # computation and the critic forward below pick their embeddings up
+                value.train()
+                shifted = (b['next_state'], b['state'], b['action'], b['reward'])
+                ContextualModel.prefetch_embeddings([
+                    (self.policy if self.target_from_live_policy else self.target_policy, shifted, target_policy_hidden, False),
+                    (target_value, shifted, target_hiddens[0], False),
+                    (value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), value_hiddens[0], True)])
+                target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
+            elif self.overlap_value_embedding:
                 # latency-bound layers: the whole (graph-free) target computation goes to a second stream, so that the critic's
                 # forward below (main stream) runs beside the target policy pass and the target critic's embedding pass
                 main = torch.cuda.current_stream(self.device)
@@ -570,6 +586,9 @@ class SACFullLengthRNNEnsembleQ(SAC):
             # 4. actor (+ alpha) step
             if self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > policy_update_cnt:
                 self._prefetch_value_embedding(value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), value_hiddens[0])
+                if self.gru_batch:                                 # the actor's pass (with a graph) and the critic's embedding (without) together
+                    now = (b['state'], b['last_state'], b['last_action'], b['reward_input'])
+                    ContextualModel.prefetch_embeddings([(self.policy, now, policy_hidden, True), (value, now, value_hiddens[0], False)])
                 if self._shared_policy_out is not None:            # the target pass's head outputs, one slot later
                     out2 = torch.nn.functional.pad(self._shared_policy_out[:, :-1], (0, 0, 1, 0))
                     self._shared_policy_out = None

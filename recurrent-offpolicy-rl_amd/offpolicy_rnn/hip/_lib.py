@@ -9,7 +9,7 @@ from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RESEL_HIP_LIBRARY') or os.path.join(_HERE, 'libresel_hip.so')      # override: ablation builds (tools/gemm_ablate.sh)
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 P, I, L, F, S, U = c_void_p, c_int, c_int64, c_float, c_void_p, c_uint64
@@ -45,6 +45,9 @@ SIGNATURES = {
     'resel_gru_workspace_bytes': (c_size_t, [I, I, I]),
     'resel_gru_seq_fwd': (c_int, [P, P, P, P, P, P, P, I, I, I, S]),
     'resel_gru_seq_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, S]),
+    'resel_gru_multi_workspace_bytes': (c_size_t, [I, I, I, I]),
+    'resel_gru_multi_fwd': (c_int, [I, P, P, P, P, P, P, P, I, I, I, S]),
+    'resel_gru_multi_form': (c_int, [I, I, I]),
     'resel_attn_varlen_fwd_workspace_bytes': (c_size_t, [I, I]),
     'resel_attn_varlen_fwd': (c_int, [P, P, P, P, P, P, I, I, I, I, I, F, F, U, U, S]),
     'resel_attn_varlen_bwd_workspace_bytes': (c_size_t, [I, I, I, I, I]),
@@ -67,6 +70,7 @@ SIGNATURES = {
     'resel_sac_target_workspace_bytes': (c_size_t, [I]),
     'resel_soft_update': (c_int, [P, P, F, L, S]),
     'resel_adamw_flat': (c_int, [P, P, P, P, L, P, P, P, I, F, F, F, I, P, S]),
+    'resel_adamw_flat_bc': (c_int, [P, P, P, P, L, P, P, P, I, F, F, F, F, F, P, S]),
     'resel_adamw_flat_dev': (c_int, [P, P, P, P, L, P, P, P, I, F, F, F, P, P, S]),
     'resel_sumsq_workspace_bytes': (c_size_t, [L]),
     'resel_sumsq': (c_int, [P, L, P, P, S]),

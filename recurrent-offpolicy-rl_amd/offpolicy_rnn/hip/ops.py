@@ -688,6 +688,71 @@ def gru_seq(gi, w_hh, b_hh, h0=None):
     return GruSeqFn.apply(gi, w_hh, b_hh, h0)
 
 
+GRU_MULTI_MAX = 4             # networks one `resel_gru_multi_fwd` launch takes
+
+
+class _GruSeqAttachFn(torch.autograd.Function):
+    """The autograd node of ONE differentiated job of `gru_seq_multi`: its forward ran in the shared launch (`done` = its h_all and
+    saved gates), the backward is `GruSeqFn`'s - one `resel_gru_seq_bwd` + `wgrad` per job."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, h0, done):
+        h_all, gates = done
+        h0 = None if h0 is None else h0.float().reshape(h_all.shape[0], h_all.shape[2]).contiguous()
+        ctx.save_for_backward(w_hh.float().contiguous(), h0, h_all, gates)
+        return h_all
+
+    @staticmethod
+    def backward(ctx, dh_all):
+        return GruSeqFn.backward(ctx, dh_all) + (None,)
+
+
+def gru_multi_form(n_net, Bsz, H) -> int:
+    """1: `gru_seq_multi` runs n_net recurrences of this shape as one persistent launch, 0: as one launch per step."""
+    form = lib().resel_gru_multi_form(int(n_net), int(Bsz), int(H))
+    check(min(form, 0), 'gru_multi_form')
+    return form
+
+
+def gru_seq_multi(jobs):
+    """jobs = [(gi, w_hh, b_hh, h0, need_grad), ...] (1 to 4 of them, equal [B, L, 3H]) -> [h_all, ...]: independent GRU recurrences
+    that share ONE launch (`resel_gru_multi_fwd`) instead of one stream each.  Every output is bit for bit what `gru_seq` returns for
+    that job alone.  A job with need_grad saves its gates and takes part in autograd; the others are constants whatever their
+    tensors' `requires_grad` says (target networks, no-grad passes)."""
+    n = len(jobs)
+    if not 1 <= n <= GRU_MULTI_MAX:
+        raise ValueError(f'gru_seq_multi takes 1 to {GRU_MULTI_MAX} jobs, got {n}')
+    prep = []
+    for gi, w_hh, b_hh, h0, need_grad in jobs:
+        _need_cuda('gru_seq_multi', gi, w_hh, b_hh, h0)
+        gi_c = gi.float().contiguous()
+        Bsz, L, H3 = gi_c.shape
+        h0_c = None if h0 is None else h0.float().reshape(Bsz, H3 // 3).contiguous()
+        prep.append((gi_c, w_hh.float().contiguous(), b_hh.float().contiguous(), h0_c))
+    Bsz, L, H3 = prep[0][0].shape
+    H = H3 // 3
+    if any(tuple(p[0].shape) != (Bsz, L, H3) for p in prep):
+        raise ValueError('gru_seq_multi: the jobs of one launch share (B, L, H)')
+    dev = prep[0][0].device
+    outs, saved = [], []
+    for (gi, w_hh, b_hh, h0, need_grad), p in zip(jobs, prep):
+        need = bool(need_grad) and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (gi, w_hh, b_hh))
+        outs.append(torch.empty(Bsz, L, H, dtype=torch.float32, device=dev))
+        saved.append(torch.empty(Bsz, L, 4 * H, dtype=torch.float32, device=dev) if need else None)
+    ws = _ws(lib().resel_gru_multi_workspace_bytes(n, Bsz, L, H), dev)
+    VP = ctypes.c_void_p * n
+    arr = lambda ts: VP(*[None if t is None else t.data_ptr() for t in ts])
+    check(lib().resel_gru_multi_fwd(n, arr([p[0] for p in prep]), arr([p[1] for p in prep]), arr([p[2] for p in prep]),
+                                    arr([p[3] for p in prep]), arr(outs), arr(saved), _p(ws), Bsz, L, H, _stream()), 'gru_multi_fwd')
+    res = []
+    for (gi, w_hh, b_hh, h0, need_grad), p, h_all, gates in zip(jobs, prep, outs, saved):
+        if gates is None:
+            res.append(h_all)
+        else:           # the node sees the caller's tensors (gradients flow to them) and saves the dense copies the kernel read
+            res.append(_GruSeqAttachFn.apply(gi, w_hh, b_hh, h0, (h_all, gates)))
+    return res
+
+
 # ---------------------------------------------------------------------------------------------- attention (cgpt)
 class AttnVarlenFn(torch.autograd.Function):
     @staticmethod
@@ -1858,12 +1923,22 @@ def soft_update_(target_flat, online_flat, tau):
     check(lib().resel_soft_update(_p(target_flat), _p(online_flat), float(tau), target_flat.numel(), _stream()), 'soft_update')
 
 
+def adamw_bias_corrections(beta1, beta2, step):
+    """(1 - beta1^t, sqrt(1 - beta2^t)) of AdamW step t, in fp64: the one spelling the eager (`adamw_flat_`, by value) and the captured
+    (`FlatAdamW.prepare_step`, device words) form of the optimizer step share."""
+    t = float(step)
+    return 1.0 - beta1 ** t, (1.0 - beta2 ** t) ** 0.5
+
+
 @torch.no_grad()
 def adamw_flat_(p, g, m, v, seg_end, seg_lr, seg_wd, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=None):
     _need_cuda('adamw_flat', p, g, m, v, seg_end, seg_lr, seg_wd)
     PARAM_EPOCH[0] += 1
-    check(lib().resel_adamw_flat(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_end), _p(seg_lr), _p(seg_wd), int(seg_end.numel()),
-                                 float(beta1), float(beta2), float(eps), int(step), _p(grad_scale), _stream()), 'adamw_flat')
+    # the step-dependent factors as the captured update gets them (`adamw_bias_corrections`: fp64 on the host, rounded once), by value:
+    # an eagerly launched and a replayed update then take bit-identical steps (`resel_adamw_flat` forms them in fp32 from `step`)
+    bc1, bc2_sqrt = adamw_bias_corrections(beta1, beta2, step)
+    check(lib().resel_adamw_flat_bc(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_end), _p(seg_lr), _p(seg_wd), int(seg_end.numel()),
+                                    float(beta1), float(beta2), float(eps), bc1, bc2_sqrt, _p(grad_scale), _stream()), 'adamw_flat')
 
 
 @torch.no_grad()

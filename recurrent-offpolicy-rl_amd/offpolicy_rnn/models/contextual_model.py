@@ -97,13 +97,16 @@ class ContextualModel:
         n_emb = self.embedding_network.rnn_num
         pre, self._prefetched = getattr(self, '_prefetched', None), None
         if pre is not None:
-            # the (graph-free) embedding pass already ran on a side stream (prefetch_embedding): join it here
-            assert detach_embedding or not torch.is_grad_enabled(), 'a prefetched embedding carries no graph'
-            emb, emb_mem, emb_full, event = pre
-            main = torch.cuda.current_stream(emb.device)
-            main.wait_event(event)
-            for t in [emb] + [h for h in list(emb_mem._data) + list(emb_full._data) if torch.is_tensor(h)]:
-                t.record_stream(main)
+            # the embedding pass already ran: on a side stream (prefetch_embedding; graph-free: join it here) or on this stream in
+            # lockstep with other networks' (prefetch_embeddings; no event, and a graph if the job asked for one)
+            emb, emb_mem, emb_full, event = pre[:4]
+            with_grad = len(pre) > 4 and pre[4]
+            assert with_grad or detach_embedding or not torch.is_grad_enabled(), 'this prefetched embedding carries no graph'
+            if event is not None:
+                main = torch.cuda.current_stream(emb.device)
+                main.wait_event(event)
+                for t in [emb] + [h for h in list(emb_mem._data) + list(emb_full._data) if torch.is_tensor(h)]:
+                    t.record_stream(main)
         else:
             mapped = not isinstance(self.uni_input_mapping_network, torch.nn.Identity)
             if row_buffer is None and mapped and torch.is_tensor(uni_model_input) and uni_model_input.dim() == embedding_input.dim():
@@ -145,6 +148,23 @@ class ContextualModel:
             event = torch.cuda.Event()
             event.record(stream)
         self._prefetched = (emb, mem, full, event)
+
+    @staticmethod
+    def prefetch_embeddings(jobs) -> None:
+        """jobs = [(model, embedding_args, rnn_memory, with_grad), ...]: run the embedding passes of the NEXT forward of each model
+        together on the CURRENT stream, their `gru` recurrences in one launch (`RNNBase.lockstep_forward`), and leave each result in
+        the model's `_prefetched`.  What `prefetch_embedding` buys with a stream per pass, as a plain launch sequence: nothing to
+        wait for, nothing to `record_stream`, capturable.  A job with_grad keeps its autograd graph (the consumer then differentiates
+        through the embedding); the others run without one."""
+        passes = []
+        for model, args, rnn_memory, with_grad in jobs:
+            n_emb = model.embedding_network.rnn_num
+            mem = rnn_memory[:n_emb] if rnn_memory is not None and len(rnn_memory) > 0 else None
+            with torch.set_grad_enabled(torch.is_grad_enabled() and bool(with_grad)):
+                x = model.get_embedding_input(*args)
+            passes.append((model.embedding_network, x, mem, with_grad))
+        for (model, _, _, with_grad), (emb, mem, full) in zip(jobs, RNNBase.lockstep_forward(passes)):
+            model._prefetched = (emb, mem, full, None, bool(with_grad) and torch.is_grad_enabled())
 
     def get_embedding(self, x, rnn_memory):
         n_emb = self.embedding_network.rnn_num

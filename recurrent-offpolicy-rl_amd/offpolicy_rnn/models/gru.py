@@ -21,9 +21,17 @@ class GRU(nn.Module):
         self.bias_ih_l0 = nn.Parameter(torch.empty(3 * hidden_size).uniform_(-k, k))
         self.bias_hh_l0 = nn.Parameter(torch.empty(3 * hidden_size).uniform_(-k, k))
 
-    def forward(self, x, hidden=None):
-        """x [B, T, in]; hidden [1, B, H] -> (y [B, T, H], last hidden [1, B, H])."""
+    def recurrence_job(self, x, hidden=None):
+        """The hoisted input projection and what the recurrence needs besides: (gi, W_hh, b_hh, h0), the arguments of `ops.gru_seq`
+        and the head of an `ops.gru_seq_multi` job (RNNBase's lockstep walk runs several networks' recurrences in one launch)."""
         gi = ops.linear(x, self.weight_ih_l0, self.bias_ih_l0)
         h0 = None if hidden is None else hidden[0]
-        y = ops.gru_seq(gi, self.weight_hh_l0, self.bias_hh_l0, h0)
+        return gi, self.weight_hh_l0, self.bias_hh_l0, h0
+
+    @staticmethod
+    def finish(y):
         return y, y[:, -1:, :].transpose(0, 1)
+
+    def forward(self, x, hidden=None):
+        """x [B, T, in]; hidden [1, B, H] -> (y [B, T, H], last hidden [1, B, H])."""
+        return self.finish(ops.gru_seq(*self.recurrence_job(x, hidden)))

@@ -262,7 +262,56 @@ class RNNBase(torch.nn.Module):
 
     def meta_forward(self, x: torch.Tensor, hidden_state: Optional[RNNHidden] = None, require_full_hidden: bool = False,
                      first_grad_part=None, out_dest=None) -> Tuple[torch.Tensor, RNNHidden, Optional[RNNHidden]]:
-        """first_grad_part = (x_part, col0): the first layer (a shared-input efc layer) differentiates x only through that
+        """The forward pass.  (Runs `_forward_steps` with every `gru` recurrence on its own, `ops.gru_seq`.)"""
+        steps = self._forward_steps(x, hidden_state, require_full_hidden, first_grad_part, out_dest)
+        try:
+            job = next(steps)
+            while True:
+                job = steps.send(ops.gru_seq(*job))
+        except StopIteration as done:
+            return done.value
+
+    @staticmethod
+    def lockstep_forward(passes):
+        """passes = [(network, x, hidden_state, with_grad), ...] -> [(out, out_state, full), ...], each what `network.meta_forward(x,
+        hidden_state, require_full_hidden=True)` returns under `torch.set_grad_enabled(with_grad)`.  The networks are walked together:
+        every pass runs up to its next `gru` layer (the other layers one network after the other, as `meta_forward` does them), then the
+        recurrences that are waiting and agree in (B, L, H) go out as ONE `ops.gru_seq_multi` launch - independent latency-bound
+        recurrences share the chip without a stream each, on the current stream.  Passes that do not line up (other layer lists or
+        shapes) simply get launches of their own: same results, one after the other."""
+        ambient = torch.is_grad_enabled()
+        gens = [net._forward_steps(x, hidden, True, None, None) for net, x, hidden, _ in passes]
+        grads = [bool(g) and ambient for _, _, _, g in passes]
+        results, jobs, reply = [None] * len(passes), {}, {}
+        live = set(range(len(passes)))
+        while live:
+            for i in sorted(live):
+                with torch.set_grad_enabled(grads[i]):
+                    try:
+                        jobs[i] = gens[i].send(reply.pop(i)) if i in reply else next(gens[i])
+                    except StopIteration as done:
+                        results[i] = done.value
+                        live.discard(i)
+            groups = {}
+            for i in sorted(jobs):
+                gi = jobs[i][0]
+                key = tuple(gi.shape) if gi.is_cuda and gi.dim() == 3 else ('alone', i)
+                groups.setdefault(key, []).append(i)
+            for members in groups.values():
+                for at in range(0, len(members), ops.GRU_MULTI_MAX):
+                    part = members[at:at + ops.GRU_MULTI_MAX]
+                    with torch.set_grad_enabled(ambient):       # each job says for itself whether it is differentiated
+                        ys = ops.gru_seq_multi([tuple(jobs[i]) + (grads[i],) for i in part])
+                    for i, y in zip(part, ys):
+                        reply[i] = y
+            jobs.clear()
+        return results
+
+    def _forward_steps(self, x: torch.Tensor, hidden_state: Optional[RNNHidden] = None, require_full_hidden: bool = False,
+                       first_grad_part=None, out_dest=None):
+        """Generator form of the forward pass: yields the (gi, W_hh, b_hh, h0) of every `gru` layer, is sent that recurrence's output
+        sequence, and returns (out, out_state, full) - so that ONE walk serves `meta_forward` and `lockstep_forward`.
+        first_grad_part = (x_part, col0): the first layer (a shared-input efc layer) differentiates x only through that
         column block (EnsembleLinear.forward); anything else keeps the ordinary path.
         out_dest: an `ops.ColDest` - if the LAST layer is an `fc` on the hand-written GEMM, its output is written straight into that column
         block of a row buffer (the caller checks with `dest.holds`)."""
@@ -327,7 +376,7 @@ class RNNBase(torch.nn.Module):
                             full.append(None)
                         continue
                 else:                                   # gru: no reset / mask handling (reference :453-454)
-                    x, h = layer(x, hidden_state[k])
+                    x, h = layer.finish((yield layer.recurrence_job(x, hidden_state[k])))
                 k += 1
                 out_state.append(h)
                 if require_full_hidden:
