@@ -32,8 +32,8 @@ fallback through `step()` draws exactly what a replay would.
 Gradient clipping (reference :239-250, 274-287) stays on the device: norm -> coefficient -> the scale word the flat AdamW kernel reads.
 Data-parallel groups: the recording is CUT at each gradient exchange (`cut`) - an update is then three graphs replayed back to back with
 the two all-reduces issued eagerly between them on the same stream (works with every backend; nothing waits on the host).
-Refused at construction (use the eager `train_one_batch`): side-stream overlap (gru with RESEL_GRU_BATCH=0), utd != 1, randomised masks / truncation, the
-three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce)."""
+Refused at construction (use the eager `train_one_batch`): utd != 1, randomised masks / truncation, the three-phase Q-guard exchange
+(RESEL_DP_GUARD=allreduce)."""
 import os
 from collections import OrderedDict
 
@@ -183,15 +183,6 @@ class GraphedUpdate:
         par = alg.parameter
         if alg.device.type != 'cuda':
             return 'needs a GPU'
-        if getattr(alg, 'overlap_value_embedding', False) and not getattr(alg, 'gru_batch', False):
-            # (the batched form - RESEL_GRU_BATCH, the default: the concurrent recurrences of a phase in one launch - is a linear launch
-            # sequence on the capture stream like every other family's and is captured.  The side-stream form is not:)
-            # tried in round 4 (twice; the second time without the tensors' record_stream calls): with the refusal lifted the capture of
-            # the gru trainer (target pass and prefetched value embeddings on side streams, forked / joined with events, the same side
-            # stream forked more than once per update) ends in a segmentation fault inside capture_end (hipStreamEndCapture) on this ROCm
-            # build; round 6 gave every fork of an update its own side stream (`_side_streams`): the same fault.  Captured on ONE stream the
-            # recurrences (3 us per step, latency-bound) would run back to back: slower than eager.
-            return 'side-stream overlap (gru) is not captured'
         if getattr(alg, 'grad_sync', None) is None:
             return 'not a full-trajectory trainer'
         if alg.grad_sync.active and os.environ.get('RESEL_DP_GUARD', 'bucket') == 'allreduce':

@@ -162,20 +162,15 @@ class SACFullLengthRNNEnsembleQ(SAC):
                                                                        self.policy.uni_network, self.policy.embedding_network)
                                     for lid in net.layer_type)
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
-        # latency-bound value embeddings (gru) of the two graph-free critic passes run on a side stream next to the policy pass
-        self.overlap_value_embedding = (self.device.type == 'cuda' and os.environ.get('RESEL_OVERLAP_EMBEDDING', '1') != '0'
-                                        and not self.discrete_env and any(lid == 'gru' for lid in self.values[0].embedding_network.layer_type))
-        self._side_stream = self._target_stream = None
-        self._side_streams, self._fork_idx = [], 0
         self._shared_policy_out = None
         self._share_this_update = False
         self.share_policy_pass = self._policy_pass_shareable()
-        if self.share_policy_pass:              # the shared pass records an autograd graph inside the target computation: keep that on one stream
-            self.overlap_value_embedding = False
-        # RESEL_GRU_BATCH (default on): instead of a stream per pass, the independent embedding passes of a phase walk their towers in
-        # lockstep and their gru recurrences share ONE launch (ContextualModel.prefetch_embeddings) - the update is then a single-stream
-        # launch sequence, which GraphedUpdate captures.  0: the side-stream form (eager only).
-        self.gru_batch = self.overlap_value_embedding and os.environ.get('RESEL_GRU_BATCH', '1') != '0'
+        # RESEL_GRU_BATCH (default on): the independent embedding passes of a phase (latency-bound gru value embeddings) walk their towers
+        # in lockstep and their recurrences share ONE launch (ContextualModel.prefetch_embeddings).  0: serial, one recurrence after
+        # another.  Both forms are launch sequences on the current stream.  Not with a shared policy pass: that pass records an autograd
+        # graph inside the target computation.
+        self.gru_batch = (self.device.type == 'cuda' and os.environ.get('RESEL_GRU_BATCH', '1') != '0' and not self.discrete_env
+                          and any(lid == 'gru' for lid in self.values[0].embedding_network.layer_type) and not self.share_policy_pass)
 
     step = property(lambda self: self.train_one_batch)          # north_star's "algorithm.step()" alias
     device_replay = True        # keep a device mirror of the replay ring and assemble sampled batches on the GPU (CUDA only)
@@ -292,17 +287,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
         return h
 
     # ------------------------------------------------------------------------------------------ target
-    def _prefetch_value_embedding(self, model, args, hidden):
-        if not self.overlap_value_embedding or self.gru_batch:       # (batched form: the phase's embeddings were produced together)
-            return
-        # one side stream PER FORK of an update (two: the target critic's and the actor step's embedding): a stream that has been forked,
-        # joined and is forked again inside one hipGraph capture ends hipStreamEndCapture with a segmentation fault on this ROCm build
-        k, self._fork_idx = self._fork_idx, self._fork_idx + 1
-        while len(self._side_streams) <= k:
-            self._side_streams.append(torch.cuda.Stream(device=self.device))
-        self._side_stream = self._side_streams[0]
-        model.prefetch_embedding(args, hidden, self._side_streams[k])
-
     target_from_live_policy = True        # (the non-REDQ TD3 trainer evaluates its frozen target policy instead)
 
     def _next_action(self, b, hidden):
@@ -397,7 +381,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
             with torch.enable_grad():           # one policy forward with a graph: the actor step reuses it one slot later
                 emb_in = self.policy.get_embedding_input(b['next_state'], b['state'], b['action'], b['reward'])
                 self._shared_policy_out = self.policy.meta_forward(emb_in, b['next_state'], policy_hidden, False)[0]
-        self._prefetch_value_embedding(self.target_values[0], (b['next_state'], b['state'], b['action'], b['reward']), target_hiddens[0])
         with torch.no_grad():
             if self._shared_policy_out is not None:     # same head, same random draws as policy.forward would make
                 sample, logp = self._target_action(*self.policy.process_model_out(self._shared_policy_out.detach()))
@@ -488,7 +471,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
 
     def _train_one_batch(self) -> Dict:
         par = self.parameter
-        self._fork_idx = 0
         if self._graph is None and self.device.type == 'cuda':
             ops.amax_maintenance()                               # update boundary: the magnitude epochs may start over here (hip/ops.py)
         self.policy.to(self.device)
@@ -531,7 +513,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
             actor_due = self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > policy_update_cnt
             self._share_this_update = self.share_policy_pass and actor_due
             self.policy.eval()
-            target_done = None
             if self.gru_batch:
                 # latency-bound layers, one stream: the three embedding passes of this phase - (target) policy and target critic on the
                 # shifted inputs without a graph, the critic with one - run in lockstep, their recurrences in ONE launch; the target
@@ -542,28 +523,12 @@ class SACFullLengthRNNEnsembleQ(SAC):
                     (self.policy if self.target_from_live_policy else self.target_policy, shifted, target_policy_hidden, False),
                     (target_value, shifted, target_hiddens[0], False),
                     (value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), value_hiddens[0], True)])
-                target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
-            elif self.overlap_value_embedding:
-                # latency-bound layers: the whole (graph-free) target computation goes to a second stream, so that the critic's
-                # forward below (main stream) runs beside the target policy pass and the target critic's embedding pass
-                main = torch.cuda.current_stream(self.device)
-                if self._target_stream is None:
-                    self._target_stream = torch.cuda.Stream(device=self.device)
-                self._target_stream.wait_stream(main)
-                with torch.cuda.stream(self._target_stream):
-                    target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
-                    target_done = torch.cuda.Event()
-                    target_done.record(self._target_stream)
-            else:
-                target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
+            target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
             valid_num = self._stats[1]
 
             # 2. critic step
             value.train()
             q = value.forward(b['state'], b['last_state'], b['last_action'], b['action'], value_hiddens[0], b['reward_input'])[0]
-            if target_done is not None:
-                main.wait_event(target_done)
-                target_Q.record_stream(main)
             if self.discrete_env:                                   # Q of the action taken (reference :158)
                 q = q.gather(-1, b['action'].long().unsqueeze(0).expand(q.shape[0], -1, -1, -1))
             if FUSED_Q and q.is_cuda and q.dtype == torch.float32:
@@ -585,7 +550,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
 
             # 4. actor (+ alpha) step
             if self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > policy_update_cnt:
-                self._prefetch_value_embedding(value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), value_hiddens[0])
                 if self.gru_batch:                                 # the actor's pass (with a graph) and the critic's embedding (without) together
                     now = (b['state'], b['last_state'], b['last_action'], b['reward_input'])
                     ContextualModel.prefetch_embeddings([(self.policy, now, policy_hidden, True), (value, now, value_hiddens[0], False)])

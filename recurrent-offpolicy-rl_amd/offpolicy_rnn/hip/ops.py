@@ -1650,7 +1650,7 @@ def amax(x):
     assert x.dtype == torch.float32 and x.stride(-1) == 1 and x.dim() in (2, 3)
     out, epoch = amax_slot(x.device)
     batch = x.shape[0] if x.dim() == 3 else 1
-    # stateless since ABI 7: pre-passes on different streams (the trainer's target / side streams) cannot disturb each other
+    # stateless since ABI 7: pre-passes on different streams cannot disturb each other
     check(lib().resel_amax(_p(x), x.stride(-2), x.stride(0) if x.dim() == 3 and batch > 1 else 0, x.shape[-2], x.shape[-1], batch,
                            _p(out), epoch, None, _stream()), 'amax')
     return out

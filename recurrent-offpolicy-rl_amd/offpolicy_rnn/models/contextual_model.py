@@ -43,6 +43,7 @@ class ContextualModel:
         self.device = torch.device('cpu')
         self.dtype = torch.float32
         self.store: Optional[FlatParameterStore] = None
+        self._prefetched = None                # (emb, mem, full, with_grad) left by prefetch_embeddings for the next forward
 
     def contextual_register_rnn_base_module(self, module, module_name: str):
         self.contextual_modules[module_name] = module
@@ -95,18 +96,12 @@ class ContextualModel:
         if rnn_memory is None:
             rnn_memory = self.make_init_state(1 if embedding_input.dim() == 2 else embedding_input.shape[0], embedding_input.device)
         n_emb = self.embedding_network.rnn_num
-        pre, self._prefetched = getattr(self, '_prefetched', None), None
+        pre, self._prefetched = self._prefetched, None
         if pre is not None:
-            # the embedding pass already ran: on a side stream (prefetch_embedding; graph-free: join it here) or on this stream in
-            # lockstep with other networks' (prefetch_embeddings; no event, and a graph if the job asked for one)
-            emb, emb_mem, emb_full, event = pre[:4]
-            with_grad = len(pre) > 4 and pre[4]
+            # the embedding pass already ran on this stream, in lockstep with other networks' (prefetch_embeddings), with a graph if
+            # the job asked for one
+            emb, emb_mem, emb_full, with_grad = pre
             assert with_grad or detach_embedding or not torch.is_grad_enabled(), 'this prefetched embedding carries no graph'
-            if event is not None:
-                main = torch.cuda.current_stream(emb.device)
-                main.wait_event(event)
-                for t in [emb] + [h for h in list(emb_mem._data) + list(emb_full._data) if torch.is_tensor(h)]:
-                    t.record_stream(main)
         else:
             mapped = not isinstance(self.uni_input_mapping_network, torch.nn.Identity)
             if row_buffer is None and mapped and torch.is_tensor(uni_model_input) and uni_model_input.dim() == embedding_input.dim():
@@ -137,25 +132,13 @@ class ContextualModel:
         out, uni_mem, uni_full = self.uni_network.meta_forward(head_in, rnn_memory[n_emb:], require_full_hidden=True, first_grad_part=uni_grad_part)
         return out, emb_mem + uni_mem, emb, emb_full + uni_full
 
-    def prefetch_embedding(self, embedding_args, rnn_memory, stream) -> None:
-        """Run the embedding pass of the NEXT no-grad / detached-embedding forward on `stream` (forked from the current
-        stream); that forward then only waits for it.  For latency-bound recurrent layers (gru: ~3 us per step whatever the
-        batch) this lets an independent pass - the actor's - use the otherwise idle chip at the same time."""
-        main = torch.cuda.current_stream(self.device)
-        stream.wait_stream(main)
-        with torch.cuda.stream(stream), torch.no_grad():
-            emb, mem, full = self.get_embedding(self.get_embedding_input(*embedding_args), rnn_memory)
-            event = torch.cuda.Event()
-            event.record(stream)
-        self._prefetched = (emb, mem, full, event)
-
     @staticmethod
     def prefetch_embeddings(jobs) -> None:
         """jobs = [(model, embedding_args, rnn_memory, with_grad), ...]: run the embedding passes of the NEXT forward of each model
         together on the CURRENT stream, their `gru` recurrences in one launch (`RNNBase.lockstep_forward`), and leave each result in
-        the model's `_prefetched`.  What `prefetch_embedding` buys with a stream per pass, as a plain launch sequence: nothing to
-        wait for, nothing to `record_stream`, capturable.  A job with_grad keeps its autograd graph (the consumer then differentiates
-        through the embedding); the others run without one."""
+        the model's `_prefetched`.  For latency-bound recurrent layers (gru: ~3 us per step whatever the batch) the independent passes
+        then share the chip, as a plain launch sequence: no stream, nothing to wait for, capturable.  A job with_grad keeps its
+        autograd graph (the consumer then differentiates through the embedding); the others run without one."""
         passes = []
         for model, args, rnn_memory, with_grad in jobs:
             n_emb = model.embedding_network.rnn_num
@@ -164,7 +147,7 @@ class ContextualModel:
                 x = model.get_embedding_input(*args)
             passes.append((model.embedding_network, x, mem, with_grad))
         for (model, _, _, with_grad), (emb, mem, full) in zip(jobs, RNNBase.lockstep_forward(passes)):
-            model._prefetched = (emb, mem, full, None, bool(with_grad) and torch.is_grad_enabled())
+            model._prefetched = (emb, mem, full, bool(with_grad) and torch.is_grad_enabled())
 
     def get_embedding(self, x, rnn_memory):
         n_emb = self.embedding_network.rnn_num

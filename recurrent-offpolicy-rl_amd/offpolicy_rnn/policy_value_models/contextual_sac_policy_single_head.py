@@ -46,7 +46,7 @@ class ContextualSACPolicySingleHead(ContextualModel):
     def forward(self, state, lst_state, lst_action, rnn_memory: Optional[RNNHidden], reward=None, detach_embedding=False
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, RNNHidden, Optional[RNNHidden]]:
         # (a prefetched embedding is waiting - ContextualModel.prefetch_embeddings: its input was built there)
-        emb_in = None if getattr(self, '_prefetched', None) is not None else self.get_embedding_input(state, lst_state, lst_action, reward)
+        emb_in = None if self._prefetched is not None else self.get_embedding_input(state, lst_state, lst_action, reward)
         out, rnn_memory, emb, full = self.meta_forward(emb_in, state, rnn_memory, detach_embedding)
         action_mean, action_sample, log_prob = self.process_model_out(out)
         return action_mean, emb, action_sample, log_prob, rnn_memory, full

@@ -52,7 +52,7 @@ class ContextualSACValue(ContextualModel):
 
     def forward(self, state, lst_state, lst_action, action, rnn_memory: Optional[RNNHidden], reward, detach_embedding=False
                 ) -> Tuple[torch.Tensor, torch.Tensor, RNNHidden, Optional[RNNHidden]]:
-        emb_in = None if getattr(self, '_prefetched', None) is not None else self.get_embedding_input(state, lst_state, lst_action, reward)
+        emb_in = None if self._prefetched is not None else self.get_embedding_input(state, lst_state, lst_action, reward)
         part = None
         # long GPU passes: the head input [state-action encoding | embedding] is ONE row buffer whose column blocks the producing GEMMs write
         # in place (no cat of 205 MB per pass at config 2, one shared magnitude handle instead of a pre-pass)

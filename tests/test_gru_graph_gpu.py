@@ -1,7 +1,7 @@
-"""The gru trainer with its concurrent recurrences in one launch (RESEL_GRU_BATCH=1): the update is a single-stream launch sequence and
-`GraphedUpdate` replays it.  Pattern, helpers and tolerances of tests/test_trainer_gpu.py `test_graphed_update_equals_the_eager_update`
+"""The gru trainer with its concurrent recurrences in one launch (RESEL_GRU_BATCH=1, the default) or one after another
+(RESEL_GRU_BATCH=0, the serial form): either way the update is a launch sequence on the current stream and `GraphedUpdate` replays it.  Pattern, helpers and tolerances of tests/test_trainer_gpu.py `test_graphed_update_equals_the_eager_update`
 (fp32 families: rtol 2e-5, atol 2e-7, 1e-6 past 16 chained updates) and of tests/test_data_parallel_gpu.py (rtol 5e-4, atol 5e-6).
-The side-stream form (RESEL_GRU_BATCH=0) is never captured here: only its refusal is checked."""
+No gru trainer creates a stream of its own: `test_no_gru_form_is_refused_or_creates_a_stream` counts them."""
 import os
 
 import numpy as np
@@ -9,7 +9,6 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-SIDE_STREAM = 'side-stream overlap (gru) is not captured'
 
 
 def _need_gpu():
@@ -46,33 +45,54 @@ def _val(v):
     return v[0] if isinstance(v, tuple) else v
 
 
+def _count_new_streams(monkeypatch):
+    """Replace `torch.cuda.Stream` by a subclass that counts the streams CREATED through it (a wrapper object around an existing
+    stream - what `torch.cuda.current_stream()` returns - passes stream_id / stream_ptr and is not one)."""
+    made = []
+
+    class CountingStream(torch.cuda.Stream):
+        def __new__(cls, *args, **kwargs):
+            if 'stream_id' not in kwargs and 'stream_ptr' not in kwargs:
+                made.append((args, kwargs))
+            return super().__new__(cls, *args, **kwargs)
+    monkeypatch.setattr(torch.cuda, 'Stream', CountingStream)
+    return made
+
+
 @pytest.mark.parametrize('algo', ['sac', 'td3'])
-def test_refusal_is_lifted_for_the_batched_form_only(algo, monkeypatch):
-    """The test that shows the feature: before it, every gru trainer was refused."""
+def test_no_gru_form_is_refused_or_creates_a_stream(algo, monkeypatch):
+    """Both forms of the gru trainer are linear launch sequences on the current stream: `GraphedUpdate` refuses neither, and building
+    the trainer and running two eager updates creates no `torch.cuda.Stream` (what keeps a fork / join out of every capture)."""
     _need_gpu()
     from offpolicy_rnn.algorithm.graphed_update import GraphedUpdate
-    monkeypatch.setenv('RESEL_GRU_BATCH', '1')
-    alg = _small(algo)
-    assert alg.overlap_value_embedding and alg.gru_batch
-    assert GraphedUpdate.refusal(alg) is None
-    monkeypatch.setenv('RESEL_GRU_BATCH', '0')
-    alg = _small(algo)
-    assert alg.overlap_value_embedding and not alg.gru_batch
-    assert GraphedUpdate.refusal(alg) == SIDE_STREAM
+    made = _count_new_streams(monkeypatch)
+    probe = torch.cuda.Stream()                                     # the counter sees a stream that IS created ...
+    assert len(made) == 1 and isinstance(torch.cuda.current_stream(), torch.cuda.Stream) and len(made) == 1     # ... and only those
+    del made[:], probe
+    for batched in (True, False):
+        monkeypatch.setenv('RESEL_GRU_BATCH', '1' if batched else '0')
+        alg = _small(algo)
+        assert alg.gru_batch == batched and not alg.share_policy_pass
+        assert GraphedUpdate.refusal(alg) is None
+        for _ in range(2):
+            log = dict(alg.train_one_batch())
+            alg.grad_num += 1
+            assert all(np.isfinite(_val(v)) for v in log.values())
+        torch.cuda.synchronize()
+        assert made == [], (batched, made)
 
 
 @pytest.mark.parametrize('algo,per,n_upd', [('td3', 1, 4), ('sac', 2, 4), ('sac', 2, 8), ('td3', 1, 8)])
 def test_batched_update_equals_the_serial_form_bit_for_bit(algo, per, n_upd, monkeypatch):
     """Batched eager update (embedding towers in lockstep, `ops.gru_seq_multi`; a prefetched embedding is placed by `cat_into`, the
-    critic's differentiated pass included) against the serial form (RESEL_OVERLAP_EMBEDDING=0: one recurrence after another, the last
+    critic's differentiated pass included) against the serial form (RESEL_GRU_BATCH=0: one recurrence after another, the last
     fc of the tower writing into the head's row buffer): logs and flat parameters - forward values AND gradients - bit for bit."""
     _need_gpu()
     runs = []
     for batched in (True, False):
-        monkeypatch.setenv('RESEL_GRU_BATCH', '1')
-        monkeypatch.setenv('RESEL_OVERLAP_EMBEDDING', '1' if batched else '0')
+        monkeypatch.setenv('RESEL_GRU_BATCH', '1' if batched else '0')
         alg = _small(algo, per, seed=5)
-        assert alg.gru_batch == batched and alg.overlap_value_embedding == batched
+        assert alg.gru_batch == batched
         torch.manual_seed(200)
         np.random.seed(200)
         logs = []
@@ -80,8 +100,6 @@ def test_batched_update_equals_the_serial_form_bit_for_bit(algo, per, n_upd, mon
             logs.append(dict(alg.train_one_batch()))
             alg.grad_num += 1
         torch.cuda.synchronize()
-        if batched:
-            assert alg._target_stream is None and alg._side_streams == []
         runs.append((logs, _state(alg)))
     for a, b in zip(runs[0][0], runs[1][0]):
         assert set(a) == set(b)
@@ -91,8 +109,7 @@ def test_batched_update_equals_the_serial_form_bit_for_bit(algo, per, n_upd, mon
         assert torch.equal(a, b), (nm, (a - b).abs().max().item())
 
 
-@pytest.mark.parametrize('algo,per,clip,ragged', [('sac', 1, False, False), ('td3', 2, False, False), ('sac', 1, True, False), ('sac', 1, False, True)])
-def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, monkeypatch):
+def _graphed_against_eager(algo, per, clip, ragged, batched, monkeypatch):
     """Graphed against eager, batched form, the tolerances of the fp32 families.  (The eager step takes the AdamW bias corrections the
     captured step reads from device words, `ops.adamw_bias_corrections`: with the fp32 `1 - powf(beta, t)` the eager entry point used
     before, the (td3, per 2) row missed rtol 2e-5 in one of 23 544 policy parameters by a factor 1.3 after 8 updates - a deterministic
@@ -102,7 +119,7 @@ def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, mon
     from test_host_logic import _push, _synth
     from offpolicy_rnn.algorithm.graphed_update import GraphedUpdate
     _quiet(monkeypatch)
-    monkeypatch.setenv('RESEL_GRU_BATCH', '1')
+    monkeypatch.setenv('RESEL_GRU_BATCH', '1' if batched else '0')
     extra = dict(value_max_gradnorm=0.05, policy_max_gradnorm=0.01) if clip else {}
 
     n_upd = (16 if ragged else 4) * per
@@ -121,6 +138,7 @@ def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, mon
         logs_e.append(dict(eager.train_one_batch()))
         eager.grad_num += 1
     graphed = _small(algo, per, ragged, **extra)
+    assert eager.gru_batch == batched and graphed.gru_batch == batched
     assert GraphedUpdate.refusal(graphed) is None
     g = GraphedUpdate(graphed, warmup=1, max_graphs=2 if ragged else 4)
     logs_g = []
@@ -135,7 +153,6 @@ def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, mon
     assert ragged or (g.graph is not None and g.eager_fallbacks <= 3 * per)
     if per == 2 and not ragged:
         assert {k[-1] for k in g.graphs} == {True, False}, 'one recording with and one without the actor step'
-    assert graphed._target_stream is None and graphed._side_streams == []
     rtol, atol = 2e-5, (2e-7 if n_upd <= 16 else 1e-6)
     for nm, a, b in zip(('policy', 'value', 'target value', 'log alpha'), _state(graphed), _state(eager)):
         np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), rtol=rtol, atol=atol, err_msg=nm)
@@ -145,6 +162,16 @@ def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, mon
             ve, vg = _val(le[k]), _val(lg[k])
             assert abs(ve - vg) <= rtol * max(1.0, abs(ve)), (k, ve, vg)
     g.close()
+
+
+@pytest.mark.parametrize('algo,per,clip,ragged', [('sac', 1, False, False), ('td3', 2, False, False), ('sac', 1, True, False), ('sac', 1, False, True)])
+def test_graphed_gru_update_equals_the_eager_update(algo, per, clip, ragged, monkeypatch):
+    _graphed_against_eager(algo, per, clip, ragged, True, monkeypatch)
+
+
+def test_graphed_serial_gru_update_equals_the_eager_update(monkeypatch):
+    """The serial form (RESEL_GRU_BATCH=0) through `GraphedUpdate`: same tolerances as the batched rows."""
+    _graphed_against_eager('sac', 2, False, False, False, monkeypatch)
 
 
 @pytest.mark.parametrize('per', [1, 2])

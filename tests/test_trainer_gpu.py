@@ -207,17 +207,17 @@ def test_shared_policy_pass_equals_two_passes_gpu(rnn, algo, tol, monkeypatch):
     np.testing.assert_allclose(runs[0][1].cpu(), runs[1][1].cpu(), rtol=tol, atol=tol * 1e-1)
 
 
-def test_gru_stream_overlap_equals_serial_order(monkeypatch):
-    """gru: the graph-free passes run on side streams next to the critic forward / the policy forward.  Streams change the
-    schedule, not the arithmetic: same seeds -> the same logs and parameters as the single-stream order, bit for bit."""
+def test_gru_batched_equals_serial_order(monkeypatch):
+    """gru: the independent embedding passes of a phase share one recurrence launch (RESEL_GRU_BATCH=1, the default) or run one after
+    another (0).  Batching changes the launches, not the arithmetic: same seeds -> the same logs and parameters, bit for bit."""
     from offpolicy_rnn import alg_init
     runs = []
     for flag in ('1', '0'):
-        monkeypatch.setenv('RESEL_OVERLAP_EMBEDDING', flag)
+        monkeypatch.setenv('RESEL_GRU_BATCH', flag)
         torch.manual_seed(5)
         np.random.seed(5)
         alg = alg_init(make_parameter('gru', sac_batch_size=60))
-        assert alg.overlap_value_embedding == (flag == '1') and not alg.share_policy_pass
+        assert alg.gru_batch == (flag == '1') and not alg.share_policy_pass
         rs = np.random.RandomState(9)
         for n in [12] * 8:
             o, a, r = _synth(rs, n, 5, 3)
