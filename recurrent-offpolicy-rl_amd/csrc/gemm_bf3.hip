@@ -2,9 +2,9 @@
 //
 //     C[b][m][n] = epi( sum_k A[b](m, k) * B[b](n, k) )          same contract and operand layouts as gemm_f32.hip
 //
-// Product formation (resel_gemm_f32 modes 6 / 9, gemm_f32.hip 'SPLIT'): every fp32 operand element x is written exactly as
+// Product formation (resel_gemm_f32 mode 6, gemm_f32.hip 'SPLIT'): every fp32 operand element x is written exactly as
 // x1 + x2 + x3, three bf16 values obtained by truncation; a bf16 x bf16 product is exact in fp32 and v_mfma_f32_32x32x16_bf16
-// accumulates the plane products in fp32.  Mode 9 keeps all nine plane products, mode 6 drops a2 b3, a3 b2, a3 b3 (each at
+// accumulates the plane products in fp32.  Mode 6 keeps six of the nine plane products: it drops a2 b3, a3 b2, a3 b3 (each at
 // most 2^-24 |a b|).  Mode 3 ("bf16x3", what torch.set_float32_matmul_precision('high') names) keeps two planes per operand -
 // 16 significant bits - and the products a1 b1 + a1 b2 + a2 b1: every dropped term is at most 2^-16 |a b|; half the matrix
 // instructions and two thirds of the split / LDS work of mode 6.  The first edition kept fp32 tiles in LDS and every wave split the fragments it read: with 2 x 2 waves
@@ -23,11 +23,10 @@
 // step s + 1's slab 0 under the second half of slab 1's MFMAs.
 // A third edition for mode 2 (producer / consumer waves, `gemm_ws_kernel` further down) takes the shapes with whole K steps; this one keeps the rest.
 // Blocks are persistent (256 = one per CU) and walk items exactly as in gemm_f32.hip: whole tiles, and K slices for the last
-// partly filled round and for weight gradients, summed by a fix-up kernel in a fixed order (deterministic, no atomics).
-#include "resel_common.h"
-#include <algorithm>
-#include <atomic>
-#include <cstdlib>
+// partly filled round and for weight gradients, summed by a fix-up kernel in a fixed order (deterministic, no atomics): the item
+// walk, the slice plan and the fix-up kernel are gemm_splitk.h, shared with gemm_f32.hip.
+// SPLIT of gemm_bf3_kernel is 2, 3 or 6; gemm_ws_kernel is mode 2 only (EPI: 0 the plain epilogues, 4 / 5 the fused ones).
+#include "gemm_splitk.h"
 #include <type_traits>
 
 namespace {
@@ -35,7 +34,7 @@ using namespace resel;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int BM = 256, BN = 128, BK = 32;
+constexpr int BM = 256, BN = 128;
 constexpr int NTH = 512;
 constexpr int GRID = 256;
 constexpr int TILE = BM * BN;
@@ -64,31 +63,6 @@ struct Params {
     float* red;
     int redrows;                                 // act 4: partial rows per batch member in `red` (2 mt + one for the rows the host entry handles apart)
 };
-
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : fast_exp(x) - 1.f; }
-
-__device__ __forceinline__ void tile_origin(const Params& p, int t, int& z, int& m0, int& n0) {
-    const int ntile = p.mt * p.nt;
-    z = t / ntile;
-    const int tt = t - z * ntile;
-    const int q = ntile / 8, r = ntile % 8, x = tt & 7, j = tt >> 3;
-    const int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-    m0 = (bid / p.nt) * BM;
-    n0 = (bid % p.nt) * BN;
-}
-struct Item { int m0, n0, z, kbeg, kend, split; };
-__device__ __forceinline__ Item decode(const Params& p, int it) {
-    Item o;
-    int t = it;
-    o.kbeg = 0; o.kend = p.K; o.split = 0;
-    if (it >= p.nfull) {
-        const int idx = it - p.nfull, tr = idx / p.nsl, sl = idx - tr * p.nsl;
-        t = p.nfull + tr;
-        o.kbeg = sl * p.kslice; o.kend = min(p.K, o.kbeg + p.kslice); o.split = idx + 1;
-    }
-    tile_origin(p, t, o.z, o.m0, o.n0);
-    return o;
-}
 
 // byte offset of (row, 16-byte chunk c = k / 8) inside one plane
 __device__ __forceinline__ int plane_off(int row, int c) {
@@ -415,7 +389,6 @@ __device__ __forceinline__ void mfma_term(f32x16 (&acc)[2][2], const Frag& f) {
 template <int SPLIT>
 __device__ __forceinline__ void mfma_small(f32x16 (&acc)[2][2], const Frag& f) {
     if (SPLIT == 3 || SPLIT == 2) return;           // two planes per operand: a1 b1 + a1 b2 + a2 b1 only (mfma_lead)
-    if (SPLIT == 9) { mfma_term<2, 2>(acc, f); mfma_term<2, 1>(acc, f); mfma_term<1, 2>(acc, f); }
     mfma_term<2, 0>(acc, f); mfma_term<0, 2>(acc, f); mfma_term<1, 1>(acc, f);
 }
 __device__ __forceinline__ void mfma_lead(f32x16 (&acc)[2][2], const Frag& f) {
@@ -465,7 +438,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
     int p_item = blockIdx.x, p_k0, p_kend;
     bool p_live = true;
     auto p_open = [&]() {
-        const Item it = decode(p, p_item);
+        const Item it = decode<BM, BN>(p, p_item);
         sa.init(p.A + (int64_t)it.z * p.sA, p.lda, p.M, it.m0, it.kbeg, tid);
         sb.init(p.B + (int64_t)it.z * p.sB, p.ldb, p.N, it.n0, it.kbeg, tid);
         p_k0 = it.kbeg; p_kend = it.kend;
@@ -514,7 +487,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
     read_a<NP>(f0, fa[0]); read_b<NPB>(f0, fb[0]);
     int cur_st = 0;
     for (int c_item = blockIdx.x; c_item < total; c_item += G) {
-        const Item cur = decode(p, c_item);
+        const Item cur = decode<BM, BN>(p, c_item);
         float zero = 0.f;
         asm volatile("" : "+v"(zero));              // opaque: or 64 registers of hoisted zeros stay live across the K loop
         f32x16 acc[2][2];
@@ -537,7 +510,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
                 }
             }
             BF3_FENCE();
-            // ---- region A: 36 (54) matrix instructions; in their shadow slab 1's fragment reads, the split + LDS stores of step
+            // ---- region A: 36 matrix instructions (two-plane modes: 12); in their shadow slab 1's fragment reads, the split + LDS stores of step
             // s + 1's tile and the global loads of step s + 2 into the registers the split has just released
             read_a<NP>(f1, fa[1] + so); read_b<NPB>(f1, fb[1] + so);
             mfma_small<SPLIT>(acc, f0);
@@ -556,14 +529,13 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
                     if (i >= 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
             } else {
-                constexpr int NMA = SPLIT == 9 ? 60 : 36;
 #pragma unroll
-                for (int i = 0; i < NMA; ++i) {
+                for (int i = 0; i < 36; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                 // one MFMA
                     if (i < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // one LDS read
-                    __builtin_amdgcn_sched_group_barrier(0x002, SPLIT == 9 ? 3 : 5, 0);   // vector instructions
+                    __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);     // vector instructions
                     if (i >= 4 && i < 4 + 18) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // one LDS write
-                    if (i >= NMA - 8) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);          // one global load
+                    if (i >= 36 - 8) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);           // one global load
                 }
             }
             BF3_FENCE();
@@ -695,24 +667,20 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 //   * one `s_barrier` per K step for all eight waves: stage s + 1 written, stage s read;
 //   * whole C tiles leave through a wave-private 5 KB LDS scratch (the third A plane of the stages, unused in mode 2) as 16-byte
 //     stores of eight whole 128-byte lines: 32 store instructions per wave and tile instead of 128 (a wave may have 63 in flight).
-// 243-245 registers, no scratch, two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
+// 256 registers, 24 bytes of scratch (EPI 5: 84-92, EPI 4: 288), two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
 // us): fwd [T,384] -> 256 77 -> 67, [T,256] -> 256 55 -> 48, [T,256] -> 1024 171 -> 150, [T,384] -> 2048 420 -> 365.
 constexpr int NTH_WS = 512;
 constexpr int WS_LDS = 2 * STAGE;
 #define WS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-template <bool AKC, bool BKC, int SPLIT, int EPI = 0>
+template <bool AKC, bool BKC, int EPI = 0>
 __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];           // 2 stages
-    constexpr bool F16 = SPLIT == 2;
-    constexpr int NP = (SPLIT == 3 || SPLIT == 2) ? 2 : 3;
-    constexpr int NPB = (SPLIT == 3 || SPLIT == 2) ? 2 : 3;
     const int tid = threadIdx.x;
     const int total = p.nfull + p.nsplit * p.nsl;
     const int G = gridDim.x;
     if ((int)blockIdx.x >= total) return;
-    float sa_ = 1.f, sb_ = 1.f;
-    if (F16) { sa_ = f16_scale(amax_read(p.amaxA)); sb_ = f16_scale(amax_read(p.amaxB)); }
+    const float sa_ = f16_scale(amax_read(p.amaxA)), sb_ = f16_scale(amax_read(p.amaxB));
     asm volatile("" :: "v"(sa_), "v"(sb_));            // the scales have landed HERE: no compiler-counted load is pending inside the producers' loop
 
     if (__builtin_amdgcn_readfirstlane(tid) >= 256) {                   // a scalar condition: the two roles are separate paths to the compiler too
@@ -734,13 +702,13 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
         f32x4a ra[2][2][SA::NR], rb[2][2][SB::NR];                      // [register set][virtual thread]
         int nsteps = 0;
         for (int it = blockIdx.x; it < total; it += G) {
-            const Item i = decode(p, it);
+            const Item i = decode<BM, BN>(p, it);
             nsteps += (i.kend - i.kbeg + BK - 1) / BK;
         }
         int p_item = blockIdx.x, p_k0 = 0, p_kend = 0;
         bool p_live = true;
         auto p_open = [&]() {
-            const Item it = decode(p, p_item);
+            const Item it = decode<BM, BN>(p, p_item);
             const float* Ab = p.A + (int64_t)it.z * p.sA;
             const float* Bb = p.B + (int64_t)it.z * p.sB;
             a0.init(Ab, p.lda, p.M, it.m0, it.kbeg, pt); a1.init(Ab, p.lda, p.M, it.m0, it.kbeg, pt + 256);
@@ -775,7 +743,6 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             all(a0, ra[S][0]); all(a1, ra[S][1]); all(b0, rb[S][0]); all(b1, rb[S][1]);
             advance();
         };
-        constexpr int FA = F16 ? 1 : 0, FB = F16 ? 2 : 0;
         // MODE 0: steady state - two sets (24 loads) in flight, every unit waits for its own loads and reloads.  MODE 1: everything has
         // landed (tail): split and store only.  MODE 2: as 1, then reload the set and wait for it (a tail step that still has a successor).
         auto recycle = [&](auto SET, auto MODEC) {
@@ -785,19 +752,19 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             uint32_t st_off = S * STAGE;
             asm volatile("" : "+s"(st_off));               // opaque: the plane addresses are formed per piece (one add), not kept in eight registers across the loop
             char* st = lds + st_off;
-            auto one = [&](auto& src, auto& regs, char* pl, f32x2_t sc, auto PLc, auto NPc, auto Fc) {
-                constexpr int PL = decltype(PLc)::value, NPP = decltype(NPc)::value, FF = decltype(Fc)::value;
+            auto one = [&](auto& src, auto& regs, char* pl, f32x2_t sc, auto PLc, auto WIDEc) {      // WIDE: the A operand's planes (split_pair_f16)
+                constexpr int PL = decltype(PLc)::value;
+                constexpr bool WIDE = decltype(WIDEc)::value;
                 typedef std::remove_reference_t<decltype(src)> ST;
                 if constexpr (ST::is_kc) {
 #pragma unroll
                     for (int i = 0; i < ST::NR; ++i) {
                         if (LOAD) asm volatile("s_waitcnt vmcnt(23)" : "+v"(regs[i]) :: "memory");
                         const float4 v = make_float4(regs[i].x, regs[i].y, regs[i].z, regs[i].w);
-                        const P3 sp = FF == 1 ? split4_f16<true>(v, sc) : FF == 2 ? split4_f16<false>(v, sc) : split4<NPP>(v);
+                        const P3 sp = split4_f16<WIDE>(v, sc);
                         char* d = pl + src.loff[0] + 4096 * i;
                         *reinterpret_cast<uint2*>(d) = sp.p1;
                         *reinterpret_cast<uint2*>(d + PL) = sp.p2;
-                        if (NPP == 3) *reinterpret_cast<uint2*>(d + 2 * PL) = sp.p3;
                         if (MODE != 1) aload(regs[i], src.base, src.piece_off(i));
                     }
                 } else {
@@ -806,7 +773,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     else { if (LOAD) asm volatile("s_waitcnt vmcnt(22)" : "+v"(regs[0]), "+v"(regs[1]) :: "memory"); }
 #pragma unroll
                     for (int i = 0; i < ST::NR; ++i) t[i] = make_float4(regs[i].x, regs[i].y, regs[i].z, regs[i].w);
-                    src.template store_from<PL, NPP, FF>(t, pl, sc);
+                    src.template store_from<PL, 2, WIDE ? 1 : 2>(t, pl, sc);
                     if (MODE != 1) {
 #pragma unroll
                         for (int i = 0; i < ST::NR; ++i) aload(regs[i], src.base, src.off[i]);
@@ -815,10 +782,10 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             };
             using IA = std::integral_constant<int, PLA>;
             using IB = std::integral_constant<int, PLB>;
-            one(a0, ra[S][0], st, scA, IA{}, std::integral_constant<int, NP>{}, std::integral_constant<int, FA>{});
-            one(a1, ra[S][1], st, scA, IA{}, std::integral_constant<int, NP>{}, std::integral_constant<int, FA>{});
-            one(b0, rb[S][0], st + 3 * PLA, scB, IB{}, std::integral_constant<int, NPB>{}, std::integral_constant<int, FB>{});
-            one(b1, rb[S][1], st + 3 * PLA, scB, IB{}, std::integral_constant<int, NPB>{}, std::integral_constant<int, FB>{});
+            one(a0, ra[S][0], st, scA, IA{}, std::true_type{});
+            one(a1, ra[S][1], st, scA, IA{}, std::true_type{});
+            one(b0, rb[S][0], st + 3 * PLA, scB, IB{}, std::false_type{});
+            one(b1, rb[S][1], st + 3 * PLA, scB, IB{}, std::false_type{});
             if (MODE != 1) advance();
         };
         auto landed = [&]() {                            // every load issued so far has landed, in every register of both sets
@@ -864,7 +831,6 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
     // ---------------------------------------------------------------------------------------------------- consumers
     // wave w: rows 128 (w >> 1) .. + 127, columns 64 (w & 1) .. + 63 of the 256 x 128 block tile = 4 x 2 tiles of 32 x 32 = 128 accumulator
     // registers; fragments of a 16-k slab: A 2 planes x 4 tiles + B 2 planes x 2 tiles = 12 ds_read_b128 (48 registers), two sets
-    static_assert(SPLIT == 2, "the 4 + 4 wave form exists for mode 2");
     const float unscale = (1.f / sa_) * (1.f / sb_);
     const int lane = tid & 63, w = tid >> 6;
     const int wm = (w >> 1) * 128, wn = (w & 1) * 64;
@@ -918,7 +884,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
     // the epilogue instead of under the item's last matrix instructions (their stage stays valid until this wave passes the next barrier)
     constexpr bool DEFER_F0 = EPI == 4;
     for (int c_item = blockIdx.x; c_item < total; c_item += G) {
-        const Item cur = decode(p, c_item);
+        const Item cur = decode<BM, BN>(p, c_item);
         if (DEFER_F0 && c_item != (int)blockIdx.x) rd(f0, fa[0] + cur_st * STAGE, fb[0] + cur_st * STAGE);
         float zero = 0.f;
         asm volatile("" : "+v"(zero));
@@ -1339,344 +1305,19 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
     amax_publish_wave(cmax, p.amaxC);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Fourth edition (experimental, RESEL_GEMM_EDITION=4; mode 2, A [rows][K], whole K steps, one batch member, no K slices): a 256 x 256
-// BLOCK TILE - a third fewer L2 -> CU bytes per product than 256 x 128 (profiles/r04_gemm.md: the K loop is byte-bound).  The 1 024
-// accumulator registers per lane of such a tile do not fit the producer / consumer form (four consumer waves x 256 + fragments), so
-// every wave does everything again (second edition's structure): 8 waves as 2 x 4, wave tile 128 x 64 = 128 accumulator registers,
-// ONE fragment set (48 registers: the other wave of the SIMD covers the LDS round trips), 32 staging registers (each thread loads,
-// splits and stores 1 / 512 of both tiles: four 16-byte pieces per operand and K step).  LDS: two planes per operand, 64 KB per stage,
-// two stages; the epilogue turns its tiles through the stage that has just been consumed (a barrier per item keeps a fast wave's
-// next plane stores out of a slow wave's scratch).
-constexpr int BN8 = 256;
-constexpr int PLB8 = BN8 * ROWB;
-constexpr int STAGE8 = 2 * PLA + 2 * PLB8;          // 65 536 bytes
-constexpr int W8_LDS = 2 * STAGE8;
-
-__device__ __forceinline__ void tile_origin8(const Params& p, int t, int& m0, int& n0) {
-    const int ntile = p.mt * p.nt;                   // p.nt counts 256-column tiles here
-    const int q = ntile / 8, r = ntile % 8, x = t & 7, j = t >> 3;
-    const int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-    m0 = (bid / p.nt) * BM;
-    n0 = (bid % p.nt) * BN8;
-}
-
-template <bool BKC>
-__global__ __launch_bounds__(512, 1) void gemm_w8_kernel(Params p) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const float sa_ = f16_scale(amax_read(p.amaxA)), sb_ = f16_scale(amax_read(p.amaxB));
-    const f32x2_t scA = {sa_, 2048.f * sa_}, scB = {sb_, 2048.f * sb_};
-    const float unscale = (1.f / sa_) * (1.f / sb_);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = (w >> 2) * 128, wn = (w & 3) * 64;
-    const int li = lane & 31, lh = lane >> 5;
-    const int total = p.nfull, G = gridDim.x;
-    if ((int)blockIdx.x >= total) return;
-
-    Src<true, BM> sa;
-    Src<BKC, BN8> sb;
-    sa.init_lds(tid);
-    sb.init_lds(tid);
-    int p_item = blockIdx.x, p_k0 = 0;
-    bool p_live = true;
-    auto p_open = [&]() {
-        int m0, n0;
-        tile_origin8(p, p_item, m0, n0);
-        sa.init(p.A, p.lda, p.M, m0, 0, tid);
-        sb.init(p.B, p.ldb, p.N, n0, 0, tid);
-        p_k0 = 0;
-    };
-    auto produce = [&]() {                          // global loads of the next K step in program order (also across items)
-        if (!p_live) return;
-        sa.load(p_k0, p.K);
-        sb.load(p_k0, p.K);
-        p_k0 += BK;
-        if (p_k0 >= p.K) {
-            p_item += G;
-            if (p_item < total) p_open(); else p_live = false;
-        }
-    };
-    auto stage_store = [&](int st) {
-        sa.template store<PLA, 2, 1>(lds + st * STAGE8, scA);
-        sb.template store<PLB8, 2, 2>(lds + st * STAGE8 + 2 * PLA, scB);
-    };
-    const char* fa[2];
-    const char* fb[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        fa[s] = lds + wm * ROWB + plane_off(li, 2 * s + lh);
-        fb[s] = lds + 2 * PLA + wn * ROWB + plane_off(li, 2 * s + lh);
-    }
-    struct F4 { f16x8 a[2][4], b[2][2]; };
-    auto rd = [&](F4& f, const char* pa, const char* pb) {
-#pragma unroll
-        for (int pi = 0; pi < 2; ++pi) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) f.a[pi][t] = *reinterpret_cast<const f16x8*>(pa + pi * PLA + t * 32 * ROWB);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) f.b[pi][t] = *reinterpret_cast<const f16x8*>(pb + pi * PLB8 + t * 32 * ROWB);
-        }
-    };
-    f32x16 acc[4][2];
-    auto mm = [&](const F4& f) {                    // a2 (2^-11 b1) + a1 b2 + a1 b1, the small terms first
-        const f16x8 k = {(_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f,
-                         (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f};
-        const f16x8 bs0 = f.b[0][0] * k, bs1 = f.b[0][1] * k;
-#ifdef BF3_AB_NOMFMA
-#pragma unroll
-        for (int a = 0; a < 4; ++a) asm volatile("" :: "v"(f.a[0][a]), "v"(f.a[1][a]), "v"(bs0), "v"(bs1), "v"(f.b[0][0]), "v"(f.b[0][1]), "v"(f.b[1][0]), "v"(f.b[1][1]));
-        return;
-#endif
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[1][a], bs0, acc[a][0], 0, 0, 0);
-            acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[1][a], bs1, acc[a][1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 1; q >= 0; --q)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[0][a], f.b[q][0], acc[a][0], 0, 0, 0);
-                acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[0][a], f.b[q][1], acc[a][1], 0, 0, 0);
-            }
-    };
-    float cmax = 0.f;
-    F4 f;
-    p_open();
-    produce();
-    stage_store(0);
-    produce();
-    __syncthreads();
-    int cur_st = 0;
-    for (int c_item = blockIdx.x; c_item < total; c_item += G) {
-        int m0, n0;
-        tile_origin8(p, c_item, m0, n0);
-        float zero = 0.f;
-        asm volatile("" : "+v"(zero));
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = zero;
-        float bv[2] = {0.f, 0.f};
-        for (int c_k0 = 0; c_k0 < p.K; c_k0 += BK) {
-            const int so = cur_st * STAGE8;
-            const bool fast = p_live && p_k0 + BK <= p.K;
-            if (c_k0 + BK >= p.K && p.bias) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int n = n0 + wn + 32 * b + li;
-                    bv[b] = p.bias[n < p.N ? n : 0];
-                }
-            }
-            BF3_FENCE();
-            rd(f, fa[0] + so, fb[0] + so);
-            mm(f);
-            stage_store(cur_st ^ 1);                 // the tile of step s + 1 (its loads were issued a step ago)
-            BF3_FENCE();
-            rd(f, fa[1] + so, fb[1] + so);
-            mm(f);
-            sa.load_sched(fast);                     // the tile of step s + 2 into the registers the split has released
-            sb.load_sched(fast);
-            BF3_FENCE();
-#ifdef BF3_AB_NOBAR
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage s + 1 is complete; every wave has read stage s
-#endif
-            BF3_FENCE();
-            if (fast) {
-                p_k0 += BK;
-                if (p_k0 >= p.K) {
-                    p_item += G;
-                    if (p_item < total) p_open(); else p_live = false;
-                }
-            } else {
-                produce();
-            }
-            BF3_FENCE();
-            cur_st ^= 1;
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] *= unscale;
-        float* C = p.C;
-#ifdef BF3_AB_NOEPI
-        if (lane == 0) C[(int64_t)m0 * p.ldc + n0 + w] = acc[0][0][0] + acc[1][1][1] + acc[2][0][2] + acc[3][1][3];
-        __syncthreads();
-        continue;
-#endif
-        const bool full_m = m0 + BM <= p.M;
-        if (full_m && n0 + BN8 <= p.N) {
-            // whole tiles leave through a wave-private 5 KB scratch in the stage that has just been consumed (cur_st now names the OTHER one,
-            // which already holds the next item's first tile)
-            char* sc = lds + (cur_st ^ 1) * STAGE8 + w * 5120;
-            float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
-            const float4* rdp = reinterpret_cast<const float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    float v[16];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
-                    if (p.act == 1) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
-                    }
-                    if (p.act == 3) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
-                    }
-                    if (p.amaxC.slot) {
-#pragma unroll
-                        for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
-                    }
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = v[e];
-                    float* q = C + (int64_t)(m0 + wm + 32 * a + (lane >> 3)) * p.ldc + n0 + wn + 32 * b + 4 * (lane & 7);
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const float4 t = rdp[g * 8 * 10];
-                        typedef float f4v __attribute__((ext_vector_type(4)));
-                        __builtin_nontemporal_store(f4v{t.x, t.y, t.z, t.w}, reinterpret_cast<f4v*>(q + (int64_t)(8 * g) * p.ldc));
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int n = n0 + wn + 32 * b + li;
-                if (n >= p.N) continue;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    float v[16];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
-                    if (p.act == 1) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
-                    }
-                    if (p.act == 3) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
-                    }
-                    const int mb = m0 + wm + 32 * a + 4 * lh;
-                    float* crow = C + (int64_t)mb * p.ldc + n;
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int dm = (e & 3) + 8 * (e >> 2);
-                        if (mb + dm < p.M) crow[(int64_t)dm * p.ldc] = v[e];
-                    }
-                    if (p.amaxC.slot) {
-#pragma unroll
-                        for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
-                    }
-                }
-            }
-        }
-        __syncthreads();                             // the scratch sits in the stage the next item's first step stores into
-    }
-    amax_publish_wave(cmax, p.amaxC);
-}
-
-// C tile = epi(sum over the K slices of a split tile), fixed summation order: as gemm_fixup_kernel of gemm_f32.hip for 256 x 128 tiles
-__global__ __launch_bounds__(256) void gemm_bf3_fixup_kernel(Params p) {
-    __shared__ float4 part[3][64];
-    const int tr = blockIdx.y, q = threadIdx.y;
-    const int e = blockIdx.x * 64 + threadIdx.x, ml = e >> 5, nl = 4 * (e & 31);
-    const float* s = p.slab + (int64_t)tr * p.nsl * TILE + ml * BN + nl;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    int i = q;
-    for (; i + 12 < p.nsl; i += 16) {
-        const float4 u0 = ld4(s + (int64_t)i * TILE), u1 = ld4(s + (int64_t)(i + 4) * TILE);
-        const float4 u2 = ld4(s + (int64_t)(i + 8) * TILE), u3 = ld4(s + (int64_t)(i + 12) * TILE);
-        v.x = (((v.x + u0.x) + u1.x) + u2.x) + u3.x; v.y = (((v.y + u0.y) + u1.y) + u2.y) + u3.y;
-        v.z = (((v.z + u0.z) + u1.z) + u2.z) + u3.z; v.w = (((v.w + u0.w) + u1.w) + u2.w) + u3.w;
-    }
-    for (; i < p.nsl; i += 4) {
-        const float4 u = ld4(s + (int64_t)i * TILE);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
-    if (q) part[q - 1][threadIdx.x] = v;
-    __syncthreads();
-    if (q) return;
-    const float4 g1 = part[0][threadIdx.x], g2 = part[1][threadIdx.x], g3 = part[2][threadIdx.x];
-    float o[4] = {(v.x + g1.x) + (g2.x + g3.x), (v.y + g1.y) + (g2.y + g3.y), (v.z + g1.z) + (g2.z + g3.z), (v.w + g1.w) + (g2.w + g3.w)};
-    int z, m0, n0;
-    tile_origin(p, p.nfull + tr, z, m0, n0);
-    const int m = m0 + ml, n = n0 + nl;
-    float cmax = 0.f;
-    if (m < p.M && n < p.N) {
-        float* c = p.C + (int64_t)z * p.sC + (int64_t)m * p.ldc + n;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (n + j >= p.N) break;
-            float x = o[j] + (p.bias ? p.bias[(int64_t)z * p.sBias + n + j] : 0.f);
-            if (p.act == 1) x = elu1(x);
-            if (p.act == 3) x = softplus_nb(x);
-            if (p.act == 2) x += c[j];
-            c[j] = x;
-            cmax = fmaxf(cmax, __builtin_fabsf(x));
-        }
-    }
-    amax_publish_wave(cmax, p.amaxC);                // q == 0: one whole wave (threadIdx.y selects the wave)
-}
-
-struct Plan { int nfull, nsplit, nsl, kslice; };
-// K slices for the tiles of a partly filled last round pay a fix-up launch (~6 us) and the slab round trip: only worth it when a whole
-// tile's K loop is long
-constexpr int g_split_min_ksteps = 4;   // thresholds 12 / 20 / 40 measured equal or slower on the whole update (profiles/r05_gemm.md)
-inline Plan make_plan(int M, int N, int K, int batch) {
-    const long nbt = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch;
-    const int ksteps = (K + BK - 1) / BK;
-    Plan pl{(int)nbt, 0, 1, ksteps * BK};
-    const int r = (int)(nbt % GRID);
-    if (r == 0 || r > GRID / 2 || ksteps < g_split_min_ksteps) return pl;
-    int s = std::min(GRID / r, ksteps / 2);
-    const int per = (ksteps + s - 1) / s;
-    s = (ksteps + per - 1) / per;
-    if (s < 2) return pl;
-    pl.nfull = (int)(nbt - r); pl.nsplit = r; pl.nsl = s; pl.kslice = per * BK;
-    return pl;
-}
-
+// one flag table per kernel instantiation (launch_big_lds)
 template <bool AKC, bool BKC, int SP>
 int launch_one(const Params& p, dim3 grid, hipStream_t s) {
-    // the attribute is per device (and the first call may come from any thread): one flag per device id, set after the call succeeds
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return RESEL_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)gemm_bf3_kernel<AKC, BKC, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE) != hipSuccess)
-            return RESEL_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    launch_timed(RESEL_PROF_GEMM, gemm_bf3_kernel<AKC, BKC, SP>, grid, dim3(NTH), (size_t)(2 * STAGE), s, p);
-    return RESEL_OK;
+    return launch_big_lds(gemm_bf3_kernel<AKC, BKC, SP>, attr_set, grid, dim3(NTH), 2 * STAGE, s, p);
 }
-
-template <bool AKC, bool BKC, int SP, int EPI = 0>
+template <bool AKC, bool BKC, int EPI = 0>
 int launch_ws(const Params& p, dim3 grid, hipStream_t s) {
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return RESEL_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)gemm_ws_kernel<AKC, BKC, SP, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS) != hipSuccess)
-            return RESEL_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    launch_timed(RESEL_PROF_GEMM, gemm_ws_kernel<AKC, BKC, SP, EPI>, grid, dim3(NTH_WS), (size_t)WS_LDS, s, p);
-    return RESEL_OK;
+    return launch_big_lds(gemm_ws_kernel<AKC, BKC, EPI>, attr_set, grid, dim3(NTH_WS), WS_LDS, s, p);
 }
 
-// edition of the split GEMM: 3 = producer / consumer waves (gemm_ws_kernel), 2 = every wave does everything (gemm_bf3_kernel)
 constexpr int g_nt = 1;               // non-temporal C stores of the third edition: 23.43 -> 23.30 ms per update, same box
-int g_edition = [] { const char* e = getenv("RESEL_GEMM_EDITION"); return e ? atoi(e) : 3; }();
 
 }  // namespace
 
@@ -1689,14 +1330,14 @@ extern "C" int resel_bf3_debug_clock(unsigned long long* host_out) {
 namespace resel {
 
 size_t gemm_bf3_workspace_bytes(int M, int N, int K, int batch) {
-    const Plan pl = make_plan(M, N, K, batch);
+    const Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
     return (size_t)pl.nsplit * pl.nsl * TILE * sizeof(float);
 }
 
-// split in {3, 6, 9}, K >= 32; argument checks are the caller's (resel_gemm_f32)
+// split in {2, 3, 6}, K >= 32; argument checks are the caller's (resel_gemm_f32)
 // the fused epilogues (act 4 / 5) exist on the producer / consumer edition, for whole-K items: mode 2, K a multiple of 32, M > 128
 bool gemm_bf3_fused_ok(int M, int N, int K, int64_t lda, int64_t ldb) {
-    return g_edition == 3 && M > 128 && N >= 4 && K >= BK && K % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
+    return M > 128 && N >= 4 && K >= BK && K % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
 }
 
 int gemm_bf3_launch(const float* A, int64_t lda, int64_t strideA, int a_kcontig, const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
@@ -1704,7 +1345,7 @@ int gemm_bf3_launch(const float* A, int64_t lda, int64_t strideA, int a_kcontig,
                     int M, int N, int K, int batch, int split, hipStream_t s, const float* amaxA, const float* amaxB,
                     unsigned long long* amax_c, unsigned amax_epoch, const float* aux, int64_t ldaux, int64_t strideAux, float* red, int redrows) {
     if (split == 2 && (!amaxA || !amaxB)) return RESEL_EINVAL;
-    Plan pl = make_plan(M, N, K, batch);
+    Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
     if (act >= 4) {                                  // every tile whole: the epilogue reductions are written per (tile, wave), no K slices
         if (split != 2 || !gemm_bf3_fused_ok(M, N, K, lda, ldb) || !aux) return RESEL_EINVAL;
         if (act == 4 && (M % BM || N % BN)) return RESEL_EINVAL;          // the act 4 epilogue has no edge form (resel_gemm_f32_dact splits the rows)
@@ -1723,46 +1364,23 @@ int gemm_bf3_launch(const float* A, int64_t lda, int64_t strideA, int a_kcontig,
          else if (a_kcontig) rc = launch_one<true, false, SP>(p, grid, s); \
          else if (b_kcontig) rc = launch_one<false, true, SP>(p, grid, s); \
          else rc = launch_one<false, false, SP>(p, grid, s); } while (0)
-#define WS_LAUNCH(SP) \
-    do { if (a_kcontig && b_kcontig) rc = launch_ws<true, true, SP>(p, grid, s); \
-         else if (a_kcontig) rc = launch_ws<true, false, SP>(p, grid, s); \
-         else if (b_kcontig) rc = launch_ws<false, true, SP>(p, grid, s); \
-         else rc = launch_ws<false, false, SP>(p, grid, s); } while (0)
     // third edition: mode 2, whole K steps (also per K slice); row strides within the 24-bit multiply of the piece offsets
-    const bool ws = g_edition >= 3 && split == 2 && K % BK == 0 && pl.kslice % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
-    // fourth edition (RESEL_GEMM_EDITION=4): tall products with A [rows][K], whole K steps, a whole number of 256-column tiles or a last
-    // one that is more than half full, no bias stride (one batch member), epilogues 0 / 1 / 3
-    if (g_edition == 4 && split == 2 && act != 2 && act < 4 && a_kcontig && batch == 1 && K % BK == 0 && K >= 2 * BK && M >= 2048 && N >= 192 &&
-        ((N + BN8 - 1) / BN8 * BN8 - N) < 128 && lda < (1 << 22) && ldb < (1 << 22)) {
-        Params q = p;
-        q.nt = (N + BN8 - 1) / BN8;
-        q.nfull = q.mt * q.nt;
-        q.nsplit = 0;
-        dim3 g8((unsigned)std::min<int64_t>(q.nfull, GRID));
-        static std::atomic<bool> attr8[2][64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return RESEL_ELAUNCH;
-        if (!attr8[b_kcontig ? 1 : 0][dev].load(std::memory_order_acquire)) {
-            const void* fn = b_kcontig ? (const void*)gemm_w8_kernel<true> : (const void*)gemm_w8_kernel<false>;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS) != hipSuccess) return RESEL_ELAUNCH;
-            attr8[b_kcontig ? 1 : 0][dev].store(true, std::memory_order_release);
-        }
-        if (b_kcontig) launch_timed(RESEL_PROF_GEMM, gemm_w8_kernel<true>, g8, dim3(512), (size_t)W8_LDS, s, q);
-        else launch_timed(RESEL_PROF_GEMM, gemm_w8_kernel<false>, g8, dim3(512), (size_t)W8_LDS, s, q);
-        return launch_status();
-    }
+    const bool ws = split == 2 && K % BK == 0 && pl.kslice % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
     if (act >= 4) {                                   // fused epilogues: the layouts the trainer uses - A [rows][K]; B either way
         if (!a_kcontig) return RESEL_EINVAL;
-        if (act == 4) rc = b_kcontig ? launch_ws<true, true, 2, 4>(p, grid, s) : launch_ws<true, false, 2, 4>(p, grid, s);
-        else rc = b_kcontig ? launch_ws<true, true, 2, 5>(p, grid, s) : launch_ws<true, false, 2, 5>(p, grid, s);
-    } else if (ws) WS_LAUNCH(2);
-    else if (split == 3) BF3_LAUNCH(3); else if (split == 2) BF3_LAUNCH(2); else BF3_LAUNCH(6);
-#undef WS_LAUNCH
+        if (act == 4) rc = b_kcontig ? launch_ws<true, true, 4>(p, grid, s) : launch_ws<true, false, 4>(p, grid, s);
+        else rc = b_kcontig ? launch_ws<true, true, 5>(p, grid, s) : launch_ws<true, false, 5>(p, grid, s);
+    } else if (ws) {
+        if (a_kcontig && b_kcontig) rc = launch_ws<true, true>(p, grid, s);
+        else if (a_kcontig) rc = launch_ws<true, false>(p, grid, s);
+        else if (b_kcontig) rc = launch_ws<false, true>(p, grid, s);
+        else rc = launch_ws<false, false>(p, grid, s);
+    } else if (split == 3) BF3_LAUNCH(3); else if (split == 2) BF3_LAUNCH(2); else BF3_LAUNCH(6);
 #undef BF3_LAUNCH
     if (rc != RESEL_OK) return rc;
-    if (pl.nsplit) hipLaunchKernelGGL(gemm_bf3_fixup_kernel, dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
+    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
 #ifdef BF3_AB_FIXUP2                    // ablation (right results): every fix-up launched TWICE - what the 86 fix-up launches of an update cost, measured
-    if (pl.nsplit && act != 2) hipLaunchKernelGGL(gemm_bf3_fixup_kernel, dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);   // with the data left intact
+    if (pl.nsplit && act != 2) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);   // with the data left intact
 #endif                                  // (skipping the fix-up instead leaves garbage tiles: the degenerate data lowers the chip's power draw, its clock
                                         //  rises and EVERY kernel of the update runs 5-13 % faster - profiles/r06_gemm.md)
     return launch_status();

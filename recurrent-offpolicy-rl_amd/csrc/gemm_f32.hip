@@ -31,12 +31,11 @@
 // Blocks are persistent: block b walks the items b, b + G, ... (G = 512 = two blocks per CU); the loads of an item's first
 // steps and its epilogue stores overlap the neighbouring items' MFMAs.  An item is a whole output tile or - for the LAST,
 // partly filled round of tiles, and for weight gradients (few tiles, K = 66 752) - a K slice of a tile whose partial sums go
-// to a workspace slab; a fix-up kernel adds the slices in fixed order (deterministic, no atomics) and applies bias/activation.
+// to a workspace slab; a fix-up kernel adds the slices in fixed order (deterministic, no atomics) and applies bias/activation
+// (gemm_splitk.h: item walk, slice plan and fix-up kernel, shared with gemm_bf3.hip).
 // Without that the last round cost a full tile time at 4 % occupancy (1044 tiles on 512 slots: 68 % efficiency).
 // Tile ids are XCD-aware: the n-tiles of one m-tile share an L2.
-#include "resel_common.h"
-#include <algorithm>
-#include <cstdlib>
+#include "gemm_splitk.h"
 
 namespace resel {                      // gemm_bf3.hip: the split modes with the operands split once per block (second edition)
 size_t gemm_bf3_workspace_bytes(int M, int N, int K, int batch);
@@ -52,7 +51,7 @@ namespace {
 using namespace resel;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int BM = 128, BN = 128, BK = 32, NG = BK / 8;
+constexpr int BM = 128, BN = 128, NG = BK / 8;
 constexpr int LDK = BK + 4;           // LDS image [row][k]: 36 floats per row
 constexpr int GRID = 512;             // persistent blocks: two per CU
 constexpr int TILE = BM * BN;
@@ -68,34 +67,6 @@ struct GemmParams {
     int nsplit, nsl, kslice;
     AmaxOut amaxC;                                // optional: publish max |C| of the stored values
 };
-
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : fast_exp(x) - 1.f; }
-
-// tile t (member-major) -> member z, tile origin (m0, n0).  XCD-aware: the tiles of one XCD (ids congruent mod 8) walk the
-// n-tiles of one m-tile after another.
-__device__ __forceinline__ void tile_origin(const GemmParams& p, int t, int& z, int& m0, int& n0) {
-    const int ntile = p.mt * p.nt;
-    z = t / ntile;
-    const int tt = t - z * ntile;
-    const int q = ntile / 8, r = ntile % 8, x = tt & 7, j = tt >> 3;
-    const int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-    m0 = (bid / p.nt) * BM;
-    n0 = (bid % p.nt) * BN;
-}
-
-struct Item { int m0, n0, z, kbeg, kend, split; };     // split: index of the slab tile + 1, 0 for a whole tile
-__device__ __forceinline__ Item decode(const GemmParams& p, int it) {
-    Item o;
-    int t = it;
-    o.kbeg = 0; o.kend = p.K; o.split = 0;
-    if (it >= p.nfull) {
-        const int idx = it - p.nfull, tr = idx / p.nsl, sl = idx - tr * p.nsl;
-        t = p.nfull + tr;
-        o.kbeg = sl * p.kslice; o.kend = min(p.K, o.kbeg + p.kslice); o.split = idx + 1;
-    }
-    tile_origin(p, t, o.z, o.m0, o.n0);
-    return o;
-}
 
 // One operand's share of a thread in a K step: four float4 along the operand's contiguous axis.
 //   KC  (P[row][k]):  piece i = row (tid / 8 + 32 i), k = 4 (tid % 8) .. + 3
@@ -206,10 +177,9 @@ __device__ __forceinline__ void mfma_group(f32x16 (&acc)[2][2], const Frags& f, 
 // x = x1 + x2 + x3 EXACTLY, each plane a bf16 (8 significant bits) obtained by truncation: x1 = top 16 bits of x, x2 = top 16
 // bits of (x - x1) (exact difference), x3 = x - x1 - x2 (at most 8 significant bits left: exact).  A bf16 x bf16 product is
 // exact in fp32, so  a b = sum_{p,q} a_p b_q  term by term; v_mfma_f32_32x32x16_bf16 accumulates the terms in fp32 like the
-// fp32 MFMA accumulates a b itself.  SPLIT = 9 keeps all nine terms (the product is represented exactly: the same contract as
-// the fp32 instruction, with nine accumulator roundings in place of one); SPLIT = 6 drops a2 b3, a3 b2, a3 b3 (each at most
+// fp32 MFMA accumulates a b itself.  SPLIT = 6 keeps six of the nine terms: it drops a2 b3, a3 b2, a3 b3 (each at most
 // 2^-24 |a b|: the size of ONE fp32 rounding of the product).  8 k per lane and instruction at 32 cycles against 2 k at 64:
-// 6 terms cost 192 cycles per 32 x 32 x 16 block where the fp32 instruction needs 512 (9 terms: 288).
+// 6 terms cost 192 cycles per 32 x 32 x 16 block where the fp32 instruction needs 512.  SPLIT is 0 (fp32 MFMA) or 6 here.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 struct Planes { bf16x8 a[3][2], b[3][2]; };                        // [plane][tile]
 
@@ -278,7 +248,6 @@ __device__ __forceinline__ void mfma_term(f32x16 (&acc)[2][2], const Planes& pl)
 template <int SPLIT>
 __device__ __forceinline__ void mfma_terms(f32x16 (&acc)[2][2], const Planes& pl, int half) {
     if (half == 0) {
-        if (SPLIT == 9) { mfma_term<2, 2>(acc, pl); mfma_term<2, 1>(acc, pl); mfma_term<1, 2>(acc, pl); }
         mfma_term<2, 0>(acc, pl); mfma_term<0, 2>(acc, pl); mfma_term<1, 1>(acc, pl);
     } else {
         mfma_term<1, 0>(acc, pl); mfma_term<0, 1>(acc, pl); mfma_term<0, 0>(acc, pl);
@@ -311,8 +280,7 @@ __device__ __forceinline__ void split_quarter(f32x16 (&acc)[2][2], const Frags& 
             if (Q == 0 || Q == 3) asm volatile("" : "+v"(np.b[pi][t]));
             else asm volatile("" : "+v"(np.a[pi][t]));
         }
-    if (SPLIT == 6 || (Q & 1)) interleave_mfma_valu<12, 8, MEM>();
-    else interleave_mfma_valu<24, 4, MEM>();
+    interleave_mfma_valu<12, 8, MEM>();
 }
 
 #define RESEL_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -341,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
     int p_item = blockIdx.x, p_k0, p_kend;
     bool p_live = true;
     auto p_open = [&]() {
-        const Item it = decode(p, p_item);
+        const Item it = decode<BM, BN>(p, p_item);
         sa.init(p.A + (int64_t)it.z * p.sA, p.lda, p.M, it.m0, it.kbeg, tid);
         sb.init(p.B + (int64_t)it.z * p.sB, p.ldb, p.N, it.n0, it.kbeg, tid);
         p_k0 = it.kbeg; p_kend = it.kend;
@@ -383,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
     int stamp_step = 0;
 #endif
     for (; c_item < total; c_item += G) {
-        const Item cur = decode(p, c_item);
+        const Item cur = decode<BM, BN>(p, c_item);
         float zero = 0.f;
         asm volatile("" : "+v"(zero));              // opaque: or 64 registers of hoisted zeros stay live across the K loop
         f32x16 acc[2][2];
@@ -542,71 +510,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
     amax_publish_wave(cmax, p.amaxC);
 }
 
-// C tile = epi(sum over the K slices of a split tile).  Fixed summation order (deterministic): four interleaved slice groups
-// (threadIdx.y) accumulate slices q, q + 4, ... each, then ((g0 + g1) + (g2 + g3)).  grid (TILE / 4 / 64, split tiles), block (64, 4).
-__global__ __launch_bounds__(256) void gemm_fixup_kernel(GemmParams p) {
-    __shared__ float4 part[3][64];
-    const int tr = blockIdx.y, q = threadIdx.y;
-    const int e = blockIdx.x * 64 + threadIdx.x, ml = e >> 5, nl = 4 * (e & 31);
-    const float* s = p.slab + (int64_t)tr * p.nsl * TILE + ml * BN + nl;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    int i = q;
-    for (; i + 12 < p.nsl; i += 16) {                     // four loads in flight per thread
-        const float4 u0 = ld4(s + (int64_t)i * TILE), u1 = ld4(s + (int64_t)(i + 4) * TILE);
-        const float4 u2 = ld4(s + (int64_t)(i + 8) * TILE), u3 = ld4(s + (int64_t)(i + 12) * TILE);
-        v.x = (((v.x + u0.x) + u1.x) + u2.x) + u3.x; v.y = (((v.y + u0.y) + u1.y) + u2.y) + u3.y;
-        v.z = (((v.z + u0.z) + u1.z) + u2.z) + u3.z; v.w = (((v.w + u0.w) + u1.w) + u2.w) + u3.w;
-    }
-    for (; i < p.nsl; i += 4) {
-        const float4 u = ld4(s + (int64_t)i * TILE);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
-    if (q) part[q - 1][threadIdx.x] = v;
-    __syncthreads();
-    if (q) return;
-    const float4 g1 = part[0][threadIdx.x], g2 = part[1][threadIdx.x], g3 = part[2][threadIdx.x];
-    float o[4] = {(v.x + g1.x) + (g2.x + g3.x), (v.y + g1.y) + (g2.y + g3.y), (v.z + g1.z) + (g2.z + g3.z), (v.w + g1.w) + (g2.w + g3.w)};
-    int z, m0, n0;
-    tile_origin(p, p.nfull + tr, z, m0, n0);
-    const int m = m0 + ml, n = n0 + nl;
-    float cmax = 0.f;
-    if (m < p.M && n < p.N) {
-        float* c = p.C + (int64_t)z * p.sC + (int64_t)m * p.ldc + n;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (n + j >= p.N) break;
-            float x = o[j] + (p.bias ? p.bias[(int64_t)z * p.sBias + n + j] : 0.f);
-            if (p.act == 1) x = elu1(x);
-            if (p.act == 3) x = softplus_nb(x);
-            if (p.act == 2) x += c[j];
-            c[j] = x;
-            cmax = fmaxf(cmax, __builtin_fabsf(x));
-        }
-    }
-    amax_publish_wave(cmax, p.amaxC);
-}
-
-// How the output tiles become items: whole tiles for the full rounds of the 512 block slots; the remaining r tiles are cut
-// into K slices so that they fill the slots once more (at least two K steps per slice), also when r is everything (weight
-// gradients: 6 tiles, K = 66 752).  r > 256 tiles are left whole (a split could not even double the blocks).
-struct Plan { int nfull, nsplit, nsl, kslice; };
-// K slices for the tiles of a partly filled last round pay a fix-up launch (~6 us) and the slab round trip: only worth it when a whole
-// tile's K loop is long
-constexpr int g_split_min_ksteps = 4;   // thresholds 12 / 20 / 40 measured equal or slower on the whole update (profiles/r05_gemm.md)
-inline Plan make_plan(int M, int N, int K, int batch) {
-    const long nbt = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch;
-    const int ksteps = (K + BK - 1) / BK;
-    Plan pl{(int)nbt, 0, 1, ksteps * BK};
-    const int r = (int)(nbt % GRID);
-    if (r == 0 || r > GRID / 2 || ksteps < g_split_min_ksteps) return pl;
-    int s = std::min(GRID / r, ksteps / 2);
-    const int per = (ksteps + s - 1) / s;           // K steps per slice
-    s = (ksteps + per - 1) / per;                   // no empty slices
-    if (s < 2) return pl;
-    pl.nfull = (int)(nbt - r); pl.nsplit = r; pl.nsl = s; pl.kslice = per * BK;
-    return pl;
-}
-
 }  // namespace
 
 #ifdef GEMM_STAMP
@@ -617,7 +520,7 @@ extern "C" int resel_gemm_debug_stamps(unsigned long long* host_out) {
 
 extern "C" size_t resel_gemm_f32_workspace_bytes(int M, int N, int K, int batch) {
     if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return 0;
-    const Plan pl = make_plan(M, N, K, batch);
+    const Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
     return std::max(std::max((size_t)pl.nsplit * pl.nsl * TILE * sizeof(float), gemm_bf3_workspace_bytes(M, N, K, batch)),
                     gemm_any_workspace_bytes(M, N, K, batch));
 }
@@ -661,7 +564,7 @@ extern "C" int resel_gemm_f32x(const float* A, int64_t lda, int64_t strideA, int
         return gemm_bf3_launch(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, act, C, ldc, strideC, workspace,
                                M, N, K, batch, split, (hipStream_t)stream, amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch);
     if (split == 3) split = 6;                     // the two-plane mode exists on the second-edition kernel only: narrow shapes keep mode 6
-    const Plan pl = make_plan(M, N, K, batch);
+    const Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
     if (pl.nsplit && (!workspace || !aligned16(workspace))) return RESEL_EINVAL;
     GemmParams p{A, B, bias, C, (float*)workspace, lda, ldb, ldc, strideA, strideB, strideC, strideBias, M, N, K, act,
                  (M + BM - 1) / BM, (N + BN - 1) / BN, pl.nfull, pl.nsplit, pl.nsl, pl.kslice, AmaxOut{(unsigned long long*)amax_c, amax_epoch}};
@@ -676,7 +579,7 @@ extern "C" int resel_gemm_f32x(const float* A, int64_t lda, int64_t strideA, int
     if (split == 6) RESEL_GEMM_LAUNCH(6);
     else RESEL_GEMM_LAUNCH(0);
 #undef RESEL_GEMM_LAUNCH
-    if (pl.nsplit) hipLaunchKernelGGL(gemm_fixup_kernel, dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
+    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, GemmParams>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
     return launch_status();
 }
 

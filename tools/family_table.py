@@ -3,9 +3,9 @@ usage: family_table.py r04f r05f r05h"""
 import csv, re, collections, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAM = [('selective scan (fwd, bwd, reduce, parameter gradients)', r'sscan'),
-       ('GEMM mode 2, producer / consumer edition', r'gemm_ws_kernel<(true|false), (true|false), 2(, 0)?>'),
+       ('GEMM mode 2, producer / consumer edition', r'gemm_ws_kernel<(true|false), (true|false)(, 2)?(, 0)?>'),
        ('GEMM fused epilogues (`head`, `dact`)', r'gemm_ws_kernel<[^>]*, [45]>'),
-       ('GEMM other forms (mode 6, fp32 MFMA, second edition)', r'gemm_bf3_kernel|gemm_f32_kernel|gemm_w8'),
+       ('GEMM other forms (mode 6, fp32 MFMA, second edition)', r'gemm_bf3_kernel|gemm_f32_kernel'),
        ('GEMM fix-ups', r'fixup'), ('conv1d', r'conv_'), ('LayerNorm', r'ln_(fwd|bwd)'),
        ('bias / activation / head passes', r'bias_act|head_(fwd|bwd)|head_fold|dact_tail'), ('column sums', r'colsum'),
        ('magnitude pre-passes', r'amax'), ('ATen cat / copies / fills / element-wise', r'at::native|rocclr'), ('everything else', r'.')]

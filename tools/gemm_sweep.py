@@ -1,6 +1,7 @@
 """Correctness sweep of the library's mode-2 GEMM against mode 6 on grids from one block to more tiles than CUs, all four operand
 layouts, batched (ensemble) and K-split (weight-gradient) shapes: the unit tests' sizes do not fill the chip, and a pipeline that reads a
-register before its load has landed only fails on large grids.  RESEL_GEMM_EDITION selects the edition under test."""
+register before its load has landed only fails on large grids.  The shape decides which kernel takes a product (whole K steps: the
+producer / consumer edition; K tails: the one-role edition)."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'recurrent-offpolicy-rl_amd')]
