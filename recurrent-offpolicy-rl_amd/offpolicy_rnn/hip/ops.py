@@ -173,7 +173,7 @@ class MambaInnerFn(torch.autograd.Function):
     only exists for d_conv <= 4).  Everything is token-major; the backward writes every gradient straight into its slot of
     two buffers - dxz [M, 2Di] (conv backward fills the x half, scan backward the z half) and dx_dbl [M, R+2N] (scan
     backward fills the B / C columns) - through the kernels' token strides, so autograd's slice-backward zero-fill + copy +
-    add passes (8 x 273 MB per update at config 2) disappear.  GEMMs: `mm_nt` / `mm_nn` / `wgrad` (hand-written for long passes, library otherwise)."""
+    add passes (8 x 273 MB per update at config 2) disappear.  GEMMs: `mm_nt` / `mm_nn` / `wgrad` (hand-written, every pass)."""
 
     @staticmethod
     def forward(ctx, x, in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask, start):
@@ -195,18 +195,17 @@ class MambaInnerFn(torch.autograd.Function):
               'causal_conv1d_fwd')
         tag_amax(xc, h_xc)
         x_dbl = mm_nt(xc, xproj_w)                                         # [M, R + 2N] = (delta_r | B | C)
-        fold = True    # (rounds 4-5: only where the hand-written GEMM took dt_proj; it takes every shape now)
-        if fold and R < 32 <= R + 2 * N and os.environ.get('RESEL_DT_PAD', '1') != '0' and gemm_split() == 2:
+        # delta = softplus(dt_proj(.) + bias) leaves the GEMM epilogue: the scan kernels spend no vector issue on it
+        if R < 32 <= R + 2 * N and os.environ.get('RESEL_DT_PAD', '1') != '0' and gemm_split() == 2:
             # dt_proj has K = dt_rank = 16: one PARTIAL K step, which only the fp32-MFMA first edition takes (58 us for a product whose floor
             # is its 137 MB of output: 28 us).  Read 32 columns of x_dbl instead - the 16 behind delta_r are B's, finite - against the weight
             # padded with 16 zero columns (one launch): a whole K step, so the producer / consumer edition with its full-line stores runs it.
             w32 = place_blocks(Di, 32, [(0, 0)], dt_w.detach())
             dt = gemm_f32(x_dbl[:, :32], w32, True, True, dt_b, GEMM_SOFTPLUS, amax_a=amax_of(x_dbl), amax_b=weight_amax(dt_w))
-        elif fold:     # delta = softplus(dt_proj(.) + bias) leaves the GEMM epilogue: the scan kernels spend no vector issue on it
-            dt = gemm_f32(x_dbl[:, :R], dt_w, True, True, dt_b, GEMM_SOFTPLUS)
         else:
-            dt = mm_nt(x_dbl[:, :R], dt_w)                                  # [M, Di]; bias enters the scan as delta_bias
-        A = A_log.float().contiguous()                                     # the kernels form A = -exp(A_log) themselves (delta_softplus + 4)
+            dt = gemm_f32(x_dbl[:, :R], dt_w, True, True, dt_b, GEMM_SOFTPLUS)
+        # delta_softplus code 6 = 4 (the kernels form A = -exp(A_log) themselves) + 2 (delta arrives finished: no delta_bias)
+        A = A_log.float().contiguous()
         need_grad = any(ctx.needs_input_grad)
         ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), x.device) if need_grad else None
         y = torch.empty(M, Di, dtype=torch.float32, device=x.device)
@@ -215,14 +214,13 @@ class MambaInnerFn(torch.autograd.Function):
         nb = lib().resel_selective_scan_fwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS)
         h_y, p_y, e_y = _slot_args(track, x.device)
         check(lib().resel_selective_scan_fwd(_p(xc), Di, _p(dt), Di, zptr, 2 * Di, _p(A), bptr, R + 2 * N, cptr, R + 2 * N,
-                                             _p(D), None if fold else _p(dt_b), _p(startf), _p(y), Di, _p(ck), None, _p(_ws(nb, x.device) if nb else None),
-                                             Bsz, L, Di, N, 4 + (2 if fold else 1), SSCAN_TIME_SEGMENTS, p_y, e_y, _stream()), 'selective_scan_fwd')
+                                             _p(D), None, _p(startf), _p(y), Di, _p(ck), None, _p(_ws(nb, x.device) if nb else None),
+                                             Bsz, L, Di, N, 6, SSCAN_TIME_SEGMENTS, p_y, e_y, _stream()), 'selective_scan_fwd')
         tag_amax(y, h_y)
         out = mm_nt(y, out_w)
         ctx.handles = keep_handles(ctx.ax, h_xc, h_y)                      # saved tensors come back untagged
         ctx.save_for_backward(x2, in_w, cw, conv_b, xproj_w, dt_w, dt_b, A, D, out_w, maskf, startf, xz, xc, x_dbl, dt, y, ck)
         ctx.dims = (Bsz, L, Dm, Di, N, R, K, conv_w.shape)
-        ctx.fold = fold
         return out.view(Bsz, L, -1)
 
     @staticmethod
@@ -251,9 +249,9 @@ class MambaInnerFn(torch.autograd.Function):
         h_ddt, p_ddt, _ = _slot_args(track, dev)                           # (published under the same epoch e_b)
         check(lib().resel_selective_scan_bwd(
             _p(xc), Di, _p(dt), Di, P(xz, Di), 2 * Di, _p(A), P(x_dbl, R), R + 2 * N, P(x_dbl, R + N), R + 2 * N,
-            _p(D), None if ctx.fold else _p(dt_b), _p(startf), _p(dy), Di, _p(ck),
+            _p(D), None, _p(startf), _p(dy), Di, _p(ck),
             _p(dxc), Di, _p(ddt), Di, P(dxz, Di), 2 * Di, P(dx_dbl, R), R + 2 * N, P(dx_dbl, R + N), R + 2 * N,
-            _p(dA), _p(dD), _p(ddt_b), _p(ws), Bsz, L, Di, N, 4 + (2 if ctx.fold else 1), SSCAN_TIME_SEGMENTS, p_dxz, p_ddt, e_b, _stream()), 'selective_scan_bwd')
+            _p(dA), _p(dD), _p(ddt_b), _p(ws), Bsz, L, Di, N, 6, SSCAN_TIME_SEGMENTS, p_dxz, p_ddt, e_b, _stream()), 'selective_scan_bwd')
         tag_amax(ddt, h_ddt)
         # [Di, R] with a 66 752-long reduction: hand-written MFMA kernel (the library reaches 7 TFLOP/s on this shape)
         d_dt_w = atb(ddt, x_dbl[:, :R]) if R <= 32 and Di % 4 == 0 and ddt.stride(1) == 1 and ddt.stride(0) % 4 == 0 \
@@ -336,11 +334,10 @@ class AddNormFn(torch.autograd.Function):
         need_res = residual is not None or prenorm
         res_out = torch.empty_like(x2) if need_res else None
         stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
-        global LAST_AMAX
         slot, slot_p, epoch = _slot_args(amax_tracking() and M * C >= (1 << 20), x.device)
         check(lib().resel_add_layernorm_fwd(_p(x2), _p(r2), _p(w), _p(b), _p(y), _p(res_out), _p(stats), M, C, float(eps),
                                             int(bool(rms)), int(act == 'elu'), slot_p, epoch, _stream()), 'add_layernorm_fwd')
-        LAST_AMAX = slot
+        publish_amax(slot)
         ctx.save_for_backward(res_out if res_out is not None else x2, w, stats, b if act else None)
         ctx.rms, ctx.has_bias, ctx.has_res, ctx.prenorm, ctx.shape = bool(rms), b is not None, residual is not None, prenorm, shape
         ctx.act = int(act == 'elu')
@@ -366,11 +363,8 @@ class AddNormFn(torch.autograd.Function):
 
 
 def _add_norm(x, residual, weight, bias, eps, rms, prenorm, act=None):
-    global LAST_AMAX
-    LAST_AMAX = None
-    out = AddNormFn.apply(x, residual, weight, bias, eps, rms, prenorm, act)
-    tag_amax(out[0] if prenorm else out, LAST_AMAX, whole=True)    # the normalised output feeds a projection: its magnitude came out of the same pass
-    return out
+    # the normalised output (the first one under prenorm) feeds a projection: its magnitude came out of the same pass
+    return apply_tagged(AddNormFn.apply, True, x, residual, weight, bias, eps, rms, prenorm, act)
 
 
 def layer_norm_fn(x, weight, bias, residual=None, eps=1e-6, prenorm=False, residual_in_fp32=False, act=None):
@@ -415,7 +409,8 @@ def _real_fwd(v, f, ld, start, h0, fuse_act):
     slot, slot_p, epoch = _slot_args(amax_tracking() and h.numel() >= (1 << 20), v.device)
     check(lib().resel_linrec_real_fwd(_p(v), _p(f), ld, _p(start), _p(h0), _p(h), Bsz, L, C, int(bool(fuse_act)), slot_p, epoch, _stream()),
           'linrec_real_fwd')
-    return h, slot
+    publish_amax(slot)
+    return h
 
 
 class GilrScanFn(torch.autograd.Function):
@@ -426,8 +421,7 @@ class GilrScanFn(torch.autograd.Function):
         Bsz, L, C = v.shape
         start = _flags(start, Bsz, L)
         h0 = None if h0 is None else h0.float().reshape(Bsz, C).contiguous()
-        global LAST_AMAX
-        h, LAST_AMAX = _real_fwd(v, f, ld, start, h0, fuse_act)
+        h = _real_fwd(v, f, ld, start, h0, fuse_act)
         ctx.save_for_backward(v, f, start, h0, h)
         ctx.act, ctx.ld = bool(fuse_act), ld
         return h
@@ -457,8 +451,7 @@ class GilrMembersFn(torch.autograd.Function):
         _, Bsz, L, C = u.shape
         start = _flags(start, Bsz, L)
         h0 = None if h0 is None else h0.float().reshape(Bsz, C).contiguous()
-        global LAST_AMAX
-        h, LAST_AMAX = _real_fwd(u[0], u[1], ld, start, h0, fuse_act)
+        h = _real_fwd(u[0], u[1], ld, start, h0, fuse_act)
         ctx.save_for_backward(u, start, h0, h)
         ctx.act, ctx.ld = bool(fuse_act), ld
         return h
@@ -477,16 +470,12 @@ class GilrMembersFn(torch.autograd.Function):
 
 def gilr_scan(v, f, start=None, h0=None, fuse_act=True):
     """h_t = f'_t h_{t-1} + (1 - f'_t) v'_t with v' = tanh(v), f' = sigmoid(f) (1 - start) when fuse_act."""
-    global LAST_AMAX
-    LAST_AMAX = None
-    return tag_amax(GilrScanFn.apply(v, f, start, h0, fuse_act), LAST_AMAX)
+    return apply_tagged(GilrScanFn.apply, False, v, f, start, h0, fuse_act)
 
 
 def gilr_scan_members(u, start=None, h0=None, fuse_act=True):
     """`gilr_scan(u[0], u[1], ...)` for u [2, B, T, C], reading the members in place (see `GilrMembersFn`)."""
-    global LAST_AMAX
-    LAST_AMAX = None
-    return tag_amax(GilrMembersFn.apply(u, start, h0, fuse_act), LAST_AMAX)
+    return apply_tagged(GilrMembersFn.apply, False, u, start, h0, fuse_act)
 
 
 def real_scan_tie_input_gate(v, f):
@@ -588,8 +577,8 @@ class LruMembersFn(torch.autograd.Function):
         E, Bsz, L, C = u.shape
         lam3 = lam3.float().contiguous()
         _, _, _, start, h0r, h0i = _complex_args(lam3[0], lam3[1], lam3[2], start, h0r, h0i, Bsz, L, C)
-        global LAST_AMAX
-        h2, LAST_AMAX = _complex_fwd(u[0], u[1], ld, lam3[0], lam3[1], lam3[2], start, h0r, h0i)
+        h2, slot = _complex_fwd(u[0], u[1], ld, lam3[0], lam3[1], lam3[2], start, h0r, h0i)
+        publish_amax(slot)
         ctx.save_for_backward(u, lam3, start, h0r, h0i, h2)
         ctx.ld = ld
         return (h2, u[2]) if E == 3 else (h2, None)
@@ -621,10 +610,7 @@ def complex_scan(vr, vi, lam_re, lam_im, gamma=None, start=None, h0r=None, h0i=N
 def complex_scan_members(u, lam3, start=None, h0r=None, h0i=None):
     """`complex_scan(u[0], u[1], lam3[0], lam3[1], lam3[2], ...)` for u [2 or 3, B, T, C] read in place and lam3 = `lru_params(params_log)`
     -> (h2 [2, B, T, C] = (Re h | Im h), u[2] or None); see `LruMembersFn`."""
-    global LAST_AMAX
-    LAST_AMAX = None
-    h2, u2 = LruMembersFn.apply(u, lam3, start, h0r, h0i)
-    return tag_amax(h2, LAST_AMAX), u2
+    return apply_tagged(LruMembersFn.apply, False, u, lam3, start, h0r, h0i)
 
 
 class SubAddMembers(torch.autograd.Function):
@@ -676,7 +662,7 @@ class GruSeqFn(torch.autograd.Function):
         ws = _ws(lib().resel_gru_workspace_bytes(Bsz, L, H), h_all.device)
         check(lib().resel_gru_seq_bwd(_p(w_hh), _p(h0), _p(h_all), _p(gates), _p(dh_all), _p(dgi), _p(dgh), _p(ws),
                                       Bsz, L, H, _stream()), 'gru_seq_bwd')
-        # dW_hh = dgh^T h_prev over the B*L rows (`wgrad`: the K-split hand-written GEMM on long passes) and db_hh = sum dgh
+        # dW_hh = dgh^T h_prev over the B*L rows (`wgrad`: the K-split hand-written GEMM) and db_hh = sum dgh
         h_prev = torch.cat((torch.zeros(Bsz, 1, H, device=h_all.device) if h0 is None else h0.unsqueeze(1), h_all[:, :-1]), dim=1)
         dw_hh = wgrad(dgh.reshape(-1, 3 * H), h_prev.reshape(-1, H))
         db_hh = dgh.sum(dim=(0, 1))
@@ -862,10 +848,9 @@ class GeluDropoutFn(torch.autograd.Function):
         assert x.dtype == torch.float32
         x = x.contiguous()
         y = torch.empty_like(x)
-        global LAST_AMAX
         slot, slot_p, epoch = _slot_args(amax_tracking() and x.numel() >= (1 << 20), x.device)
         check(lib().resel_gelu_dropout_fwd(_p(x), _p(y), x.numel(), float(p_drop), int(seed), int(offset), slot_p, epoch, _stream()), 'gelu_dropout_fwd')
-        LAST_AMAX = slot
+        publish_amax(slot)
         ctx.save_for_backward(x)
         ctx.drop = (float(p_drop), int(seed), int(offset))
         return y
@@ -885,9 +870,7 @@ def gelu_dropout(x, p_drop, seed=None, offset=None):
     (seed, offset) - one `dropout_counter` draw when p_drop > 0, none otherwise (plain GELU)."""
     if p_drop > 0.0 and seed is None:
         seed, offset = dropout_counter(x.device)
-    global LAST_AMAX
-    LAST_AMAX = None
-    return tag_amax(GeluDropoutFn.apply(x, p_drop if p_drop > 0.0 else 0.0, seed or 0, offset or 0), LAST_AMAX)
+    return apply_tagged(GeluDropoutFn.apply, False, x, p_drop if p_drop > 0.0 else 0.0, seed or 0, offset or 0)
 
 
 # ---------------------------------------------------------------------------------------------- SAC / TD3 arithmetic
@@ -1066,12 +1049,10 @@ def bias_act_bwd(g2, a2, rows_per_seg, act, need_dbias):
     nseg = rows // int(rows_per_seg)
     db = torch.empty(nseg, C, dtype=torch.float32, device=g2.device) if need_dbias else None
     ws = _ws(lib().resel_bias_act_bwd_workspace_bytes(rows, C, int(rows_per_seg)), g2.device) if need_dbias else None
-    global LAST_AMAX
     slot, slot_p, epoch = _slot_args(amax_tracking() and rows * C >= (1 << 20), g2.device)
     check(lib().resel_bias_act_bwd(_p(g2), g2.stride(0), _p(a2) if aid else None, a2.stride(0) if aid else 0, _p(gy) if aid else None, _p(db), _p(ws), rows, C, int(rows_per_seg), aid,
                                    slot_p, epoch, _stream()), 'bias_act_bwd')
     tag_amax(gy, slot)
-    LAST_AMAX = slot
     return gy, db
 
 
@@ -1096,37 +1077,34 @@ def ensemble_head_bwd(gq, a3, w3):
     db2 = torch.empty(E, H, dtype=torch.float32, device=a3.device)
     dw3 = torch.empty(E, H, dtype=torch.float32, device=a3.device)
     ws = _ws(lib().resel_ensemble_head_bwd_workspace_bytes(E * M, H, M), a3.device)
-    global LAST_AMAX
     slot, slot_p, epoch = _slot_args(amax_tracking() and E * M * H >= (1 << 20), a3.device)
     check(lib().resel_ensemble_head_bwd(_p(gq), _p(a3), _p(w3), _p(gy), _p(db2), _p(dw3), _p(ws), E * M, H, M, slot_p, epoch, _stream()),
           'ensemble_head_bwd')
     tag_amax(gy, slot)
-    LAST_AMAX = slot
     return gy, db2, dw3
 
 
 class LinearAct(torch.autograd.Function):
     """act(x W^T + b) for nn.Linear weights (reference rnn_base.py:462-474: `fc` layer followed by its activation module):
-    one GEMM with the bias / activation tail (`mm_nt`); the backward needs the layer OUTPUT only.  On long GPU passes an input
-    width (17- / 6-wide encoders) or an output width (6-wide TD3 action head) that is not a multiple of 4 is zero-padded inside
-    the node - exact zeros in every dot product, the padding rows / columns of the gradients are dropped - so that every
-    contraction of the update runs on the hand-written GEMM."""
+    one GEMM with the bias / activation tail (`mm_nt`); the backward needs the layer OUTPUT only.  An input width (17- / 6-wide
+    encoders) or an output width (6-wide TD3 action head) that is not a multiple of 4 is zero-padded inside the node - exact zeros
+    in every dot product, the padding rows / columns of the gradients are dropped - so that every contraction runs on the
+    matrix-core editions of the hand-written GEMM."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, dest=None):
-        """dest: a `ColDest` - the column block of a row buffer the output should be written to in place (when the hand-written GEMM runs
-        and nothing is padded; otherwise the output is a fresh tensor and whoever assembles the buffer copies it in)."""
+        """dest: a `ColDest` - the column block of a row buffer the output should be written to in place (when it fits and no output
+        column is padded; otherwise the output is a fresh tensor and whoever assembles the buffer copies it in)."""
         x2 = x.reshape(-1, x.shape[-1])
         x2 = x2 if x2.stride(-1) == 1 else x2.contiguous()
-        long_pass = x2.is_cuda                         # (rounds 2-5: passes of 4 096 tokens and more)
-        ctx.kpad = (-x2.shape[1]) % 4 if long_pass else 0
-        ctx.npad = (-weight.shape[0]) % 4 if long_pass else 0
+        ctx.kpad = (-x2.shape[1]) % 4
+        ctx.npad = (-weight.shape[0]) % 4
         n_out = weight.shape[0]
         if ctx.kpad or ctx.npad:
             x2 = torch.nn.functional.pad(x2, (0, ctx.kpad)) if ctx.kpad else x2
             weight = torch.nn.functional.pad(weight, (0, ctx.kpad, 0, ctx.npad))
             bias = torch.nn.functional.pad(bias, (0, ctx.npad)) if (bias is not None and ctx.npad) else bias
-        if dest is not None and long_pass and not ctx.npad and dest.fits(x2.shape[0], weight.shape[0]):
+        if dest is not None and not ctx.npad and dest.fits(x2.shape[0], weight.shape[0]):
             y2 = mm_nt(x2, weight, bias, act, out=dest.view(), amax_out=dest.rb.amax if dest.rb.handle() is not None else None)
             dest.note(y2)
         else:
@@ -1145,13 +1123,7 @@ class LinearAct(torch.autograd.Function):
         if ctx.npad:
             g2 = torch.nn.functional.pad(g2, (0, ctx.npad))
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if y2.shape[1] % 4:                                           # short passes keep odd widths: plain torch tail
-            g2 = g2 if g2.is_contiguous() else g2.contiguous()
-            aid = ACT_IDS[ctx.act]                                     # 0: identity ('linear' / None), 1: ELU; anything else is a KeyError
-            gy = g2 if aid == 0 else g2 * torch.where(y2 > 0, torch.ones_like(y2), y2 + 1.0)          # elu'(x) from the output
-            db = gy.sum(dim=0) if need_db else None
-        else:
-            gy, db = bias_act_bwd(g2, y2, y2.shape[0], ctx.act, need_db)
+        gy, db = bias_act_bwd(g2, y2, y2.shape[0], ctx.act, need_db)
         dx = mm_nn(gy, weight) if ctx.needs_input_grad[0] else None
         dw = wgrad(gy, x2, amax_x=handle_alive(ctx.ax)) if ctx.needs_input_grad[1] else None
         if ctx.kpad or ctx.npad:                      # drop the padding rows / columns again
@@ -1198,10 +1170,8 @@ def place_blocks(rows, cols, origins, *srcs):
 
 
 def linear_act(x, weight, bias, act, dest=None):
-    global LAST_AMAX
-    LAST_AMAX = None
     # (an output written into a row buffer is a view of it: its magnitude must not be taken for the whole buffer's)
-    return tag_amax(LinearAct.apply(x, weight, bias, act, dest), LAST_AMAX, whole=dest is None)
+    return apply_tagged(LinearAct.apply, dest is None, x, weight, bias, act, dest)
 
 
 # ---- row buffers: the column blocks of ONE token-major matrix written in place by the GEMMs that produce them -----------------------
@@ -1294,20 +1264,15 @@ def linear(x, weight, bias=None):
     """x W^T + b for an fp32 nn.Linear: the `LinearAct` node (hand-written GEMM forward, input and weight gradients) for every pass -
     the whole trajectories of an update and the single token of a rollout step alike (`resel_gemm_f32x` takes every shape: the matrix-core
     editions where the layout allows them, csrc/gemm_any.hip for the rest).  An input width that is not a multiple of 4 (the 17-wide
-    observation / 6-wide action encoders) is zero-padded to 16-byte rows inside the node.  There is no library GEMM behind this module
-    (round 5 kept `F.linear` for passes under 4 096 tokens); CPU tensors raise in `gemm_f32`."""
+    observation / 6-wide action encoders) is zero-padded to 16-byte rows inside the node.  There is no library GEMM behind this module;
+    CPU tensors raise in `gemm_f32`."""
     return linear_act(x, weight, bias, None)
 
 
-# Every CUDA fp32 pass takes the hand-written kernels since round 6 (the constant is what remains of the round 2-5 switch between them
-# and the GEMM library: 4 096 tokens then).  Code that asked "is this a long pass?" now asks "is this a CUDA pass?".
-GEMM_F32_MIN_ROWS = 1
-
-
-def gemm_f32_ok(rows, *mats):
-    """True when `resel_gemm_f32` takes these operands as they are: on the GPU, fp32, unit column stride (any row alignment: the C entry
-    routes shapes the matrix-core editions cannot read to csrc/gemm_any.hip)."""
-    return rows >= 1 and all(t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1 for t in mats)
+def gemm_f32_ok(*mats):
+    """True when `resel_gemm_f32` takes these operands as they are: on the GPU, fp32, unit column stride (any row count and alignment: the
+    C entry routes shapes the matrix-core editions cannot read to csrc/gemm_any.hip)."""
+    return all(t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1 for t in mats)
 
 
 def rows_aligned16(*mats):
@@ -1315,10 +1280,6 @@ def rows_aligned16(*mats):
     fused epilogues, which have no other form) read."""
     return all(t.data_ptr() % 16 == 0 and t.shape[-1] % 4 == 0 and all(st % 4 == 0 for st in t.stride()[:-1])
                and (t.dim() < 2 or t.stride(-2) < (1 << 22)) for t in mats)
-
-
-GEMM_F32_MIN_DIM = 1        # (rounds 2-5: outputs / reductions narrower than 4 stayed with the library)
-GEMM_F32_MIN_K = 1
 
 
 def _unit(t):
@@ -1476,8 +1437,26 @@ AMAX_WORDS = 128              # int64 words per handle
 AMAX_PREPASS_FRACTION = 0.16  # of the estimated GEMM time one may spend on reading an untagged operand (measured: profiles/r04_gemm.md)
 _AMAX_ARENA = {}              # device -> [int64 tensor [AMAX_SLOTS], next index]
 _AMAX_EPOCH = [0]
-LAST_AMAX = None              # handle of the magnitude published by the most recent producer call (wrappers tag Function outputs with it)
+LAST_AMAX = None              # the side channel from a Function's forward to `apply_tagged` around its .apply: written by `publish_amax` only
 LAST_SPLIT = [None]
+
+
+def publish_amax(slot):
+    """Called by a producer inside an `autograd.Function.forward` (outputs of `.apply` come back untagged): hand the magnitude handle of
+    the output (or None) to the `apply_tagged` that wraps the `.apply`."""
+    global LAST_AMAX
+    LAST_AMAX = slot
+
+
+def apply_tagged(fn, whole, *args):
+    """fn(*args) with its output (the first one of several) tagged with the handle that a producer inside fn published through
+    `publish_amax`, and with none if nothing inside published - never with what an earlier producer left behind.  whole: as `tag_amax`."""
+    global LAST_AMAX
+    LAST_AMAX = None
+    out = fn(*args)
+    tag_amax(out[0] if type(out) is tuple else out, LAST_AMAX, whole)
+    LAST_AMAX = None
+    return out
 
 
 _AMAX_SERIAL = [0]            # handles handed out so far; every arena handle object carries the serial of its current tenant (`_resel_serial`)
@@ -1697,6 +1676,32 @@ def amax_tracking():
     return gemm_split() == 2
 
 
+def _operand_handles(A, B, amax_a, amax_b):
+    """Magnitude handles of a product's operands as far as they are known without a pass: the caller's, a producer's tag, the
+    parameter store's (None where none of them has one)."""
+    ha = amax_a if amax_a is not None else amax_of(A)
+    hb = amax_b if amax_b is not None else amax_of(B)
+    return weight_amax(A) if ha is None else ha, weight_amax(B) if hb is None else hb
+
+
+def _prepass(x):
+    """One `amax` pass over an operand nobody has a handle for; tagged for reuse."""
+    h = amax(x)
+    tag_amax(x, h)
+    return h
+
+
+def _verify_operands(A, B, ha, hb, what):
+    amax_check(A, ha, 'A of ' + what)
+    amax_check(B, hb, 'B of ' + what)
+
+
+def _gemm_done(out, slot, split):
+    """Tail of the three GEMM forms: the output carries the magnitude its epilogue published."""
+    LAST_SPLIT[0] = split                            # tools/gemm_census.py: which product mode the call took
+    return tag_amax(out, slot)
+
+
 @torch.no_grad()
 def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None, split=None, amax_a=None, amax_b=None, amax_out=None):
     """C[b] = act(A[b] (.) B[b] + bias[b]) on the matrix cores, fp32 in / out (include/resel_hip.h `resel_gemm_f32`).
@@ -1727,7 +1732,6 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
         bs = bias.stride(0) if batched else 0
     multi = batch > 1
     split = gemm_split() if split is None else int(split)
-    global LAST_AMAX
     ha = hb = None
     if split == 2:
         # mode 2 (fp16 planes of the scaled operands) needs a bound on max |A|, max |B| on the device: a producer's tag, the
@@ -1735,25 +1739,17 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
         if K < 32 or M <= 128:
             split = 6
         else:
-            ha = amax_a if amax_a is not None else amax_of(A)
-            hb = amax_b if amax_b is not None else amax_of(B)
-            ha = weight_amax(A) if ha is None else ha
-            hb = weight_amax(B) if hb is None else hb
+            ha, hb = _operand_handles(A, B, amax_a, amax_b)
             if ha is None or hb is None:
                 t_gemm = 2.0 * M * N * K * batch / 1.5e8                       # us at 150 TFLOP/s
                 cost = (0.0 if ha is not None else 4.0 * M * K * batch / 4.5e6 + 2.5) + (0.0 if hb is not None else 4.0 * N * K * batch / 4.5e6 + 2.5)
                 if cost <= AMAX_PREPASS_FRACTION * t_gemm:
-                    if ha is None:
-                        ha = amax(A)
-                        tag_amax(A, ha)
-                    if hb is None:
-                        hb = amax(B)
-                        tag_amax(B, hb)
+                    ha = _prepass(A) if ha is None else ha
+                    hb = _prepass(B) if hb is None else hb
                 else:
                     split = 6
     if AMAX_VERIFY and split == 2:
-        amax_check(A, ha, f'A of gemm M={M} N={N} K={K} batch={batch}')
-        amax_check(B, hb, f'B of gemm M={M} N={N} K={K} batch={batch}')
+        _verify_operands(A, B, ha, hb, f'gemm M={M} N={N} K={K} batch={batch}')
     # max |C| for whoever multiplies C next (only while mode 2 is the product mode, and only for outputs worth a pass)
     # (amax_out: the (handle, pointer, epoch) of a row buffer this product fills a column block of - its producers share one handle)
     slot, slot_p, epoch = amax_out if amax_out is not None else \
@@ -1762,33 +1758,22 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
                             B.stride(0) if multi else 0, int(b_kcontig), _p(bias), bs, 2 if act == GEMM_ACCUMULATE else 3 if act == GEMM_SOFTPLUS else ACT_IDS[act], _p(out), out.stride(-2),
                             out.stride(0) if multi else 0, _p(ws), M, N, K, batch, split, _p(ha) if split == 2 else None,
                             _p(hb) if split == 2 else None, slot_p, epoch, _stream()), 'gemm_f32')
-    tag_amax(out, slot)
-    LAST_AMAX = slot
-    LAST_SPLIT[0] = split                            # tools/gemm_census.py: which product mode the call took
-    return out
+    publish_amax(slot)                               # for `linear_act` / `EnsembleLinear.forward`, which run this product inside a Function
+    return _gemm_done(out, slot, split)
 
 
 # ---- fused epilogues of the producer / consumer GEMM (include/resel_hip.h `resel_gemm_f32_dact` / `resel_gemm_f32_head`) ----------
 def _forced_handles(A, B, amax_a, amax_b):
     """Magnitude handles of both operands for a product that exists in mode 2 only: the caller's, a producer's tag, the parameter
     store's - or one pre-pass (tagged for reuse)."""
-    ha = amax_a if amax_a is not None else amax_of(A)
-    hb = amax_b if amax_b is not None else amax_of(B)
-    ha = weight_amax(A) if ha is None else ha
-    hb = weight_amax(B) if hb is None else hb
-    if ha is None:
-        ha = amax(A)
-        tag_amax(A, ha)
-    if hb is None:
-        hb = amax(B)
-        tag_amax(B, hb)
-    return ha, hb
+    ha, hb = _operand_handles(A, B, amax_a, amax_b)
+    return _prepass(A) if ha is None else ha, _prepass(B) if hb is None else hb
 
 
 def gemm_fused_ok(kind, M, N, K, *mats):
-    """True when a fused-epilogue form (kind 4: dact, 5: head) may take a product of this shape: product mode 2, a long pass, the
+    """True when a fused-epilogue form (kind 4: dact, 5: head) may take a product of this shape: product mode 2, the
     producer / consumer edition's shape rules (K a multiple of 32, M > 128; dact: N a multiple of 128), 16-byte aligned rows."""
-    if os.environ.get('RESEL_GEMM_FUSED', '1') == '0' or gemm_split() != 2 or not gemm_f32_ok(M, *mats) or not rows_aligned16(*mats):
+    if os.environ.get('RESEL_GEMM_FUSED', '1') == '0' or gemm_split() != 2 or not gemm_f32_ok(*mats) or not rows_aligned16(*mats):
         return False
     ld = max(int(t.stride(-2)) for t in mats)
     return bool(lib().resel_gemm_f32_fused_supported(int(kind), int(M), int(N), int(K), ld, ld))
@@ -1809,8 +1794,7 @@ def gemm_f32_dact(A, B, b_kcontig, Y, out, need_dbias=True, amax_a=None, amax_b=
     assert A.stride(-1) == 1 and B.stride(-1) == 1 and Y.stride(-1) == 1 and out.stride(-1) == 1
     ha, hb = _forced_handles(A, B, amax_a, amax_b)
     if AMAX_VERIFY:
-        amax_check(A, ha, f'A of gemm_dact M={M} N={N} K={K} batch={batch}')
-        amax_check(B, hb, f'B of gemm_dact M={M} N={N} K={K} batch={batch}')
+        _verify_operands(A, B, ha, hb, f'gemm_dact M={M} N={N} K={K} batch={batch}')
     GEMM_FLOPS[0] += 2.0 * M * N * K * batch
     L = lib()
     ws = _ws(L.resel_gemm_f32_fused_workspace_bytes(M, N, K, batch, 4), A.device)
@@ -1820,11 +1804,7 @@ def gemm_f32_dact(A, B, b_kcontig, Y, out, need_dbias=True, amax_a=None, amax_b=
     check(L.resel_gemm_f32_dact(_p(A), A.stride(-2), A.stride(0) if multi else 0, 1, _p(B), B.stride(-2), B.stride(0) if multi else 0, int(b_kcontig),
                                 _p(Y), Y.stride(-2), Y.stride(0) if multi else 0, _p(out), out.stride(-2), out.stride(0) if multi else 0,
                                 _p(dbias), _p(ws), M, N, K, batch, _p(ha), _p(hb), slot_p, epoch, _stream()), 'gemm_f32_dact')
-    tag_amax(out, slot)
-    global LAST_AMAX
-    LAST_AMAX = slot
-    LAST_SPLIT[0] = 2
-    return out, dbias
+    return _gemm_done(out, slot, 2), dbias
 
 
 @torch.no_grad()
@@ -1838,8 +1818,7 @@ def gemm_f32_head(A, B, b_kcontig, bias, w3, b3, amax_a=None, amax_b=None):
     assert A.stride(-1) == 1 and B.stride(-1) == 1 and w3.shape == (batch, N) and w3.is_contiguous() and bias.shape == (batch, N) and bias.stride(-1) == 1
     ha, hb = _forced_handles(A, B, amax_a, amax_b)
     if AMAX_VERIFY:
-        amax_check(A, ha, f'A of gemm_head M={M} N={N} K={K} batch={batch}')
-        amax_check(B, hb, f'B of gemm_head M={M} N={N} K={K} batch={batch}')
+        _verify_operands(A, B, ha, hb, f'gemm_head M={M} N={N} K={K} batch={batch}')
     GEMM_FLOPS[0] += 2.0 * M * N * K * batch
     L = lib()
     ws = _ws(L.resel_gemm_f32_fused_workspace_bytes(M, N, K, batch, 5), A.device)
@@ -1850,11 +1829,7 @@ def gemm_f32_head(A, B, b_kcontig, bias, w3, b3, amax_a=None, amax_b=None):
     check(L.resel_gemm_f32_head(_p(A), A.stride(-2), A.stride(0) if multi else 0, 1, _p(B), B.stride(-2), B.stride(0) if multi else 0, int(b_kcontig),
                                 _p(bias), bias.stride(0) if multi else 0, _p(w3), N, _p(b3), _p(a), a.stride(-2), a.stride(0) if multi else 0, _p(q), _p(ws),
                                 M, N, K, batch, _p(ha), _p(hb), slot_p, epoch, _stream()), 'gemm_f32_head')
-    tag_amax(a, slot)
-    global LAST_AMAX
-    LAST_AMAX = slot
-    LAST_SPLIT[0] = 2
-    return a, q
+    return _gemm_done(a, slot, 2), q
 
 
 # ---- one-token rollout step (T = 1, no autograd) ----------------------------------------------------------------------

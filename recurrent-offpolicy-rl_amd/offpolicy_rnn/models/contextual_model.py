@@ -78,12 +78,9 @@ class ContextualModel:
 
     # ------------------------------------------------------------------------------------------ forward
     def head_row_buffer(self, lead, device, dtype):
-        """A row buffer [prod(lead), uni input width + embedding width] for the head input of a long fp32 GPU pass (None otherwise): the
+        """A row buffer [prod(lead), uni input width + embedding width] for the head input of an fp32 GPU pass (None otherwise): the
         GEMMs that produce the input encoding and the embedding write their column blocks in place instead of a `cat` afterwards."""
-        rows = 1
-        for v in lead:
-            rows *= int(v)
-        if torch.device(device).type != 'cuda' or dtype != torch.float32 or rows < ops.GEMM_F32_MIN_ROWS or len(lead) == 0:
+        if torch.device(device).type != 'cuda' or dtype != torch.float32 or len(lead) == 0:
             return None
         return ops.RowBuffer(lead, self.uni_network.input_size, device)
 

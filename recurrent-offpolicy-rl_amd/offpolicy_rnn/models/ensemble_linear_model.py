@@ -31,7 +31,6 @@ class _SharedInput(torch.autograd.Function):
         """ax: magnitude handle of x2 (ops.amax_of) when the caller has one - saved tensors and reshaped views lose their tags."""
         E, n_in, n_out = weight.shape
         w_cat = weight.permute(1, 0, 2).reshape(n_in, E * n_out)                 # [in, E*out] (weights only: tiny copy)
-        ops.LAST_AMAX = None
         x2 = x2 if x2.stride(-1) == 1 else x2.contiguous()
         # bias + ELU in the GEMM's epilogue (837 us against the library's 995 at 66 752 x 384 -> 2048)
         y2 = ops.gemm_f32(x2, w_cat, True, False, None if bias is None else bias.reshape(E * n_out), act, amax_a=ax,
@@ -92,7 +91,6 @@ class _PerMember(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x3, weight, bias, act, ax=None):
         E, M, _ = x3.shape
-        ops.LAST_AMAX = None
         x3 = _unit(x3)
         # bias + ELU in the GEMM epilogue: 583 us against the library's 605 + a 140 us tail pass (8 x 66 752 x 256 x 256)
         y = ops.gemm_f32(x3, weight, True, False, bias, act, amax_a=ax)
@@ -228,7 +226,7 @@ def critic_mlp_fusable(l0, act0, l1, act1, l2, act2, x) -> bool:
         return False
     M = x.numel() // n_in
     x2 = x.reshape(-1, n_in)
-    return (min(n_in, H1, H2) >= 32 and H1 % 32 == 0 and H2 % 32 == 0 and ops.gemm_f32_ok(M, x2) and ops.rows_aligned16(x2)
+    return (min(n_in, H1, H2) >= 32 and H1 % 32 == 0 and H2 % 32 == 0 and ops.gemm_f32_ok(x2) and ops.rows_aligned16(x2)
             and ops.gemm_fused_ok(5, M, H2, H1, l1.weight) and ops.gemm_fused_ok(4, M, H1, H2, l1.weight))
 
 
@@ -302,14 +300,15 @@ class EnsembleLinear(nn.Module):
         elif nd == 5:
             shared = False
         ax = ops.amax_of(x)                  # magnitude handle of the input, if its producer left one (reshapes below drop the tag)
+        # y [E, M, out] comes back tagged with the magnitude its GEMM published, and so does the tensor it is a view of
         if shared:
             lead = tuple(x.shape[:-1])
             if grad_part is not None:
-                y = _SharedInput.apply(x.detach().reshape(-1, n_in), W, b, act, grad_part[0], grad_part[1], ax)
+                y = ops.apply_tagged(_SharedInput.apply, True, x.detach().reshape(-1, n_in), W, b, act, grad_part[0], grad_part[1], ax)
             else:
-                y = _SharedInput.apply(x.reshape(-1, n_in), W, b, act, None, 0, ax)
+                y = ops.apply_tagged(_SharedInput.apply, True, x.reshape(-1, n_in), W, b, act, None, 0, ax)
         else:
             assert grad_part is None, 'grad_part is a shared-input feature'
             lead = tuple(x.shape[1:-1])
-            y = _PerMember.apply(x.reshape(E, -1, n_in), W, b, act, ax)
-        return ops.tag_amax(y.reshape((E,) + lead + (n_out,)), ops.LAST_AMAX, whole=True)      # a view: only the row axis is split
+            y = ops.apply_tagged(_PerMember.apply, True, x.reshape(E, -1, n_in), W, b, act, ax)
+        return y.reshape((E,) + lead + (n_out,))       # a view (only the row axis is split): `amax_of` finds the tag through its base

@@ -363,7 +363,7 @@ class RNNBase(torch.nn.Module):
                     x, h = layer(x, hidden_state[k], hidden_state.mask)
                 elif lid.startswith('cgpt'):
                     multi = x.dim() == 3 and x.shape[-2] > 1          # whole packed rows (training) vs one rollout step
-                    fuse_act = multi and self._fuse_out_act(ind, x) and x.shape[0] * x.shape[1] >= ops.GEMM_F32_MIN_ROWS
+                    fuse_act = multi and self._fuse_out_act(ind, x)
                     x = layer(x, inference_params=None if multi else hidden_state[k],
                               seqlens=hidden_state.attention_concat_mask if multi else None, out_act='elu' if fuse_act else None)
                     h = hidden_state[k]

@@ -37,17 +37,17 @@ def register_encoders(owner):
 
 
 def _fusable(act_mod, x, mods) -> bool:
-    """The activation module behind the encoders is a plain ELU and the pass is a long fp32 GPU pass of Linear encoders: it rides in
+    """The activation module behind the encoders is a plain ELU and the pass is an fp32 GPU pass of Linear encoders: it rides in
     the encoder GEMM's epilogue (and its derivative in the backward's bias pass) instead of two element-wise ATen passes."""
     return (isinstance(act_mod, torch.nn.ELU) and act_mod.alpha == 1.0 and x.is_cuda and x.dtype == torch.float32
-            and x.numel() // x.shape[-1] >= ops.GEMM_F32_MIN_ROWS and all(isinstance(m, torch.nn.Linear) and m.bias is not None for m in mods))
+            and all(isinstance(m, torch.nn.Linear) and m.bias is not None for m in mods))
 
 
 def encode_concat(pairs, act_mod=None, dest=None) -> torch.Tensor:
-    """cat([enc_i(x_i)], -1) for Linear encoders as ONE library GEMM: the (narrow) inputs are concatenated instead of the
+    """cat([enc_i(x_i)], -1) for Linear encoders as ONE GEMM: the (narrow) inputs are concatenated instead of the
     (wide) outputs and multiplied by the block-diagonal of the encoder weights with the biases fused (addmm epilogue) -
     per update this removes three skinny GEMMs, three bias-add passes and the 384-wide cat per call.  The zero blocks
-    add exact zeros to every dot product; autograd splits the gradients back through block_diag / cat (long GPU passes: through
+    add exact zeros to every dot product; autograd splits the gradients back through block_diag / cat (GPU passes: through
     `ops.place_blocks`, one launch per operand, gradients as views).
     act_mod: the activation module applied to the result (None: none) - fused into the GEMM when `_fusable`.
     dest: an `ops.ColDest` the fused GEMM writes its output to in place (a column block of the head's row buffer)."""
@@ -60,13 +60,13 @@ def encode_concat(pairs, act_mod=None, dest=None) -> torch.Tensor:
     # no activation behind the encoders (`linear`): the same node without an epilogue, so that `dest` is honoured there too
     plain = (act_mod is None or isinstance(act_mod, torch.nn.Identity)) and _fusable(torch.nn.ELU(), xs[0], mods)
     if len(pairs) == 1:                       # one encoder alone (the actor step's action encoding): still the hand-written GEMM
-        if (fuse or plain) and mods[0].weight.shape[0] >= ops.GEMM_F32_MIN_DIM and mods[0].weight.shape[1] >= ops.GEMM_F32_MIN_K:
+        if fuse or plain:
             return ops.linear_act(xs[0], mods[0].weight, mods[0].bias, 'elu' if fuse else None, dest=dest)
         return (act_mod if fuse else post)(ops.linear(xs[0], mods[0].weight, mods[0].bias))
     ks, ns = [m.weight.shape[1] for m in mods], [m.weight.shape[0] for m in mods]
     kp = sum(ks) + (-sum(ks)) % 4            # 17 + 17 + 6 + 1 = 41 input columns: three zero columns make the rows 16-byte multiples,
-    if xs[0].is_cuda and xs[0].dtype == torch.float32 and xs[0].numel() // xs[0].shape[-1] >= ops.GEMM_F32_MIN_ROWS and len(mods) <= 8:
-        # which the hand-written GEMM needs (35 us against the library's 97 at 66 752 tokens).  Long GPU passes: the three operands are
+    if xs[0].is_cuda and xs[0].dtype == torch.float32 and len(mods) <= 8:
+        # which the hand-written GEMM needs (35 us against the library's 97 at 66 752 tokens).  GPU passes: the three operands are
         # assembled by ONE launch each (`ops.place_blocks`) and their gradients come back as views
         c0 = [sum(ks[:i]) for i in range(len(ks))]
         r0 = [sum(ns[:i]) for i in range(len(ns))]
@@ -83,7 +83,7 @@ def encode_concat(pairs, act_mod=None, dest=None) -> torch.Tensor:
             w = torch.nn.functional.pad(w, (0, pad))
         x = torch.cat(xs, dim=-1)
     x2 = x.reshape(-1, x.shape[-1])
-    if (fuse or plain) and w.shape[0] >= ops.GEMM_F32_MIN_DIM and w.shape[1] >= ops.GEMM_F32_MIN_K:
+    if fuse or plain:
         return ops.linear_act(x2, w, b, 'elu' if fuse else None, dest=dest).view(*x.shape[:-1], w.shape[0])
     y = ops.linear(x2, w, b)
     return (act_mod if fuse else post)(y.view(*x.shape[:-1], w.shape[0]))

@@ -54,7 +54,7 @@ class ContextualSACValue(ContextualModel):
                 ) -> Tuple[torch.Tensor, torch.Tensor, RNNHidden, Optional[RNNHidden]]:
         emb_in = None if self._prefetched is not None else self.get_embedding_input(state, lst_state, lst_action, reward)
         part = None
-        # long GPU passes: the head input [state-action encoding | embedding] is ONE row buffer whose column blocks the producing GEMMs write
+        # GPU passes: the head input [state-action encoding | embedding] is ONE row buffer whose column blocks the producing GEMMs write
         # in place (no cat of 205 MB per pass at config 2, one shared magnitude handle instead of a pre-pass)
         rb = self.head_row_buffer(state.shape[:-1], state.device, state.dtype) if self.separate_encoder else None
         if detach_embedding and torch.is_grad_enabled() and action.requires_grad and self._action_only_graph():
