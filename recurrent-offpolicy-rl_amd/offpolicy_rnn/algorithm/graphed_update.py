@@ -14,8 +14,18 @@ copies around the replay (not as nodes of it): `step()` never waits for the upda
 i + 1 (sampling plan, tables, graph launch) while update i runs; a slot is reused three updates later, after its event.
 Actor noise comes from torch's CUDA generator, which torch.cuda.graph registers: every replay draws fresh numbers.
 
-A graph is valid for ONE batch shape (rows, row length, number of plan segments, longest segment) - synthetic benches, fixed-length
-episodes.  Every `step()` is exactly ONE update (same update-to-data ratio and random streams as the eager loop): the first `warmup`
+A graph is valid for ONE batch shape (rows, row length, number of plan segments, longest segment).  With fixed-length episodes (the
+synthetic benches) the exact shape recurs on every update.  With early termination it hardly ever does - the sampler trims a batch
+to the longest row it drew - so the shapes are BUCKETED (`buckets`, buffers/transition_buffer/shape_buckets.py): rows, row length
+and plan entries are rounded up a coarse ladder (1, 2, 3, 4, 6, 8, 12, ...; rows of at least 32 slots, never past the ring's row
+capacity + 1) and the key becomes (rows, row length, plan entries).  The padding is what the sampler writes behind a short row
+anyway (`mask = 0, start = 1`; plan entries with row -1 are dropped by the gather kernel; the losses divide by the sum of the mask):
+the update computes the same thing on up to 1.5x the tokens, its GEMMs sum in another order (last-bit differences), and the actor
+noise is drawn for the padded tensor (another sample of the same distribution).  `buckets='off'`: exact keys only.  `'on'`: bucketed
+from the first update.  `'auto'`: exact keys until more distinct shapes (actor flag aside) have been seen than
+the graphs can hold, then bucketed for good - a fixed-length workload never switches and stays bit for bit what it was.  Not for
+attention layers (their token / cu_seqlens tables vary with the batch and would need buckets of their own): `'on'` raises, `'auto'`
+stays exact.  `train()` takes the mode from RESEL_GRAPH_BUCKETS (`buckets_from_env`: 1, auto; unset = 'off').  Every `step()` is exactly ONE update (same update-to-data ratio and random streams as the eager loop): the first `warmup`
 calls run eagerly (allocator and lazily initialised kernels warm up), a shape is recorded the SECOND time it occurs (a shape that
 never recurs is not worth two device synchronisations and an activation pool), at most `max_graphs` graphs live at a time in ONE
 shared memory pool (they never replay concurrently), the least recently used one is dropped for a newcomer - but an evicted shape must
@@ -40,9 +50,10 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from ..buffers.transition_buffer.shape_buckets import pad_plan
 from ..hip import ops
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
-from .sac_full_length_rnn_ensembleQ import DeferredLog
+from .sac_full_length_rnn_ensembleQ import NO_SEQ_BUCKETS, DeferredLog
 
 
 class _StaticLog(DeferredLog):
@@ -59,14 +70,36 @@ class GraphedUpdate:
     RECAPTURE_HITS = 8                                # occurrences an EVICTED shape needs before it is recorded again
     CAPTURE_WINDOW = 256                              # at most `max_graphs` recordings per this many updates: more recurring shapes than graphs run eagerly
 
-    def __init__(self, alg, warmup=3, max_graphs=None):
+    BUCKET_SHAPES = 8                                 # bucketed shapes held per launch sequence when the caller sets no `max_graphs`
+    NO_SEQ_BUCKETS = NO_SEQ_BUCKETS + "; use buckets='off' or 'auto'"
+
+    @staticmethod
+    def buckets_from_env():
+        """The `buckets` mode `train()` asks for: RESEL_GRAPH_BUCKETS = 1 'on', auto 'auto', 0 or unset 'off'; anything else is an error.
+        Unset is 'off' (not 'auto') until bucketed replays have been timed against eager launches at the published batch sizes
+        (profiles/r08_graph_buckets.md): a ragged workload is moved to padded batches only where its user asks for it."""
+        v = os.environ.get('RESEL_GRAPH_BUCKETS', '')
+        if v not in ('', '0', '1', 'auto'):
+            raise ValueError(f'RESEL_GRAPH_BUCKETS={v!r}: 1 (bucketed from the first update), auto (once the shapes turn out ragged), '
+                             f'0 or unset (exact shapes only)')
+        return {'': 'off', '0': 'off', '1': 'on', 'auto': 'auto'}[v]
+
+    def __init__(self, alg, warmup=3, max_graphs=None, buckets='off'):
         why = self.refusal(alg)
         if why:
             raise RuntimeError('GraphedUpdate: ' + why)
+        if buckets not in ('off', 'on', 'auto'):
+            raise ValueError(f'GraphedUpdate: buckets={buckets!r} (off, on, auto)')
+        if buckets == 'on' and getattr(alg, '_needs_seq_table', False):
+            raise RuntimeError('GraphedUpdate: ' + self.NO_SEQ_BUCKETS)
         self.alg, self.device = alg, alg.device
         self.graphs = OrderedDict()                   # batch shape key -> CUDAGraph, least recently used first
-        if max_graphs is None:                        # four batch shapes; with policy_update_per > 1 every shape has two launch sequences
-            max_graphs = 4 * (2 if alg.parameter.policy_update_per > 1 else 1)
+        self._sequences = 2 if alg.parameter.policy_update_per > 1 else 1   # launch sequences per shape: with / without the actor step
+        self._own_max_graphs = max_graphs is None
+        if max_graphs is None:                        # four exact (eight bucketed) batch shapes per launch sequence
+            max_graphs = (self.BUCKET_SHAPES if buckets == 'on' else 4) * self._sequences
+        self.buckets = buckets                        # 'auto' becomes 'on' at most once (_count_shape)
+        self._shapes = set()                          # 'auto': distinct exact shapes seen so far
         self.warmup, self.max_graphs = warmup, max_graphs
         self._eager_left = warmup                     # updates still to run eagerly before anything is recorded
         self._seen = OrderedDict()                    # batch shape key -> occurrences so far (least recently seen first; pruned to SEEN_CAP)
@@ -244,12 +277,15 @@ class GraphedUpdate:
     def _prepare(self):
         alg, par = self.alg, self.alg.parameter
         pl = alg.replay_buffer.plan_trajs_device(par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj,
-                                                 nest_stack_trajs=alg.allow_nest_stack)
+                                                 nest_stack_trajs=alg.allow_nest_stack, buckets=self.buckets == 'on')
+        if self.buckets == 'auto' and self._count_shape(pl):
+            pl = pad_plan(pl, alg.replay_buffer.max_traj_step)              # the plan that tipped the count is the first bucketed one
         alg.replay_buffer._mirror(self.device)        # transitions pushed since the last update reach the device ring HERE, outside the graph
         n = pl['seg'].shape[0]
         if n > self.PLAN_CAPACITY:
             raise RuntimeError(f'GraphedUpdate: {n} plan segments exceed the static plan buffer ({self.PLAN_CAPACITY})')
-        key = (pl['nrow'], pl['longest'], pl['max_len'], n)
+        # bucketed: `max_len` is the row length (it only sizes the gather grid)
+        key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else (pl['nrow'], pl['longest'], pl['max_len'], n)
         built = self._build_seqs(pl) if self._drop_base is not None else None
         # staging slot of this update: its copies of three updates ago have long run; the log handed out then is read out before its block is reused
         slot = self._slot = self._ring[self._turn % self.RING]
@@ -274,6 +310,25 @@ class GraphedUpdate:
                 opt.prepare_step(slot['bc'][2 * i:2 * i + 2])
         self._turn += 1
         return key + (bool(actor_due),)
+
+    def _count_shape(self, pl):
+        """'auto': True once, when this exact shape is one more than the graphs can hold (`max_graphs` over the launch sequences) - the
+        workload is ragged, exact keys would leave most updates eager.  Drops what was recorded and counted for exact keys."""
+        if getattr(self.alg, '_needs_seq_table', False):                    # attention layers: no buckets (NO_SEQ_BUCKETS)
+            return False
+        self._shapes.add((pl['nrow'], pl['longest'], pl['max_len'], pl['seg'].shape[0]))
+        if len(self._shapes) <= max(1, self.max_graphs // self._sequences):
+            return False
+        self.buckets = 'on'
+        if self._own_max_graphs:
+            self.max_graphs = self.BUCKET_SHAPES * self._sequences
+        self.graphs.clear()
+        self._seen.clear()
+        self._captures = []
+        self.alg.logger(f'update graphs: {len(self._shapes)} batch shapes in {self._steps + 1} updates - batch shapes are bucketed from here on '
+                        f'(RESEL_GRAPH_BUCKETS=0 keeps exact shapes)')
+        self._shapes.clear()
+        return True
 
     def _body(self):
         alg = self.alg
@@ -303,7 +358,7 @@ class GraphedUpdate:
         slot['used'] = True
         items = dict(self._log_items)
         pl = self._plan                               # the host entries of THIS update (the captured dict holds the recorded update's)
-        items.update(real_batch_size=pl['total_size'], real_batch_traj_num=pl['nrow'],
+        items.update(real_batch_size=pl['total_size'], real_batch_traj_num=pl.get('nrow_real', pl['nrow']),
                      average_traj_len=self.alg.replay_buffer.size / len(self.alg.replay_buffer))
         slot['handed'] = _StaticLog(list(self._log_keys), slot['log'][:n], slot['evt'], items)
         return slot['handed']

@@ -222,7 +222,9 @@ class SAC:
             if why:
                 self.logger(f'updates are launched eagerly ({why})')
             else:
-                graphed = GraphedUpdate(self)
+                # RESEL_GRAPH_BUCKETS (variable-length episodes): 1 = batch shapes bucketed from the first update, auto = once the workload
+                # turns out ragged (fixed-length ones never switch), 0 / unset = exact shapes only
+                graphed = GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())
                 update = graphed.step
         try:
             self._train_loop(update)

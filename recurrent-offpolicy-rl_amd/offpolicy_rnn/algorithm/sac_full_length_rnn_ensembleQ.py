@@ -66,6 +66,10 @@ def _ensemble_subset(model, member_index):
             l.member_index = None
 
 
+NO_SEQ_BUCKETS = 'shape buckets do not cover layers that need sequence tables (cgpt): the token and cu_seqlens tables vary with the batch ' \
+                 'and are not bucketed'
+
+
 class DeferredLog(dict):
     """The update's log dict.  Host-side entries are plain items; the device scalars travel in one asynchronous copy into
     pinned memory and become floats on first access (`resolve()`), so a caller that does not read them - a training loop
@@ -156,6 +160,9 @@ class SACFullLengthRNNEnsembleQ(SAC):
         self.target_policy.eval()
         self.grad_sync = GradSync()
         self._graph = None                             # set while a captured update is being recorded / replayed (graphed_update.py)
+        # eager updates pad their batch into its shape bucket (shape_buckets.py; tests, tools).  Device replay ring only, and not with
+        # attention layers (their sequence tables are not bucketed): `_train_one_batch` raises otherwise
+        self.shape_buckets = False
         self._subset_rng = None                        # REDQ subset stream: None = numpy's global stream (see _subset_stream)
         self._pinned = PinnedRing(torch.float32)       # staging blocks of the host-built batch (one event per block)
         self._needs_seq_table = any(lid.startswith('cgpt') for net in (self.values[0].uni_network, self.values[0].embedding_network,
@@ -480,6 +487,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
         host: Dict[str, float] = {}
         for utd_idx in range(par.utd):
             self.timer.register_point(tag='sample_trajs', level=2)
+            real_rows = None
             if self._graph is not None:
                 # captured update (algorithm/graphed_update.py): the host half of the sampling ran before the replay, the plan sits in
                 # static buffers; here only the device half is enqueued (a memcpy node + the gather kernel)
@@ -489,17 +497,24 @@ class SACFullLengthRNNEnsembleQ(SAC):
             elif getattr(self, 'device_replay', False) and self.device.type == 'cuda' \
                     and self.replay_buffer.device_supported(randomize_mask=par.randomize_mask):
                 # device-resident ring: the host decides WHICH trajectories go where, the batch array is built on the GPU
+                if self.shape_buckets and self._needs_seq_table:
+                    raise RuntimeError('shape_buckets: ' + NO_SEQ_BUCKETS)
                 dev, batch_size, table = self.replay_buffer.sample_trajs_device(
-                    self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack)
+                    self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack,
+                    buckets=self.shape_buckets)
+                real_rows = self.replay_buffer._last_real_rows
                 self.timer.register_end(level=2)
                 b = self._batch_views(dev, table)
             else:
+                if self.shape_buckets:
+                    raise RuntimeError('shape_buckets: only batches assembled from the device replay ring are bucketed')
                 batch, batch_size, valid, table = self.replay_buffer.sample_trajs(
                     par.sac_batch_size, None, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized,
                     equalize_data_of_each_traj=True, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack)
                 self.timer.register_end(level=2)
                 b = self._upload_batch(batch, valid, table)
             rows = b['state'].shape[0]
+            real_rows = real_rows or rows                        # rows drawn: fewer than `rows` only for a bucketed batch
             value, target_value = self.values[0], self.target_values[0]
             # hidden states + side channels: the target pass uses the one-slot-earlier flags (reference :368-378)
             target_policy_hidden = self._make_hidden(self.policy, rows, b['total_start'], b['total_valid'], b['target_attention_mask'])
@@ -608,14 +623,14 @@ class SACFullLengthRNNEnsembleQ(SAC):
         keys = list(scal)
         packed = torch.stack([scal[k].reshape(()).float() for k in keys])
         if self._graph is not None:                              # captured update: a D2H node into the graph's static pinned buffer
-            return self._graph.log_node(keys, packed, host, dict(real_batch_size=batch_size, real_batch_traj_num=rows,
+            return self._graph.log_node(keys, packed, host, dict(real_batch_size=batch_size, real_batch_traj_num=real_rows,
                                                                   average_traj_len=self.replay_buffer.size / len(self.replay_buffer),
                                                                   amp_scalar_pi=0, amp_scalar_q=0))
         if ops.AMAX_VERIFY and self.device.type == 'cuda':       # RESEL_AMAX_VERIFY=1: every mode-2 product of this update had its handles checked
             ops.amax_verify_raise(self.device)
         log = DeferredLog(keys, packed, pinned=self.device.type == 'cuda')     # ONE device->host copy of all scalars
         log.set_host({k: float(v) for k, v in host.items()})
-        log.set_host(dict(real_batch_size=batch_size, real_batch_traj_num=rows,
+        log.set_host(dict(real_batch_size=batch_size, real_batch_traj_num=real_rows,
                           average_traj_len=self.replay_buffer.size / len(self.replay_buffer), amp_scalar_pi=0, amp_scalar_q=0))
         if not getattr(self, 'defer_log', False):
             log.resolve()                                        # reference behaviour: floats in hand when the call returns

@@ -12,6 +12,7 @@ from typing import Tuple
 import numpy as np
 
 from .replay_memory import MemoryArray, Transition
+from .shape_buckets import pad_plan
 
 
 class NestedMemoryArray(MemoryArray):
@@ -159,9 +160,12 @@ class NestedMemoryArray(MemoryArray):
         self._dirty = []
         return st['buf']
 
-    def plan_trajs_device(self, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False, nest_stack_trajs=True):
+    def plan_trajs_device(self, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False, nest_stack_trajs=True,
+                          buckets=False):
         """Host half of `sample_trajs_device`: the same sampling decisions (and numpy RNG consumption) as `sample_trajs`.  Returns a dict
-        with the int32 plan `seg` [nseg, 4] = (row, first slot, length incl. skip, first transition) and the scalars the gather needs."""
+        with the int32 plan `seg` [nseg, 4] = (row, first slot, length incl. skip, first transition) and the scalars the gather needs.
+        `buckets`: the same plan padded into its shape bucket (shape_buckets.py) - rows, row length and plan entries rounded up, the
+        drawn values kept in `nrow_real` / `longest_real`."""
         skip = self._skip_step
         if get_all:
             picked = np.arange(self.available_traj_num)
@@ -191,7 +195,8 @@ class NestedMemoryArray(MemoryArray):
         for r, seq in enumerate(table):
             traj_len_array[r, :len(seq)] = seq
         seg = np.asarray(plan, dtype=np.int32)
-        return dict(seg=seg, max_len=int(seg[:, 2].max()), nrow=nrow, longest=longest, total_size=total_size, table=traj_len_array)
+        pl = dict(seg=seg, max_len=int(seg[:, 2].max()), nrow=nrow, longest=longest, total_size=total_size, table=traj_len_array)
+        return pad_plan(pl, self.max_traj_step) if buckets else pl
 
     def _gather_pairs(self, device):
         import torch
@@ -216,12 +221,14 @@ class NestedMemoryArray(MemoryArray):
         return out
 
     def sample_trajs_device(self, device, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False,
-                            nest_stack_trajs=True):
+                            nest_stack_trajs=True, buckets=False):
         """Same sampling decisions (and numpy RNG consumption) as `sample_trajs`, but the batch array is assembled on the
         device by `ops.gather_trajs` from the device mirror of the ring: returns (batch [rows, T', W + 3] on `device`,
-        total_size, traj_len_array)."""
+        total_size, traj_len_array).  `buckets`: the batch padded into its shape bucket (empty rows and trailing slots are
+        `mask = 0, start = 1`); the number of rows drawn is left in `_last_real_rows`."""
         import torch
-        pl = self.plan_trajs_device(batch_size, max_sample_size, get_all, random_trunc_traj, nest_stack_trajs)
+        pl = self.plan_trajs_device(batch_size, max_sample_size, get_all, random_trunc_traj, nest_stack_trajs, buckets=buckets)
+        self._last_real_rows = pl.get('nrow_real', pl['nrow'])
         seg = pl['seg']
         st = self._gather_pairs(device)
         # the plan block is rewritten on every sample while earlier copies may still be queued: one event per block
