@@ -21,6 +21,7 @@
 // per step.]  Neither roofline is tight for this layer; the reported figure is the achieved step rate.
 #include "resel_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 using namespace resel;
@@ -540,78 +541,88 @@ inline int pick_kc(int H) {
         if (H % kc == 0 && H / kc <= KQMAX && H / kc >= 4) return kc;
     return 0;
 }
+// The run-time KC as a template argument: f(std::integral_constant<int, KC>) for the six instantiations, RESEL_EINVAL for any other KC.
+template <typename F>
+inline int with_kc(int KC, F&& f) {
+    switch (KC) {
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 24: return f(std::integral_constant<int, 24>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+    }
+    return RESEL_EINVAL;
+}
 inline bool gru_ok(int B, int L, int H) { return B > 0 && L > 0 && H > 0 && H % 16 == 0 && H <= HMAX && pick_kc(H) > 0; }
-inline size_t wlayout_floats(int H) { return (size_t)3 * H * H; }
+inline int gru_workgroups(int B, int H) { return (H / US) * ((B + RG - 1) / RG); }     // of one network: unit slices x row groups
+
+// Workspace of one call on n networks (the single-network entries: n = 1):
+//   [n x W copy (3 H H floats each) | carry (2 B H floats; single-network entries only) | n x (exchange granules, 8 bytes each; error word in 64 bytes)]
+// The granule / error blocks of all networks are contiguous: one memset clears them.
+struct GruWorkspace {
+    char* base;
+    size_t n, w_bytes, carry_bytes, granule_bytes;
+    GruWorkspace(void* workspace, int n_net, int B, int H, bool with_carry)
+        : base((char*)workspace), n((size_t)n_net), w_bytes((size_t)3 * H * H * sizeof(float)),
+          carry_bytes(with_carry ? (size_t)2 * B * H * sizeof(float) : 0), granule_bytes((size_t)((B + RG - 1) / RG) * 2 * RG * H * sizeof(u64)) {}
+    size_t sync_bytes() const { return granule_bytes + 64; }                            // per network
+    size_t bytes() const { return n * (w_bytes + sync_bytes()) + carry_bytes; }
+    float* wcopy(int k = 0) const { return (float*)(base + k * w_bytes); }
+    float* carry() const { return (float*)(base + n * w_bytes); }
+    char* sync(int k = 0) const { return base + n * w_bytes + carry_bytes + k * sync_bytes(); }
+    u64* xchg(int k = 0) const { return (u64*)sync(k); }
+    int* err(int k = 0) const { return (int*)(sync(k) + granule_bytes); }
+};
+
+// RESEL_GRU_PERSISTENT=0 forces the launch-per-step form (read once per process)
+inline bool gru_persistent_allowed() {
+    static const int mode = getenv("RESEL_GRU_PERSISTENT") ? atoi(getenv("RESEL_GRU_PERSISTENT")) : 1;
+    return mode != 0;
+}
+// persistent form: all workgroups must be co-resident.  The backward kernel runs at 2 waves per SIMD (2 workgroups per CU),
+// so the grid is capped at one workgroup per CU of the smallest configuration this library targets (256 CUs); larger
+// problems keep the launch-per-step form.
+// (the multi-network forward below has its own residency rule: its grid is up to four times as large)
+inline bool persistent_ok(int B, int H) { return gru_persistent_allowed() && gru_workgroups(B, H) <= 256; }
 
 }  // namespace
 
-inline size_t xchg_granules(int B, int H) { return (size_t)((B + RG - 1) / RG) * 2 * RG * H; }
-// [W copy | carry (2 B H floats) | exchange granules (8 bytes each) | error word]
-inline size_t xchg_offset_bytes(int B, int H) { return (wlayout_floats(H) + (size_t)2 * B * H) * sizeof(float); }
-
 extern "C" size_t resel_gru_workspace_bytes(int B, int L, int H) {
     (void)L;
-    return xchg_offset_bytes(B, H) + xchg_granules(B, H) * sizeof(unsigned long long) + 64;
+    return GruWorkspace(nullptr, 1, B, H, true).bytes();
 }
-
-// persistent form: all workgroups must be co-resident.  The backward kernel runs at 2 waves per SIMD (2 workgroups per CU),
-// so the grid is capped at one workgroup per CU of the smallest configuration this library targets (256 CUs); larger
-// problems keep the launch-per-step form.  RESEL_GRU_PERSISTENT=0 forces the launch-per-step form.
-inline bool persistent_ok(int B, int H) {
-    static const int mode = getenv("RESEL_GRU_PERSISTENT") ? atoi(getenv("RESEL_GRU_PERSISTENT")) : 1;
-    return mode != 0 && (H / US) * ((B + RG - 1) / RG) <= 256;
-}
-// (the multi-network forward below has its own residency rule: its grid is up to four times as large)
 
 extern "C" int resel_gru_seq_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0,
                                  float* h_all, float* gates, void* workspace, int B, int L, int H, resel_stream_t stream) {
     if (!gi || !w_hh || !b_hh || !h_all || !workspace || !gru_ok(B, L, H)) return RESEL_EINVAL;
     if (!aligned16(h_all) || !aligned16(workspace) || (h0 && !aligned16(h0))) return RESEL_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* wf = (float*)workspace;
+    const GruWorkspace ws(workspace, 1, B, H, true);
     const int64_t nw = (int64_t)3 * H * H;
     const int KC = pick_kc(H), KQ = H / KC;
-    hipLaunchKernelGGL(gru_layout_fwd_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w_hh, wf, H, KQ);
-    GruFwd p{gi, wf, b_hh, h0, h_all, gates, B, L, H, 0};
+    hipLaunchKernelGGL(gru_layout_fwd_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w_hh, ws.wcopy(), H, KQ);
+    GruFwd p{gi, ws.wcopy(), b_hh, h0, h_all, gates, B, L, H, 0};
     if (persistent_ok(B, H)) {
-        char* base = (char*)workspace + xchg_offset_bytes(B, H);
-        u64* xchg = (u64*)base;
-        int* err = (int*)(base + xchg_granules(B, H) * sizeof(u64));
-        if (hipMemsetAsync(base, 0, xchg_granules(B, H) * sizeof(u64) + 64, s) != hipSuccess) return RESEL_ELAUNCH;
-        const dim3 pgrid((H / US) * ((B + RG - 1) / RG));
-        switch (KC) {
-            case 4: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<4>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 8: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<8>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 12: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<12>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 16: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<16>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 24: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<24>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 32: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<32>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            default: return RESEL_EINVAL;
-        }
-        return launch_status();
+        if (hipMemsetAsync(ws.sync(), 0, ws.sync_bytes(), s) != hipSuccess) return RESEL_ELAUNCH;
+        const dim3 pgrid(gru_workgroups(B, H));
+        return with_kc(KC, [&](auto kc) {
+            launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_persistent_kernel<decltype(kc)::value>, pgrid, dim3(16 * KQ), 0, s, p, ws.xchg(), ws.err());
+            return launch_status();
+        });
     }
     dim3 grid(H / US, (B + RG - 1) / RG);
-    for (int t = 0; t < L; ++t) {
-        p.t = t;
-        switch (KC) {
-            case 4: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<4>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 8: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<8>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 12: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<12>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 16: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<16>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 24: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<24>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 32: launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<32>, grid, dim3(16 * KQ), 0, s, p); break;
-            default: return RESEL_EINVAL;
+    return with_kc(KC, [&](auto kc) {
+        for (int t = 0; t < L; ++t) {
+            p.t = t;
+            launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_step_kernel<decltype(kc)::value>, grid, dim3(16 * KQ), 0, s, p);
         }
-    }
-    return launch_status();
+        return launch_status();
+    });
 }
 
 // ---- multi-network forward ------------------------------------------------------------------------------------------
-// workspace: [n x W copy (3 H H floats each) | n x (exchange granules, error word in 64 bytes) | slack], n x the single-network size
-// (rounded to 16 bytes) in all, so that a caller may size either way.  The granule / error blocks of all networks are contiguous:
-// one memset clears them.
-inline size_t multi_sync_bytes(int B, int H) { return xchg_granules(B, H) * sizeof(u64) + 64; }
-
+// workspace: GruWorkspace without a carry; sized n x the single-network size (rounded to 16 bytes), so that a caller may size either way.
 extern "C" size_t resel_gru_multi_workspace_bytes(int n_net, int B, int L, int H) {
     if (n_net < 1) n_net = 1;
     return (size_t)n_net * ((resel_gru_workspace_bytes(B, L, H) + 15) & ~(size_t)15);
@@ -647,23 +658,11 @@ inline int multi_resident_cap() {
     return cap;
 }
 inline int multi_cap(int KC) {
-    switch (KC) {
-        case 4: return multi_resident_cap<4>();
-        case 8: return multi_resident_cap<8>();
-        case 12: return multi_resident_cap<12>();
-        case 16: return multi_resident_cap<16>();
-        case 24: return multi_resident_cap<24>();
-        case 32: return multi_resident_cap<32>();
-    }
-    return 0;
-}
-inline bool gru_persistent_allowed() {               // RESEL_GRU_PERSISTENT=0 forces the launch-per-step form (read once per process)
-    static const int mode = getenv("RESEL_GRU_PERSISTENT") ? atoi(getenv("RESEL_GRU_PERSISTENT")) : 1;
-    return mode != 0;
+    const int cap = with_kc(KC, [](auto kc) { return multi_resident_cap<decltype(kc)::value>(); });
+    return cap > 0 ? cap : 0;                            // no instantiation for this KC: nothing is resident
 }
 inline bool multi_persistent_ok(int n_net, int B, int H) {
-    if (!gru_persistent_allowed()) return false;
-    return n_net * (H / US) * ((B + RG - 1) / RG) <= multi_cap(pick_kc(H));
+    return gru_persistent_allowed() && n_net * gru_workgroups(B, H) <= multi_cap(pick_kc(H));
 }
 
 extern "C" int resel_gru_multi_form(int n_net, int B, int H) {
@@ -680,46 +679,37 @@ extern "C" int resel_gru_multi_fwd(int n_net, const float* const* gi, const floa
         if (!gi[n] || !w_hh[n] || !b_hh[n] || !h_all[n] || !aligned16(h_all[n]) || (h0 && h0[n] && !aligned16(h0[n]))) return RESEL_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
+    const GruWorkspace ws(workspace, n_net, B, H, false);
     const int64_t nw = (int64_t)3 * H * H;
     const int KC = pick_kc(H), KQ = H / KC;
-    const int per_net = (H / US) * ((B + RG - 1) / RG);
-    char* sync = (char*)workspace + (size_t)n_net * wlayout_floats(H) * sizeof(float);
     GruLayoutMulti lay{};
     GruFwdMulti m{};
     for (int n = 0; n < n_net; ++n) {
-        float* wf = (float*)workspace + (size_t)n * wlayout_floats(H);
-        char* base = sync + (size_t)n * multi_sync_bytes(B, H);
         lay.w_hh[n] = w_hh[n];
-        lay.wf[n] = wf;
-        m.net[n] = GruFwd{gi[n], wf, b_hh[n], h0 ? h0[n] : nullptr, h_all[n], gates ? gates[n] : nullptr, B, L, H, 0};
-        m.xchg[n] = (u64*)base;
-        m.err[n] = (int*)(base + xchg_granules(B, H) * sizeof(u64));
+        lay.wf[n] = ws.wcopy(n);
+        m.net[n] = GruFwd{gi[n], ws.wcopy(n), b_hh[n], h0 ? h0[n] : nullptr, h_all[n], gates ? gates[n] : nullptr, B, L, H, 0};
+        m.xchg[n] = ws.xchg(n);
+        m.err[n] = ws.err(n);
     }
-    m.per_net = per_net;
+    m.per_net = gru_workgroups(B, H);
     hipLaunchKernelGGL(gru_layout_fwd_multi_kernel, dim3((unsigned)((nw + 255) / 256), n_net), dim3(256), 0, s, lay, H, KQ);
     // the error words are cleared in either form: callers read them after the pass
-    if (hipMemsetAsync(sync, 0, (size_t)n_net * multi_sync_bytes(B, H), s) != hipSuccess) return RESEL_ELAUNCH;
-#define RESEL_GRU_MULTI_CASE(KCV, KERNEL, GRID)                                                              \
-    case KCV: launch_timed(RESEL_PROF_GRU_FWD, KERNEL<KCV>, GRID, dim3(16 * KQ), 0, s, m); break;
-#define RESEL_GRU_MULTI_SWITCH(KERNEL, GRID)                                                                 \
-    switch (KC) {                                                                                            \
-        RESEL_GRU_MULTI_CASE(4, KERNEL, GRID) RESEL_GRU_MULTI_CASE(8, KERNEL, GRID) RESEL_GRU_MULTI_CASE(12, KERNEL, GRID) \
-        RESEL_GRU_MULTI_CASE(16, KERNEL, GRID) RESEL_GRU_MULTI_CASE(24, KERNEL, GRID) RESEL_GRU_MULTI_CASE(32, KERNEL, GRID) \
-        default: return RESEL_EINVAL;                                                                        \
-    }
+    if (hipMemsetAsync(ws.sync(), 0, (size_t)n_net * ws.sync_bytes(), s) != hipSuccess) return RESEL_ELAUNCH;
     if (multi_persistent_ok(n_net, B, H)) {
-        const dim3 pgrid((unsigned)(n_net * per_net));
-        RESEL_GRU_MULTI_SWITCH(gru_fwd_multi_persistent_kernel, pgrid)
-        return launch_status();
+        const dim3 pgrid((unsigned)(n_net * m.per_net));
+        return with_kc(KC, [&](auto kc) {
+            launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_multi_persistent_kernel<decltype(kc)::value>, pgrid, dim3(16 * KQ), 0, s, m);
+            return launch_status();
+        });
     }
     const dim3 grid(H / US, (B + RG - 1) / RG, n_net);
-    for (int t = 0; t < L; ++t) {
-        for (int n = 0; n < n_net; ++n) m.net[n].t = t;
-        RESEL_GRU_MULTI_SWITCH(gru_fwd_multi_step_kernel, grid)
-    }
-#undef RESEL_GRU_MULTI_SWITCH
-#undef RESEL_GRU_MULTI_CASE
-    return launch_status();
+    return with_kc(KC, [&](auto kc) {
+        for (int t = 0; t < L; ++t) {
+            for (int n = 0; n < n_net; ++n) m.net[n].t = t;
+            launch_timed(RESEL_PROF_GRU_FWD, gru_fwd_multi_step_kernel<decltype(kc)::value>, grid, dim3(16 * KQ), 0, s, m);
+        }
+        return launch_status();
+    });
 }
 
 extern "C" int resel_gru_seq_bwd(const float* w_hh, const float* h0, const float* h_all, const float* gates,
@@ -728,45 +718,30 @@ extern "C" int resel_gru_seq_bwd(const float* w_hh, const float* h0, const float
     if (!w_hh || !h_all || !gates || !dh_all || !dgi || !dgh || !workspace || !gru_ok(B, L, H)) return RESEL_EINVAL;
     if (!aligned16(workspace)) return RESEL_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* wb = (float*)workspace;
-    float* carry = wb + wlayout_floats(H);
+    const GruWorkspace ws(workspace, 1, B, H, true);
+    float* carry = ws.carry();
     const int64_t nw = (int64_t)3 * H * H;
     const int KC = pick_kc(H), KQ = H / KC;
-    hipLaunchKernelGGL(gru_layout_bwd_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w_hh, wb, H, KQ);
-    if (hipMemsetAsync(carry, 0, (size_t)2 * B * H * sizeof(float), s) != hipSuccess) return RESEL_ELAUNCH;
-    GruBwd p{wb, h0, h_all, gates, dh_all, nullptr, nullptr, dgi, dgh, B, L, H, 0};
+    hipLaunchKernelGGL(gru_layout_bwd_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w_hh, ws.wcopy(), H, KQ);
+    if (hipMemsetAsync(carry, 0, ws.carry_bytes, s) != hipSuccess) return RESEL_ELAUNCH;
+    GruBwd p{ws.wcopy(), h0, h_all, gates, dh_all, nullptr, nullptr, dgi, dgh, B, L, H, 0};
     if (persistent_ok(B, H)) {
-        char* base = (char*)workspace + xchg_offset_bytes(B, H);
-        u64* xchg = (u64*)base;
-        int* err = (int*)(base + xchg_granules(B, H) * sizeof(u64));
-        if (hipMemsetAsync(base, 0, xchg_granules(B, H) * sizeof(u64) + 64, s) != hipSuccess) return RESEL_ELAUNCH;
+        if (hipMemsetAsync(ws.sync(), 0, ws.sync_bytes(), s) != hipSuccess) return RESEL_ELAUNCH;
         p.carry_out = carry;
-        const dim3 pgrid((H / US) * ((B + RG - 1) / RG));
-        switch (KC) {
-            case 4: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<4>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 8: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<8>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 12: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<12>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 16: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<16>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 24: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<24>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            case 32: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<32>, pgrid, dim3(16 * KQ), 0, s, p, xchg, err); break;
-            default: return RESEL_EINVAL;
-        }
-        return launch_status();
+        const dim3 pgrid(gru_workgroups(B, H));
+        return with_kc(KC, [&](auto kc) {
+            launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<decltype(kc)::value>, pgrid, dim3(16 * KQ), 0, s, p, ws.xchg(), ws.err());
+            return launch_status();
+        });
     }
     dim3 grid(H / US, (B + RG - 1) / RG);
-    for (int t = L - 1; t >= 0; --t) {
-        p.t = t;
-        p.carry_in = carry + (size_t)((t + 1) & 1) * B * H;
-        p.carry_out = carry + (size_t)(t & 1) * B * H;
-        switch (KC) {
-            case 4: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<4>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 8: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<8>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 12: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<12>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 16: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<16>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 24: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<24>, grid, dim3(16 * KQ), 0, s, p); break;
-            case 32: launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<32>, grid, dim3(16 * KQ), 0, s, p); break;
-            default: return RESEL_EINVAL;
+    return with_kc(KC, [&](auto kc) {
+        for (int t = L - 1; t >= 0; --t) {
+            p.t = t;
+            p.carry_in = carry + (size_t)((t + 1) & 1) * B * H;
+            p.carry_out = carry + (size_t)(t & 1) * B * H;
+            launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_step_kernel<decltype(kc)::value>, grid, dim3(16 * KQ), 0, s, p);
         }
-    }
-    return launch_status();
+        return launch_status();
+    });
 }

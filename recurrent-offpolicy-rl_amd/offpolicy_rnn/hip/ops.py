@@ -54,6 +54,11 @@ def _flags(t: Optional[torch.Tensor], B: int, L: int) -> Optional[torch.Tensor]:
     return t.reshape(B, L).to(torch.float32).contiguous()
 
 
+def _h0(h0: Optional[torch.Tensor], B: int, C: int) -> Optional[torch.Tensor]:
+    """Initial state of a recurrence -> dense fp32 [B, C]."""
+    return None if h0 is None else h0.float().reshape(B, C).contiguous()
+
+
 def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -86,6 +91,48 @@ def profile_collect():
 SSCAN_TIME_SEGMENTS = int(os.environ.get('RESEL_SSCAN_TIME_SEGMENTS', '0'))
 
 
+# The marshalling sites of the scan and conv entries (one per entry; `SelectiveScanFn`, `CausalConv1dFn` and `MambaInnerFn` call them).  A
+# token-major operand is a [B, L, C] tensor or an [M = B L, C] column block of a wider matrix, unit stride on its last axis: the kernel
+# gets its `data_ptr()` and, as token stride, its `stride(-2)`.  The caller allocates every output; the workspace belongs to the helper.
+def _sscan_fwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, out, ck, last, softplus, amax_out=None, epoch=0):
+    """softplus: the entry's `delta_softplus` code (0 / 1, or the mixer's 6); amax_out, epoch: magnitude slot of `out` (pointer) or None."""
+    Di, N = A.shape
+    nb = lib().resel_selective_scan_fwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS)
+    check(lib().resel_selective_scan_fwd(
+        _p(u), u.stride(-2), _p(delta), delta.stride(-2), _p(z), 0 if z is None else z.stride(-2), _p(A),
+        _p(Bm), Bm.stride(-2), _p(Cm), Cm.stride(-2), _p(D), _p(delta_bias), _p(start),
+        _p(out), out.stride(-2), _p(ck), _p(last), _p(_ws(nb, u.device) if nb else None), Bsz, L, Di, N, softplus,
+        SSCAN_TIME_SEGMENTS, amax_out, epoch, _stream()), 'selective_scan_fwd')
+
+
+def _sscan_bwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, dout, ck, du, ddelta, dz, dB, dC, dA, dD, dbias, softplus,
+               amax_dz=None, amax_ddelta=None, epoch=0):
+    Di, N = A.shape
+    ws = _ws(lib().resel_selective_scan_bwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS), u.device)
+    check(lib().resel_selective_scan_bwd(
+        _p(u), u.stride(-2), _p(delta), delta.stride(-2), _p(z), 0 if z is None else z.stride(-2), _p(A),
+        _p(Bm), Bm.stride(-2), _p(Cm), Cm.stride(-2), _p(D), _p(delta_bias), _p(start),
+        _p(dout), dout.stride(-2), _p(ck),
+        _p(du), du.stride(-2), _p(ddelta), ddelta.stride(-2), _p(dz), 0 if dz is None else dz.stride(-2),
+        _p(dB), dB.stride(-2), _p(dC), dC.stride(-2), _p(dA), _p(dD), _p(dbias), _p(ws),
+        Bsz, L, Di, N, softplus, SSCAN_TIME_SEGMENTS, amax_dz, amax_ddelta, epoch, _stream()), 'selective_scan_bwd')
+
+
+def _conv_fwd(Bsz, L, x, w, bias, mask, y, act, amax_y=None, epoch=0):
+    Di, K = w.shape
+    check(lib().resel_causal_conv1d_fwd(_p(x), x.stride(-2), _p(w), _p(bias), _p(mask), _p(y), y.stride(-2), Bsz, L, Di, K, act,
+                                        amax_y, epoch, _stream()), 'causal_conv1d_fwd')
+
+
+def _conv_bwd(Bsz, L, x, w, bias, mask, dy, dy2, dx, dw, db, act, amax_dx=None, epoch=0):
+    """dy2: second part of the output gradient, summed with dy on load, or None (then this is the library's `resel_causal_conv1d_bwd`)."""
+    Di, K = w.shape
+    ws = _ws(lib().resel_causal_conv1d_bwd_workspace_bytes(Bsz, L, Di, K), x.device)
+    check(lib().resel_causal_conv1d_bwd2(_p(x), x.stride(-2), _p(w), _p(bias), _p(mask), _p(dy), dy.stride(-2),
+                                         _p(dy2), 0 if dy2 is None else dy2.stride(-2), _p(dx), dx.stride(-2), _p(dw), _p(db), _p(ws),
+                                         Bsz, L, Di, K, act, amax_dx, epoch, _stream()), 'causal_conv1d_bwd')
+
+
 class SelectiveScanFn(torch.autograd.Function):
     """Token-major selective scan with start resets.  Interface counterpart of the reference's
     `SelectiveScanFn` (mamba_ssm/ops/selective_scan_interface_new.py:19-84)."""
@@ -107,12 +154,7 @@ class SelectiveScanFn(torch.autograd.Function):
         if need_grad:
             ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), u.device)
         last = torch.empty(Bsz, Di, N, dtype=torch.float32, device=u.device) if return_last_state else None
-        nb = lib().resel_selective_scan_fwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS)
-        check(lib().resel_selective_scan_fwd(
-            _p(u), u.stride(1), _p(delta), delta.stride(1), _p(z), 0 if z is None else z.stride(1), _p(A),
-            _p(Bm), Bm.stride(1), _p(Cm), Cm.stride(1), _p(D), _p(delta_bias), _p(start),
-            _p(out), out.stride(1), _p(ck), _p(last), _p(_ws(nb, u.device) if nb else None), Bsz, L, Di, N, int(bool(delta_softplus)),
-            SSCAN_TIME_SEGMENTS, None, 0, _stream()), 'selective_scan_fwd')
+        _sscan_fwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, out, ck, last, int(bool(delta_softplus)))
         ctx.save_for_backward(u, delta, A, Bm, Cm, D, z, delta_bias, start, ck)
         ctx.softplus = bool(delta_softplus)
         if return_last_state:
@@ -135,14 +177,7 @@ class SelectiveScanFn(torch.autograd.Function):
         dA = torch.empty(Di, N, dtype=torch.float32, device=dev)
         dD = torch.empty(Di, dtype=torch.float32, device=dev) if D is not None else None
         dbias = torch.empty(Di, dtype=torch.float32, device=dev) if delta_bias is not None else None
-        ws = _ws(lib().resel_selective_scan_bwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS), dev)
-        check(lib().resel_selective_scan_bwd(
-            _p(u), u.stride(1), _p(delta), delta.stride(1), _p(z), 0 if z is None else z.stride(1), _p(A),
-            _p(Bm), Bm.stride(1), _p(Cm), Cm.stride(1), _p(D), _p(delta_bias), _p(start),
-            _p(dout), dout.stride(1), _p(ck),
-            _p(du), du.stride(1), _p(ddelta), ddelta.stride(1), _p(dz), 0 if dz is None else dz.stride(1),
-            _p(dB), dB.stride(1), _p(dC), dC.stride(1), _p(dA), _p(dD), _p(dbias), _p(ws),
-            Bsz, L, Di, N, int(ctx.softplus), SSCAN_TIME_SEGMENTS, None, None, 0, _stream()), 'selective_scan_bwd')
+        _sscan_bwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, dout, ck, du, ddelta, dz, dB, dC, dA, dD, dbias, int(ctx.softplus))
         return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None, None
 
 
@@ -191,8 +226,7 @@ class MambaInnerFn(torch.autograd.Function):
         xc = torch.empty(M, Di, dtype=torch.float32, device=x.device)
         track = amax_tracking() and M * Di >= (1 << 20)                    # publish the magnitudes of the tensors the projections read
         h_xc, p_xc, e_xc = _slot_args(track, x.device)
-        check(lib().resel_causal_conv1d_fwd(_p(xz), 2 * Di, _p(cw), _p(conv_b), _p(maskf), _p(xc), Di, Bsz, L, Di, K, 1, p_xc, e_xc, _stream()),
-              'causal_conv1d_fwd')
+        _conv_fwd(Bsz, L, xz, cw, conv_b, maskf, xc, 1, p_xc, e_xc)          # reads the x half: the first Di columns of xz's rows
         tag_amax(xc, h_xc)
         x_dbl = mm_nt(xc, xproj_w)                                         # [M, R + 2N] = (delta_r | B | C)
         # delta = softplus(dt_proj(.) + bias) leaves the GEMM epilogue: the scan kernels spend no vector issue on it
@@ -209,13 +243,8 @@ class MambaInnerFn(torch.autograd.Function):
         need_grad = any(ctx.needs_input_grad)
         ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), x.device) if need_grad else None
         y = torch.empty(M, Di, dtype=torch.float32, device=x.device)
-        zptr = ctypes.c_void_p(xz.data_ptr() + 4 * Di)
-        bptr, cptr = ctypes.c_void_p(x_dbl.data_ptr() + 4 * R), ctypes.c_void_p(x_dbl.data_ptr() + 4 * (R + N))
-        nb = lib().resel_selective_scan_fwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS)
         h_y, p_y, e_y = _slot_args(track, x.device)
-        check(lib().resel_selective_scan_fwd(_p(xc), Di, _p(dt), Di, zptr, 2 * Di, _p(A), bptr, R + 2 * N, cptr, R + 2 * N,
-                                             _p(D), None, _p(startf), _p(y), Di, _p(ck), None, _p(_ws(nb, x.device) if nb else None),
-                                             Bsz, L, Di, N, 6, SSCAN_TIME_SEGMENTS, p_y, e_y, _stream()), 'selective_scan_fwd')
+        _sscan_fwd(Bsz, L, xc, dt, xz[:, Di:], A, x_dbl[:, R:R + N], x_dbl[:, R + N:], D, None, startf, y, ck, None, 6, p_y, e_y)
         tag_amax(y, h_y)
         out = mm_nt(y, out_w)
         ctx.handles = keep_handles(ctx.ax, h_xc, h_y)                      # saved tensors come back untagged
@@ -242,16 +271,11 @@ class MambaInnerFn(torch.autograd.Function):
         dA = torch.empty(Di, N, dtype=torch.float32, device=dev)
         dD = torch.empty(Di, dtype=torch.float32, device=dev)
         ddt_b = torch.empty(Di, dtype=torch.float32, device=dev)
-        ws = _ws(lib().resel_selective_scan_bwd_workspace_bytes(Bsz, L, Di, N, SSCAN_TIME_SEGMENTS), dev)
-        P = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
         track = amax_tracking() and M * Di >= (1 << 20)
         h_dxz, p_dxz, e_b = _slot_args(track, dev)                         # ONE handle for dxz: the scan fills its z half, the conv its x half
         h_ddt, p_ddt, _ = _slot_args(track, dev)                           # (published under the same epoch e_b)
-        check(lib().resel_selective_scan_bwd(
-            _p(xc), Di, _p(dt), Di, P(xz, Di), 2 * Di, _p(A), P(x_dbl, R), R + 2 * N, P(x_dbl, R + N), R + 2 * N,
-            _p(D), None, _p(startf), _p(dy), Di, _p(ck),
-            _p(dxc), Di, _p(ddt), Di, P(dxz, Di), 2 * Di, P(dx_dbl, R), R + 2 * N, P(dx_dbl, R + N), R + 2 * N,
-            _p(dA), _p(dD), _p(ddt_b), _p(ws), Bsz, L, Di, N, 6, SSCAN_TIME_SEGMENTS, p_dxz, p_ddt, e_b, _stream()), 'selective_scan_bwd')
+        _sscan_bwd(Bsz, L, xc, dt, xz[:, Di:], A, x_dbl[:, R:R + N], x_dbl[:, R + N:], D, None, startf, dy, ck,
+                   dxc, ddt, dxz[:, Di:], dx_dbl[:, R:R + N], dx_dbl[:, R + N:], dA, dD, ddt_b, 6, p_dxz, p_ddt, e_b)
         tag_amax(ddt, h_ddt)
         # [Di, R] with a 66 752-long reduction: hand-written MFMA kernel (the library reaches 7 TFLOP/s on this shape)
         d_dt_w = atb(ddt, x_dbl[:, :R]) if R <= 32 and Di % 4 == 0 and ddt.stride(1) == 1 and ddt.stride(0) % 4 == 0 \
@@ -263,9 +287,7 @@ class MambaInnerFn(torch.autograd.Function):
         gx = mm_nn(dx_dbl, xproj_w)
         dcw = torch.empty(Di, K, dtype=torch.float32, device=dev)
         dcb = torch.empty(Di, dtype=torch.float32, device=dev) if conv_b is not None else None
-        ws2 = _ws(lib().resel_causal_conv1d_bwd_workspace_bytes(Bsz, L, Di, K), dev)
-        check(lib().resel_causal_conv1d_bwd2(_p(xz), 2 * Di, _p(cw), _p(conv_b), _p(maskf), _p(dxc), Di, _p(gx), gx.stride(0) if gx is not None else 0, _p(dxz), 2 * Di,
-                                             _p(dcw), _p(dcb), _p(ws2), Bsz, L, Di, K, 1, p_dxz, e_b, _stream()), 'causal_conv1d_bwd')
+        _conv_bwd(Bsz, L, xz, cw, conv_b, maskf, dxc, gx, dxz, dcw, dcb, 1, p_dxz, e_b)       # x halves of xz and dxz: their rows' first Di columns
         tag_amax(dxz, h_dxz)
         d_in_w = wgrad(dxz, x2, amax_x=ax)
         dx = mm_nn(dxz, in_w).view(Bsz, L, Dm) if ctx.needs_input_grad[0] else None
@@ -285,12 +307,10 @@ class CausalConv1dFn(torch.autograd.Function):
         x = _tok_major(x)
         Bsz, L, Di = x.shape
         w = weight.float().reshape(Di, -1).contiguous()
-        K = w.shape[1]
         bias = None if bias is None else bias.float().contiguous()
         mask = _flags(mask, Bsz, L)
         y = torch.empty(Bsz, L, Di, dtype=torch.float32, device=x.device)
-        check(lib().resel_causal_conv1d_fwd(_p(x), x.stride(1), _p(w), _p(bias), _p(mask), _p(y), y.stride(1),
-                                            Bsz, L, Di, K, int(bool(activation)), None, 0, _stream()), 'causal_conv1d_fwd')
+        _conv_fwd(Bsz, L, x, w, bias, mask, y, int(bool(activation)))
         ctx.save_for_backward(x, w, bias, mask)
         ctx.act = bool(activation)
         ctx.wshape = weight.shape
@@ -305,10 +325,7 @@ class CausalConv1dFn(torch.autograd.Function):
         dx = torch.empty(Bsz, L, Di, dtype=torch.float32, device=x.device)
         dw = torch.empty(Di, K, dtype=torch.float32, device=x.device)
         db = torch.empty(Di, dtype=torch.float32, device=x.device) if bias is not None else None
-        ws = _ws(lib().resel_causal_conv1d_bwd_workspace_bytes(Bsz, L, Di, K), x.device)
-        check(lib().resel_causal_conv1d_bwd(_p(x), x.stride(1), _p(w), _p(bias), _p(mask), _p(dy), dy.stride(1),
-                                            _p(dx), dx.stride(1), _p(dw), _p(db), _p(ws), Bsz, L, Di, K, int(ctx.act),
-                                            None, 0, _stream()), 'causal_conv1d_bwd')
+        _conv_bwd(Bsz, L, x, w, bias, mask, dy, None, dx, dw, db, int(ctx.act))
         return dx, dw.reshape(ctx.wshape), db, None, None
 
 
@@ -413,6 +430,13 @@ def _real_fwd(v, f, ld, start, h0, fuse_act):
     return h
 
 
+def _real_bwd(v, f, ld, start, h0, h, dh, dv, df, ld_d, fuse_act, amax_d=None, epoch=0):
+    """dv, df: token rows `ld_d` floats apart (dense tensors, or the two members of one tensor whose magnitude slot is amax_d)."""
+    Bsz, L, C = v.shape
+    check(lib().resel_linrec_real_bwd(_p(v), _p(f), ld, _p(start), _p(h0), _p(h), _p(dh), _p(dv), _p(df), ld_d, Bsz, L, C,
+                                      int(fuse_act), amax_d, epoch, _stream()), 'linrec_real_bwd')
+
+
 class GilrScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, f, start, h0, fuse_act):
@@ -420,7 +444,7 @@ class GilrScanFn(torch.autograd.Function):
         (v, f), ld = _token_rows(v, f)
         Bsz, L, C = v.shape
         start = _flags(start, Bsz, L)
-        h0 = None if h0 is None else h0.float().reshape(Bsz, C).contiguous()
+        h0 = _h0(h0, Bsz, C)
         h = _real_fwd(v, f, ld, start, h0, fuse_act)
         ctx.save_for_backward(v, f, start, h0, h)
         ctx.act, ctx.ld = bool(fuse_act), ld
@@ -433,8 +457,7 @@ class GilrScanFn(torch.autograd.Function):
         dh = dh.float().contiguous()
         dv = torch.empty(Bsz, L, C, dtype=torch.float32, device=v.device)
         df = torch.empty_like(dv)
-        check(lib().resel_linrec_real_bwd(_p(v), _p(f), ctx.ld, _p(start), _p(h0), _p(h), _p(dh), _p(dv), _p(df), C, Bsz, L, C,
-                                          int(ctx.act), None, 0, _stream()), 'linrec_real_bwd')
+        _real_bwd(v, f, ctx.ld, start, h0, h, dh, dv, df, C, ctx.act)
         return dv, df, None, None, None
 
 
@@ -450,7 +473,7 @@ class GilrMembersFn(torch.autograd.Function):
         u, ld = _member_rows(u)
         _, Bsz, L, C = u.shape
         start = _flags(start, Bsz, L)
-        h0 = None if h0 is None else h0.float().reshape(Bsz, C).contiguous()
+        h0 = _h0(h0, Bsz, C)
         h = _real_fwd(u[0], u[1], ld, start, h0, fuse_act)
         ctx.save_for_backward(u, start, h0, h)
         ctx.act, ctx.ld = bool(fuse_act), ld
@@ -459,12 +482,10 @@ class GilrMembersFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh):
         u, start, h0, h = ctx.saved_tensors
-        _, Bsz, L, C = u.shape
         dh = dh.float().contiguous()
         du = _like_members(u)
         slot, slot_p, epoch = _slot_args(amax_tracking() and du.numel() >= (1 << 20), u.device)
-        check(lib().resel_linrec_real_bwd(_p(u[0]), _p(u[1]), ctx.ld, _p(start), _p(h0), _p(h), _p(dh), _p(du[0]), _p(du[1]), du.stride(2),
-                                          Bsz, L, C, int(ctx.act), slot_p, epoch, _stream()), 'linrec_real_bwd')
+        _real_bwd(u[0], u[1], ctx.ld, start, h0, h, dh, du[0], du[1], du.stride(2), ctx.act, slot_p, epoch)
         return tag_amax(du, slot), None, None, None
 
 
@@ -497,20 +518,16 @@ def _complex_args(lam_re, lam_im, gamma, start, h0r, h0i, Bsz, L, C):
     lam_re, lam_im = lam_re.float().contiguous(), lam_im.float().contiguous()
     gamma = None if gamma is None else gamma.float().contiguous()
     start = _flags(start, Bsz, L)
-    h0r = None if h0r is None else h0r.float().reshape(Bsz, C).contiguous()
-    h0i = None if h0i is None else h0i.float().reshape(Bsz, C).contiguous()
-    return lam_re, lam_im, gamma, start, h0r, h0i
+    return lam_re, lam_im, gamma, start, _h0(h0r, Bsz, C), _h0(h0i, Bsz, C)
 
 
-def _complex_bwd(vr, vi, ld, lam_re, lam_im, gamma, start, h0r, h0i, h2, dh2, dvr, dvi, ld_du):
+def _complex_bwd(vr, vi, ld, lam_re, lam_im, gamma, start, h0r, h0i, h2, dh2, dvr, dvi, ld_du, dlr, dli, dg):
+    """dvr, dvi: token rows `ld_du` floats apart; dlr, dli, dg [C]: separate tensors or the rows of one [3, C] tensor (dg None without gamma)."""
     Bsz, L, C = vr.shape
-    dlr, dli = torch.empty_like(lam_re), torch.empty_like(lam_im)
-    dg = torch.empty_like(lam_re) if gamma is not None else None
     ws = _ws(lib().resel_linrec_complex_bwd_workspace_bytes(Bsz, L, C), vr.device)
     check(lib().resel_linrec_complex_bwd(_p(vr), _p(vi), ld, _p(lam_re), _p(lam_im), _p(gamma), _p(start), _p(h0r), _p(h0i),
                                          _p(h2[0]), _p(h2[1]), _p(dh2[0]), _p(dh2[1]), _p(dvr), _p(dvi), ld_du, _p(dlr), _p(dli), _p(dg),
                                          _p(ws), Bsz, L, C, _stream()), 'linrec_complex_bwd')
-    return dlr, dli, dg
 
 
 class LruScanFn(torch.autograd.Function):
@@ -532,7 +549,9 @@ class LruScanFn(torch.autograd.Function):
         dh2 = (dhr.float().contiguous(), dhi.float().contiguous())
         dvr = torch.empty(Bsz, L, C, dtype=torch.float32, device=vr.device)
         dvi = torch.empty_like(dvr)
-        dlr, dli, dg = _complex_bwd(vr, vi, ctx.ld, lam_re, lam_im, gamma, start, h0r, h0i, h2, dh2, dvr, dvi, C)
+        dlr, dli = torch.empty_like(lam_re), torch.empty_like(lam_im)
+        dg = torch.empty_like(lam_re) if gamma is not None else None
+        _complex_bwd(vr, vi, ctx.ld, lam_re, lam_im, gamma, start, h0r, h0i, h2, dh2, dvr, dvi, C, dlr, dli, dg)
         return dvr, dvi, dlr, dli, dg, None, None, None
 
 
@@ -586,15 +605,12 @@ class LruMembersFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh2, du2):
         u, lam3, start, h0r, h0i, h2 = ctx.saved_tensors
-        E, Bsz, L, C = u.shape
         dh2 = dh2.float().contiguous()
         du = _like_members(u)
         dlam3 = torch.empty_like(lam3)
-        ws = _ws(lib().resel_linrec_complex_bwd_workspace_bytes(Bsz, L, C), u.device)
-        check(lib().resel_linrec_complex_bwd(_p(u[0]), _p(u[1]), ctx.ld, _p(lam3[0]), _p(lam3[1]), _p(lam3[2]), _p(start), _p(h0r), _p(h0i),
-                                             _p(h2[0]), _p(h2[1]), _p(dh2[0]), _p(dh2[1]), _p(du[0]), _p(du[1]), du.stride(2),
-                                             _p(dlam3[0]), _p(dlam3[1]), _p(dlam3[2]), _p(ws), Bsz, L, C, _stream()), 'linrec_complex_bwd')
-        if E == 3:
+        _complex_bwd(u[0], u[1], ctx.ld, lam3[0], lam3[1], lam3[2], start, h0r, h0i, h2, dh2, du[0], du[1], du.stride(2),
+                     dlam3[0], dlam3[1], dlam3[2])
+        if u.shape[0] == 3:
             if du2 is None:
                 du[2].zero_()
             else:
@@ -634,15 +650,20 @@ class SubAddMembers(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------- GRU
+def _gru_operands(gi, w_hh, b_hh, h0):
+    """The operands of a GRU recurrence as the kernels read them: dense fp32 gi [B, L, 3H], w_hh, b_hh and h0 [B, H] (or None)."""
+    gi = gi.float().contiguous()
+    Bsz, _, H3 = gi.shape
+    return gi, w_hh.float().contiguous(), b_hh.float().contiguous(), _h0(h0, Bsz, H3 // 3)
+
+
 class GruSeqFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gi, w_hh, b_hh, h0):
         _need_cuda('gru_seq', gi, w_hh, b_hh)
-        gi = gi.float().contiguous()
+        gi, w_hh, b_hh, h0 = _gru_operands(gi, w_hh, b_hh, h0)
         Bsz, L, H3 = gi.shape
         H = H3 // 3
-        w_hh, b_hh = w_hh.float().contiguous(), b_hh.float().contiguous()
-        h0 = None if h0 is None else h0.float().reshape(Bsz, H).contiguous()
         need_grad = any(ctx.needs_input_grad)
         h_all = torch.empty(Bsz, L, H, dtype=torch.float32, device=gi.device)
         gates = torch.empty(Bsz, L, 4 * H, dtype=torch.float32, device=gi.device) if need_grad else None
@@ -684,8 +705,8 @@ class _GruSeqAttachFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gi, w_hh, b_hh, h0, done):
         h_all, gates = done
-        h0 = None if h0 is None else h0.float().reshape(h_all.shape[0], h_all.shape[2]).contiguous()
-        ctx.save_for_backward(w_hh.float().contiguous(), h0, h_all, gates)
+        _, w_hh, _, h0 = _gru_operands(gi, w_hh, b_hh, h0)
+        ctx.save_for_backward(w_hh, h0, h_all, gates)
         return h_all
 
     @staticmethod
@@ -711,10 +732,7 @@ def gru_seq_multi(jobs):
     prep = []
     for gi, w_hh, b_hh, h0, need_grad in jobs:
         _need_cuda('gru_seq_multi', gi, w_hh, b_hh, h0)
-        gi_c = gi.float().contiguous()
-        Bsz, L, H3 = gi_c.shape
-        h0_c = None if h0 is None else h0.float().reshape(Bsz, H3 // 3).contiguous()
-        prep.append((gi_c, w_hh.float().contiguous(), b_hh.float().contiguous(), h0_c))
+        prep.append(_gru_operands(gi, w_hh, b_hh, h0))
     Bsz, L, H3 = prep[0][0].shape
     H = H3 // 3
     if any(tuple(p[0].shape) != (Bsz, L, H3) for p in prep):

@@ -479,9 +479,13 @@ def test_lru_params_one_launch_vs_torch(ops):
 
 
 # ------------------------------------------------------------------------------------------------ GRU
-@pytest.mark.parametrize('B,L,H', [(3, 20, 64), (18, 40, 256), (2, 130, 32), (5, 9, 80), (2, 6, 384), (68, 6, 256)])
+@pytest.mark.parametrize('B,L,H', [(3, 20, 64), (18, 40, 256), (2, 130, 32), (5, 9, 80), (2, 6, 384), (68, 6, 256),
+                                   (3, 7, 192), (3, 5, 512),                                                       # persistent, KC = 12, 32
+                                   (344, 3, 48), (208, 3, 80), (88, 3, 192), (44, 3, 384), (36, 3, 512)])          # per step, KC = 4, 8, 12, 24, 32
 def test_gru_seq_fwd_bwd_vs_aten(ops, B, L, H):
-    """Against torch.nn.GRU on CPU (the reference's GRU layer is exactly that module, rnn_base.py:59)."""
+    """Against torch.nn.GRU on CPU (the reference's GRU layer is exactly that module, rnn_base.py:59).  With H / KC = 4 ... 16 reduction
+    pieces per unit, KC = 4, 8, 12, 16, 24, 32 is picked for H = 32 / 48 / 64, 80, 192, 256, 384, 512; a grid of (H/16) * ceil(B/4) > 256
+    workgroups takes the launch-per-step form.  Every KC runs forward and backward in both forms."""
     g = torch.Generator().manual_seed(H + L)
     gru = torch.nn.GRU(H, H, batch_first=True)
     with torch.no_grad():
