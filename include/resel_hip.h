@@ -243,6 +243,31 @@ int resel_attn_varlen_bwd(const uint16_t* qkv, const int32_t* cu_seqlens, const 
                           const float* lse, const uint16_t* dout, uint16_t* dqkv, void* workspace,
                           int T, int S, int H, int hd, int max_seqlen, float scale,
                           float p_drop, uint64_t seed, uint64_t offset, resel_stream_t stream);
+/* Padded forms (sequence tables of a shape bucket, algorithm/graphed_update.py `seq_buckets`): same arguments, same kernels and
+ * workspaces, but T may exceed cu_seqlens[S] and sequences may have length zero (cu_seqlens padded by repeating its last value).
+ * Rows [0, cu_seqlens[S]) are bit for bit what the entries above give on the unpadded problem; rows [cu_seqlens[S], T) of out, of
+ * every head's lse and of dqkv are written as zero by one more pass that reads the token count on the device and touches only
+ * that tail (no whole-tensor memset) - inside a recorded graph's static pool they would otherwise hold stale bits. */
+int resel_attn_varlen_fwd_padded(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, uint16_t* out, float* lse,
+                                 void* workspace, int T, int S, int H, int hd, int max_seqlen, float scale,
+                                 float p_drop, uint64_t seed, uint64_t offset, resel_stream_t stream);
+int resel_attn_varlen_bwd_padded(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, const uint16_t* out,
+                                 const float* lse, const uint16_t* dout, uint16_t* dqkv, void* workspace,
+                                 int T, int S, int H, int hd, int max_seqlen, float scale,
+                                 float p_drop, uint64_t seed, uint64_t offset, resel_stream_t stream);
+
+/* Token packing with a DEVICE-side token count (padded sequence tables: idx has the bucket's length T, *n_dev = cu_seqlens[S] of
+ * them are real).  fp32 rows of C floats, C % 4 == 0, 16-byte aligned bases, leading dimensions multiples of 4.
+ *   pack:   out[t] = t < *n_dev ? src[idx[t]] : 0 for t < T  (what `index_select` does at a fixed size, plus a zero tail);
+ *           idx[t] must be a row of src for t < *n_dev, the entries behind are never read.
+ *   unpack: EVERY row m < M of dst is written exactly once per call: packed[t] where some t < *n_dev has idx[t] == m, zeros
+ *           otherwise (what `zeros.index_copy` does, without a memset pass, without a write race, deterministic).  idx must be
+ *           strictly increasing over [0, *n_dev) - a per-row binary search finds the source.
+ * *n_dev is clamped to [0, T].  Each is the other's gradient (a padded token carries a zero gradient). */
+int resel_pack_rows(const float* src, int64_t ld_src, const int64_t* idx, const int32_t* n_dev, float* out, int64_t ld_out,
+                    int T, int C, resel_stream_t stream);
+int resel_unpack_rows(const float* packed, int64_t ld, const int64_t* idx, const int32_t* n_dev, float* dst, int64_t ld_dst,
+                      int M, int T, int C, resel_stream_t stream);
 
 /* Element-wise dropout y = keep(i) ? x / (1 - p) : 0 with the keep mask a counter function of (seed, offset, element index)
  * (16-bit threshold round((1 - p) * 65536); oracle/kernels.py `dropout_keep`).  Replaces the `nn.Dropout`s of the cgpt

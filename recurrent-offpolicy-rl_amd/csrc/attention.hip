@@ -912,6 +912,27 @@ void launch_bwd(const AttnParams& p, const bf16_t* out, dim3 gq, dim3 gk, hipStr
     launch_timed(RESEL_PROF_ATTN_DKV, attn_dkv_kernel<HD, DROP>, gk, dim3(256), 0, s, p);
 }
 
+// Padded problems (`_padded` entries): T is a bucketed token count >= cu[S], the attention kernels above leave the rows [cu[S], T)
+// unwritten.  This pass writes zeros there and NOWHERE else: the real token count is read on the device, a workgroup in front of
+// the tail returns without a memory access.  rows: [T][rv] 16-byte pieces (out: H * hd / 8 per token, dqkv: 3 H * hd / 8);
+// lse: [H][T] fp32 or nullptr.
+__global__ __launch_bounds__(256) void attn_tail_zero_kernel(const int32_t* __restrict__ cu, int S, uint4* __restrict__ rows, int rv,
+                                                             float* __restrict__ lse, int H, int T) {
+    const int n = min(max(cu[S], 0), T);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nv = (int64_t)(T - n) * rv;
+    uint4* tail = rows + (int64_t)n * rv;
+    for (int64_t i = first; i < nv; i += stride) tail[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (lse != nullptr) {
+        const int64_t nl = (int64_t)(T - n) * H;
+        for (int64_t i = first; i < nl; i += stride) lse[(i / (T - n)) * T + n + i % (T - n)] = 0.f;
+    }
+}
+inline void launch_tail_zero(const int32_t* cu, int S, void* rows, int rv, float* lse, int H, int T, hipStream_t s) {
+    const int64_t blocks = ((int64_t)T * rv + 255) / 256;
+    hipLaunchKernelGGL(attn_tail_zero_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, cu, S, (uint4*)rows, rv, lse, H, T);
+}
+
 }  // namespace
 
 extern "C" int resel_attn_varlen_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, uint16_t* out, float* lse,
@@ -961,5 +982,27 @@ extern "C" int resel_attn_varlen_bwd(const uint16_t* qkv, const int32_t* cu_seql
     const bool drop = p_drop > 0.f;
     if (hd == 32) { if (drop) launch_bwd<32, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<32, false>(p, (const bf16_t*)out, gq, gk, s); }
     else          { if (drop) launch_bwd<64, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<64, false>(p, (const bf16_t*)out, gq, gk, s); }
+    return launch_status();
+}
+
+// The same launches on a padded problem (sequence tables of a shape bucket: zero-length sequences behind the real ones, T >= cu[S]),
+// followed by the pass that defines the token tail.
+extern "C" int resel_attn_varlen_fwd_padded(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, uint16_t* out, float* lse,
+                                            void* workspace, int T, int S, int H, int hd, int max_seqlen, float scale,
+                                            float p_drop, uint64_t seed, uint64_t offset, resel_stream_t stream) {
+    const int rc = resel_attn_varlen_fwd(qkv, cu_seqlens, slopes, out, lse, workspace, T, S, H, hd, max_seqlen, scale, p_drop, seed, offset, stream);
+    if (rc != RESEL_OK) return rc;
+    launch_tail_zero(cu_seqlens, S, out, H * hd / 8, lse, H, T, (hipStream_t)stream);
+    return launch_status();
+}
+
+extern "C" int resel_attn_varlen_bwd_padded(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, const uint16_t* out,
+                                            const float* lse, const uint16_t* dout, uint16_t* dqkv, void* workspace,
+                                            int T, int S, int H, int hd, int max_seqlen, float scale,
+                                            float p_drop, uint64_t seed, uint64_t offset, resel_stream_t stream) {
+    const int rc = resel_attn_varlen_bwd(qkv, cu_seqlens, slopes, out, lse, dout, dqkv, workspace, T, S, H, hd, max_seqlen, scale, p_drop, seed,
+                                         offset, stream);
+    if (rc != RESEL_OK) return rc;
+    launch_tail_zero(cu_seqlens, S, dqkv, 3 * H * hd / 8, nullptr, H, T, (hipStream_t)stream);
     return launch_status();
 }

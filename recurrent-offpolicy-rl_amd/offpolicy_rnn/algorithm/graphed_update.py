@@ -23,9 +23,14 @@ anyway (`mask = 0, start = 1`; plan entries with row -1 are dropped by the gathe
 the update computes the same thing on up to 1.5x the tokens, its GEMMs sum in another order (last-bit differences), and the actor
 noise is drawn for the padded tensor (another sample of the same distribution).  `buckets='off'`: exact keys only.  `'on'`: bucketed
 from the first update.  `'auto'`: exact keys until more distinct shapes (actor flag aside) have been seen than
-the graphs can hold, then bucketed for good - a fixed-length workload never switches and stays bit for bit what it was.  Not for
-attention layers (their token / cu_seqlens tables vary with the batch and would need buckets of their own): `'on'` raises, `'auto'`
-stays exact.  `train()` takes the mode from RESEL_GRAPH_BUCKETS (`buckets_from_env`: 1, auto; unset = 'off').  Every `step()` is exactly ONE update (same update-to-data ratio and random streams as the eager loop): the first `warmup`
+the graphs can hold, then bucketed for good - a fixed-length workload never switches and stays bit for bit what it was.
+Attention layers (cgpt) need more: their token / cu_seqlens tables vary with the batch inside one batch bucket.  By default `'on'`
+raises for them and `'auto'` stays exact.  With `seq_buckets` (RESEL_GRAPH_SEQ_BUCKETS=1; opt-in like the bucket mode itself,
+profiles/r09_cgpt_buckets.md) the two tables are padded into one more bucket (`shape_buckets.pad_seq_tables`: token count up the
+ladder, sequences to a power of two - empty sequences, the real token count stays in cu_seqlens' last element ON THE DEVICE), the
+decoder packs / unpacks with kernels that read that count (`ops.pack_tokens` / `unpack_tokens`) and the attention core defines the
+token tail (`ops.attn_varlen(padded=True)`); the bucketed key is (rows, row length, plan entries, tokens, cu entries, attention
+blocks per row, actor flag) and has in practice as many values as the batch bucket alone.  `train()` takes the mode from RESEL_GRAPH_BUCKETS (`buckets_from_env`: 1, auto; unset = 'off').  Every `step()` is exactly ONE update (same update-to-data ratio and random streams as the eager loop): the first `warmup`
 calls run eagerly (allocator and lazily initialised kernels warm up), a shape is recorded the SECOND time it occurs (a shape that
 never recurs is not worth two device synchronisations and an activation pool), at most `max_graphs` graphs live at a time in ONE
 shared memory pool (they never replay concurrently), the least recently used one is dropped for a newcomer - but an evicted shape must
@@ -50,7 +55,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from ..buffers.transition_buffer.shape_buckets import pad_plan
+from ..buffers.transition_buffer.shape_buckets import pad_plan, pad_seq_tables
 from ..hip import ops
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
 from .sac_full_length_rnn_ensembleQ import NO_SEQ_BUCKETS, DeferredLog
@@ -84,13 +89,25 @@ class GraphedUpdate:
                              f'0 or unset (exact shapes only)')
         return {'': 'off', '0': 'off', '1': 'on', 'auto': 'auto'}[v]
 
-    def __init__(self, alg, warmup=3, max_graphs=None, buckets='off'):
+    @staticmethod
+    def seq_buckets_from_env():
+        """`seq_buckets=None` of the constructor: RESEL_GRAPH_SEQ_BUCKETS = 1 on; 0, empty or unset off; anything else is an error.
+        Off until bucketed cgpt replays have been timed at the published sizes (profiles/r09_cgpt_buckets.md)."""
+        v = os.environ.get('RESEL_GRAPH_SEQ_BUCKETS', '')
+        if v not in ('', '0', '1'):
+            raise ValueError(f'RESEL_GRAPH_SEQ_BUCKETS={v!r}: 1 (pad the sequence tables of attention layers into buckets), '
+                             f'0 or unset (such layers keep exact shapes)')
+        return v == '1'
+
+    def __init__(self, alg, warmup=3, max_graphs=None, buckets='off', seq_buckets=None):
         why = self.refusal(alg)
         if why:
             raise RuntimeError('GraphedUpdate: ' + why)
         if buckets not in ('off', 'on', 'auto'):
             raise ValueError(f'GraphedUpdate: buckets={buckets!r} (off, on, auto)')
-        if buckets == 'on' and getattr(alg, '_needs_seq_table', False):
+        # read HERE, not by the caller: `train()` builds `GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())`
+        self.seq_buckets = self.seq_buckets_from_env() if seq_buckets is None else bool(seq_buckets)
+        if buckets == 'on' and getattr(alg, '_needs_seq_table', False) and not self.seq_buckets:
             raise RuntimeError('GraphedUpdate: ' + self.NO_SEQ_BUCKETS)
         self.alg, self.device = alg, alg.device
         self.graphs = OrderedDict()                   # batch shape key -> CUDAGraph, least recently used first
@@ -190,8 +207,9 @@ class GraphedUpdate:
         tam = np.concatenate((am[:, 1:], np.zeros((rows, 1), dtype=np.int32)), axis=1)
         return [PackedSeqs.build_host(a, T) for a in (am, tam)]
 
-    def _prepare_seqs(self, built):
-        """Both descriptions into the pinned buffers (the previous replay has read them); returns their part of the shape key."""
+    def _prepare_seqs(self, built, padded_key=None):
+        """Both descriptions into the pinned buffers (the previous replay has read them); returns their part of the shape key
+        (`padded_key`: the tables were padded by `pad_seq_tables`, which also made their key)."""
         sq = self._seq_buffers(max(b[0].size for b in built), max(b[1].size for b in built))
         k = self._turn % self.RING
         for i, (idx, cu, mx, tb) in enumerate(built):
@@ -201,15 +219,15 @@ class GraphedUpdate:
             sq['cu_host'][k][i].numpy()[:cu.size] = cu
             sq['idx_dev'][i][:idx.size].copy_(sq['idx_host'][k][i][:idx.size], non_blocking=True)      # stream-ordered, outside the graph
             sq['cu_dev'][i][:cu.size].copy_(sq['cu_host'][k][i][:cu.size], non_blocking=True)
-        self._seq_now = [(b[0].size, b[1].size, b[2], b[3]) for b in built]
-        return tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
+        self._seq_now = [(b[0].size, b[1].size, b[2], b[3], padded_key is not None) for b in built]
+        return padded_key if padded_key is not None else tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
 
     def packed_seqs(self):
         """Called by the trainer's `_batch_views` while this object drives the update: views of the static device tables (refreshed by
         `_prepare_seqs` before the replay)."""
         sq = self._seq
-        return [PackedSeqs.from_static(sq['idx_dev'][i][:n_idx], sq['cu_dev'][i][:n_cu], mx, tb)
-                for i, (n_idx, n_cu, mx, tb) in enumerate(self._seq_now)]
+        return [PackedSeqs.from_static(sq['idx_dev'][i][:n_idx], sq['cu_dev'][i][:n_cu], mx, tb, padded=padded)
+                for i, (n_idx, n_cu, mx, tb, padded) in enumerate(self._seq_now)]
 
     @staticmethod
     def refusal(alg):
@@ -278,15 +296,21 @@ class GraphedUpdate:
         alg, par = self.alg, self.alg.parameter
         pl = alg.replay_buffer.plan_trajs_device(par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj,
                                                  nest_stack_trajs=alg.allow_nest_stack, buckets=self.buckets == 'on')
-        if self.buckets == 'auto' and self._count_shape(pl):
-            pl = pad_plan(pl, alg.replay_buffer.max_traj_step)              # the plan that tipped the count is the first bucketed one
+        built = None
+        if self.buckets == 'auto':
+            if self._drop_base is not None and self.seq_buckets:            # the exact key of attention layers holds the table sizes too
+                built = self._build_seqs(pl)
+            if self._count_shape(pl, built):
+                pl = pad_plan(pl, alg.replay_buffer.max_traj_step)          # the plan that tipped the count is the first bucketed one
+                built = None
         alg.replay_buffer._mirror(self.device)        # transitions pushed since the last update reach the device ring HERE, outside the graph
         n = pl['seg'].shape[0]
         if n > self.PLAN_CAPACITY:
             raise RuntimeError(f'GraphedUpdate: {n} plan segments exceed the static plan buffer ({self.PLAN_CAPACITY})')
         # bucketed: `max_len` is the row length (it only sizes the gather grid)
         key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else (pl['nrow'], pl['longest'], pl['max_len'], n)
-        built = self._build_seqs(pl) if self._drop_base is not None else None
+        if self._drop_base is not None and built is None:
+            built = self._build_seqs(pl)
         # staging slot of this update: its copies of three updates ago have long run; the log handed out then is read out before its block is reused
         slot = self._slot = self._ring[self._turn % self.RING]
         if slot['handed'] is not None:
@@ -294,7 +318,10 @@ class GraphedUpdate:
             slot['handed'] = None
         if slot['used']:
             slot['evt'].synchronize()
-        if built is not None:
+        if built is not None and self.buckets == 'on':                      # reachable with `seq_buckets` only
+            padded, seq_key = pad_seq_tables(built, pl['nrow'], pl['longest'])
+            key = key + self._prepare_seqs(padded, seq_key)
+        elif built is not None:
             key = key + self._prepare_seqs(built)
         slot['plan'].numpy()[:n] = pl['seg']
         self._plan_dev[:n].copy_(slot['plan'][:n], non_blocking=True)        # stream-ordered: behind the previous update's gather
@@ -311,12 +338,13 @@ class GraphedUpdate:
         self._turn += 1
         return key + (bool(actor_due),)
 
-    def _count_shape(self, pl):
+    def _count_shape(self, pl, built=None):
         """'auto': True once, when this exact shape is one more than the graphs can hold (`max_graphs` over the launch sequences) - the
         workload is ragged, exact keys would leave most updates eager.  Drops what was recorded and counted for exact keys."""
-        if getattr(self.alg, '_needs_seq_table', False):                    # attention layers: no buckets (NO_SEQ_BUCKETS)
+        if getattr(self.alg, '_needs_seq_table', False) and not self.seq_buckets:      # attention layers: no buckets (NO_SEQ_BUCKETS)
             return False
-        self._shapes.add((pl['nrow'], pl['longest'], pl['max_len'], pl['seg'].shape[0]))
+        tables = () if built is None else tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
+        self._shapes.add((pl['nrow'], pl['longest'], pl['max_len'], pl['seg'].shape[0]) + tables)
         if len(self._shapes) <= max(1, self.max_graphs // self._sequences):
             return False
         self.buckets = 'on'

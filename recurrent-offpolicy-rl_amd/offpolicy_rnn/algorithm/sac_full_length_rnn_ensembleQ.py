@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from ..buffers.transition_buffer.nested_replay_memory import NestedMemoryArray as NestedTransitionMemoryArray
+from ..buffers.transition_buffer.shape_buckets import pad_seq_tables
 from ..hip import ops
 from ..models.contextual_model import ContextualModel
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
@@ -67,7 +68,7 @@ def _ensemble_subset(model, member_index):
 
 
 NO_SEQ_BUCKETS = 'shape buckets do not cover layers that need sequence tables (cgpt): the token and cu_seqlens tables vary with the batch ' \
-                 'and are not bucketed'
+                 'and are bucketed only with seq_buckets (RESEL_GRAPH_SEQ_BUCKETS=1)'
 
 
 class DeferredLog(dict):
@@ -161,8 +162,10 @@ class SACFullLengthRNNEnsembleQ(SAC):
         self.grad_sync = GradSync()
         self._graph = None                             # set while a captured update is being recorded / replayed (graphed_update.py)
         # eager updates pad their batch into its shape bucket (shape_buckets.py; tests, tools).  Device replay ring only, and not with
-        # attention layers (their sequence tables are not bucketed): `_train_one_batch` raises otherwise
+        # attention layers unless `seq_buckets` is set as well (then `_batch_views` pads their sequence tables into buckets,
+        # shape_buckets.pad_seq_tables, and the decoder takes its padded path): `_train_one_batch` raises otherwise
         self.shape_buckets = False
+        self.seq_buckets = False
         self._subset_rng = None                        # REDQ subset stream: None = numpy's global stream (see _subset_stream)
         self._pinned = PinnedRing(torch.float32)       # staging blocks of the host-built batch (one event per block)
         self._needs_seq_table = any(lid.startswith('cgpt') for net in (self.values[0].uni_network, self.values[0].embedding_network,
@@ -280,6 +283,12 @@ class SACFullLengthRNNEnsembleQ(SAC):
             am[:, :table.shape[1]] = table
             tam = np.concatenate((am[:, 1:], np.zeros((rows, 1), dtype=np.int32)), axis=1)
             # built on the host (the table is host data anyway): token indices + cu_seqlens for the var-len attention kernel
+            if self.shape_buckets and self.seq_buckets:
+                built, _ = pad_seq_tables([PackedSeqs.build_host(a, T) for a in (am, tam)], rows, T)
+                out['attention_mask'], out['target_attention_mask'] = [
+                    PackedSeqs.from_static(torch.from_numpy(idx).to(self.device), torch.from_numpy(cu).to(self.device), mx, tb, padded=True)
+                    for idx, cu, mx, tb in built]
+                return out
             out['attention_mask'], out['target_attention_mask'] = PackedSeqs(am, T, self.device), PackedSeqs(tam, T, self.device)
         return out
 
@@ -497,7 +506,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
             elif getattr(self, 'device_replay', False) and self.device.type == 'cuda' \
                     and self.replay_buffer.device_supported(randomize_mask=par.randomize_mask):
                 # device-resident ring: the host decides WHICH trajectories go where, the batch array is built on the GPU
-                if self.shape_buckets and self._needs_seq_table:
+                if self.shape_buckets and self._needs_seq_table and not self.seq_buckets:
                     raise RuntimeError('shape_buckets: ' + NO_SEQ_BUCKETS)
                 dev, batch_size, table = self.replay_buffer.sample_trajs_device(
                     self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack,

@@ -6,11 +6,20 @@ shapes cover every batch.  The extra slots are what the sampler writes behind a 
 plan entries carry row -1 and are dropped by the gather kernel, the losses divide by the sum of the mask: the padded update computes
 what the exact one does, at up to 1.5x the tokens in the worst case.
 
+Attention layers (cgpt) also take two SEQUENCE tables per batch - the packed token indices and cu_seqlens of the batch and of its
+one-slot shift - whose sizes vary with the draw even inside one batch bucket.  `pad_seq_tables` moves both into ONE more bucket
+(token count up the ladder, number of sequences up to a power of two) that is a function of what the batch bucket already bounds,
+so in practice the graph key gains no value of its own: the extra sequences are empty (cu_seqlens repeats its last value - which
+is the real token count, readable by the kernels on the device), the extra token slots are never read.
+
 Host arithmetic only: no torch in here (the planner runs while the previous update is still on the GPU)."""
 import numpy as np
 
 MIN_ROW_LEN = 32                                      # shorter rows are not worth a shape of their own
 MIN_NSEG = 16
+MIN_TOKENS = 256                                      # token tables shorter than this are not worth a shape of their own
+MIN_SEQS = 16
+ATTN_BLOCK = 128                                      # tokens per attention workgroup: the longest-sequence bound is a multiple of it
 
 
 def ladder(x):
@@ -47,3 +56,30 @@ def pad_plan(pl, row_cap):
     table_b[:table.shape[0]] = table
     table_b[table.shape[0]:, 0] = 1
     return dict(pl, seg=seg_b, table=table_b, nrow=rows, longest=row_len, max_len=row_len, nrow_real=pl['nrow'], longest_real=pl['longest'])
+
+
+def pad_seq_tables(built, rows, row_len):
+    """The two sequence descriptions of a bucketed batch (`GraphedUpdate._build_seqs`: [(idx, cu, max_seqlen, table)] for the batch and
+    its one-slot shift) padded into one shared bucket; `rows`, `row_len`: the bucketed batch shape.
+      tokens     Tb = min(max(ladder(largest token count), MIN_TOKENS), rows * row_len) - idx padded to Tb (the tail is in range and
+                 never read: the kernels take the real count from cu[Sb]);
+      sequences  Sb = max(MIN_SEQS, next power of two of the larger sequence count) - cu padded to Sb + 1 by REPEATING its last
+                 value (sequences of length zero; cu[Sb] stays the real token count);
+      longest    ATTN_BLOCK * nqb with nqb = ceil(row_len / ATTN_BLOCK): no sequence is longer than a row; it only sizes the
+                 attention grids, the kernels read the real lengths from cu.
+    Returns (padded [(idx, cu, longest, table)], (Tb, Sb + 1, nqb)) - the second is the tables' part of the graph key."""
+    cap = int(rows) * int(row_len)
+    n_tok = max(int(b[0].size) for b in built)
+    n_seq = max(int(b[1].size) - 1 for b in built)
+    assert n_tok <= cap, (n_tok, rows, row_len)
+    tb = min(max(ladder(n_tok), MIN_TOKENS), cap)
+    sb = max(MIN_SEQS, 1 << max(n_seq - 1, 0).bit_length())
+    nqb = (int(row_len) + ATTN_BLOCK - 1) // ATTN_BLOCK
+    out = []
+    for idx, cu, _, table in built:
+        idx_b = np.zeros(tb, dtype=np.int64)
+        idx_b[:idx.size] = idx
+        cu_b = np.full(sb + 1, cu[-1], dtype=np.int32)
+        cu_b[:cu.size] = cu
+        out.append((idx_b, cu_b, ATTN_BLOCK * nqb, table))
+    return out, (tb, sb + 1, nqb)

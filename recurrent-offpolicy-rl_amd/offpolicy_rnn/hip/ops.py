@@ -760,7 +760,7 @@ def gru_seq_multi(jobs):
 # ---------------------------------------------------------------------------------------------- attention (cgpt)
 class AttnVarlenFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset, padded=False):
         _need_cuda('attn_varlen', qkv, cu_seqlens)
         assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.shape[1] == 3
         qkv = qkv.contiguous()
@@ -771,10 +771,12 @@ class AttnVarlenFn(torch.autograd.Function):
         out = torch.empty(T, H, hd, dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         ws = _ws(lib().resel_attn_varlen_fwd_workspace_bytes(S, int(max_seqlen)), qkv.device)
-        check(lib().resel_attn_varlen_fwd(_p(qkv), _p(cu), _p(slopes), _p(out), _p(lse), _p(ws), T, S, H, hd, int(max_seqlen), float(scale),
-                                          float(p_drop), int(seed), int(offset), _stream()), 'attn_varlen_fwd')
+        fwd = lib().resel_attn_varlen_fwd_padded if padded else lib().resel_attn_varlen_fwd
+        check(fwd(_p(qkv), _p(cu), _p(slopes), _p(out), _p(lse), _p(ws), T, S, H, hd, int(max_seqlen), float(scale),
+                  float(p_drop), int(seed), int(offset), _stream()), 'attn_varlen_fwd')
         ctx.save_for_backward(qkv, cu, slopes, out, lse)
         ctx.max_seqlen, ctx.scale, ctx.drop = int(max_seqlen), float(scale), (float(p_drop), int(seed), int(offset))
+        ctx.padded = bool(padded)
         return out
 
     @staticmethod
@@ -784,9 +786,10 @@ class AttnVarlenFn(torch.autograd.Function):
         dout = dout.to(torch.bfloat16).contiguous()
         dqkv = torch.empty_like(qkv)
         ws = _ws(lib().resel_attn_varlen_bwd_workspace_bytes(T, cu.numel() - 1, H, hd, ctx.max_seqlen), qkv.device)
-        check(lib().resel_attn_varlen_bwd(_p(qkv), _p(cu), _p(slopes), _p(out), _p(lse), _p(dout), _p(dqkv), _p(ws), T, cu.numel() - 1, H, hd,
-                                          ctx.max_seqlen, ctx.scale, *ctx.drop, _stream()), 'attn_varlen_bwd')
-        return dqkv, None, None, None, None, None, None, None
+        bwd = lib().resel_attn_varlen_bwd_padded if ctx.padded else lib().resel_attn_varlen_bwd
+        check(bwd(_p(qkv), _p(cu), _p(slopes), _p(out), _p(lse), _p(dout), _p(dqkv), _p(ws), T, cu.numel() - 1, H, hd,
+                  ctx.max_seqlen, ctx.scale, *ctx.drop, _stream()), 'attn_varlen_bwd')
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 _MASK64 = (1 << 64) - 1
@@ -823,11 +826,75 @@ def dropout_counter(device):
     return gen.initial_seed() & _MASK64, off & _MASK64
 
 
-def attn_varlen(qkv, cu_seqlens, max_seqlen, slopes=None, scale=None, p_drop=0.0, seed=0, offset=0):
+def attn_varlen(qkv, cu_seqlens, max_seqlen, slopes=None, scale=None, p_drop=0.0, seed=0, offset=0, padded=False):
     """qkv [T, 3, H, hd] bf16 packed tokens -> out [T, H, hd] bf16: causal softmax(q k^T * scale - slope_h (i - j)) v per sequence.
-    p_drop > 0: dropout on the attention probabilities with the keep mask keyed on (seed, offset) (see resel_hip.h)."""
+    p_drop > 0: dropout on the attention probabilities with the keep mask keyed on (seed, offset) (see resel_hip.h).
+    `padded`: the tables of a shape bucket - T may exceed cu_seqlens[-1] and sequences may be empty; the same kernels, then a pass
+    that writes the token tail of out / lse (backward: dqkv) as zero (`resel_attn_varlen_fwd_padded`)."""
     scale = qkv.shape[-1] ** -0.5 if scale is None else scale
-    return AttnVarlenFn.apply(qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset)
+    return AttnVarlenFn.apply(qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset, padded)
+
+
+# ------------------------------------------------------------------ token packing with a device-side count (padded sequence tables)
+def _pack_rows(src, idx, n_dev):
+    T, C = idx.numel(), src.shape[1]
+    out = torch.empty(T, C, dtype=torch.float32, device=src.device)
+    check(lib().resel_pack_rows(_p(src), src.stride(0), _p(idx), _p(n_dev), _p(out), C, T, C, _stream()), 'pack_rows')
+    return out
+
+
+def _unpack_rows(packed, idx, n_dev, M):
+    T, C = packed.shape
+    dst = torch.empty(M, C, dtype=torch.float32, device=packed.device)
+    check(lib().resel_unpack_rows(_p(packed), packed.stride(0), _p(idx), _p(n_dev), _p(dst), C, M, T, C, _stream()), 'unpack_rows')
+    return dst
+
+
+def _rows_arg(name, x, idx, n_dev):
+    _need_cuda(name, x, idx, n_dev)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] % 4 == 0, (name, x.dtype, tuple(x.shape))
+    assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and n_dev.dtype == torch.int32 and n_dev.numel() >= 1
+    return x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 else x.contiguous()
+
+
+class PackTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flat, idx, n_dev):
+        flat = _rows_arg('pack_tokens', flat, idx, n_dev)
+        ctx.save_for_backward(idx, n_dev)
+        ctx.rows = flat.shape[0]
+        return _pack_rows(flat, idx, n_dev)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, n_dev = ctx.saved_tensors
+        return _unpack_rows(_rows_arg('pack_tokens backward', g, idx, n_dev), idx, n_dev, ctx.rows), None, None
+
+
+class UnpackTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, packed, idx, n_dev, rows):
+        packed = _rows_arg('unpack_tokens', packed, idx, n_dev)
+        assert packed.shape[0] == idx.numel(), (tuple(packed.shape), idx.numel())
+        ctx.save_for_backward(idx, n_dev)
+        return _unpack_rows(packed, idx, n_dev, int(rows))
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, n_dev = ctx.saved_tensors
+        return _pack_rows(_rows_arg('unpack_tokens backward', g, idx, n_dev), idx, n_dev), None, None, None
+
+
+def pack_tokens(flat, idx, n_dev):
+    """flat [M, C] fp32, idx int64 [T] (a padded token table), n_dev int32 device word (its first element: the real token count, e.g.
+    `cu_seqlens[-1:]`) -> [T, C]: row t is flat[idx[t]] for t < n, zero behind.  Backward: `unpack_tokens` of the gradient."""
+    return PackTokensFn.apply(flat, idx, n_dev)
+
+
+def unpack_tokens(packed, idx, n_dev, rows):
+    """packed [T, C] fp32 -> [rows, C]: row idx[t] is packed[t] for t < n, every other row zero (all rows written by one kernel; idx
+    strictly increasing over its real prefix).  Backward: `pack_tokens` of the gradient - a padded token gets a zero gradient."""
+    return UnpackTokensFn.apply(packed, idx, n_dev, rows)
 
 
 class CounterDropoutFn(torch.autograd.Function):
