@@ -7,13 +7,11 @@
 // reference's bf16-autocast projections see them (`rnd` bits), same epilogues as resel_gemm_f32x (bias, ELU, softplus, accumulate),
 // same magnitude publication.  Long reductions with few output tiles (narrow weight gradients over all tokens) are cut along K over
 // grid.z; the partial tiles are summed in a fixed order by a second kernel (bitwise reproducible, no atomics).
-#include "resel_common.h"
+#include "gemm_call.h"
 #include <algorithm>
 
 namespace {
 using namespace resel;
-
-constexpr int RND_A = 1, RND_B = 2, RND_OUT = 4, OUT_BF16 = 8, A_BF16 = 16;
 
 struct AnyParams {
     const void* A;
@@ -199,40 +197,35 @@ size_t gemm_any_workspace_bytes(int M, int N, int K, int batch) {
 }
 
 // rows form: M <= 8, both operands K-contiguous with 16-byte (bf16 A: 8-byte) aligned rows, no accumulate
-bool gemm_any_rows_ok(const void* A, int64_t lda, int64_t strideA, int a_kcontig, int a_bf16, const float* B, int64_t ldb, int64_t strideB,
-                      int b_kcontig, int M, int K, int act) {
+bool gemm_any_rows_ok(const GemmCall& c, bool a_bf16) {
     const uintptr_t am = a_bf16 ? 7u : 15u;
-    return M <= 8 && a_kcontig && b_kcontig && act != 2 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && strideA % 4 == 0 && strideB % 4 == 0 &&
-           !(reinterpret_cast<uintptr_t>(A) & am) && !(reinterpret_cast<uintptr_t>(B) & 15u);
+    return c.M <= 8 && c.a_kcontig && c.b_kcontig && c.act != 2 && c.K % 4 == 0 && c.lda % 4 == 0 && c.ldb % 4 == 0 && c.strideA % 4 == 0 &&
+           c.strideB % 4 == 0 && !(reinterpret_cast<uintptr_t>(c.A) & am) && !(reinterpret_cast<uintptr_t>(c.B) & 15u);
 }
 
-// rnd: RND_A | RND_B | RND_OUT | OUT_BF16 | A_BF16 (bf16 A: rows form only)
-int gemm_any_launch(const void* A, int64_t lda, int64_t strideA, int a_kcontig, const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
-                    const float* bias, int64_t strideBias, int act, void* C, int64_t ldc, int64_t strideC, void* workspace,
-                    int M, int N, int K, int batch, int rnd, unsigned long long* amax_c, unsigned amax_epoch, hipStream_t s) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || act < 0 || act > 3 || lda <= 0 || ldb <= 0 || ldc <= 0) return RESEL_EINVAL;
-    if ((rnd & OUT_BF16) && act == 2) return RESEL_EINVAL;
-    const bool rows = gemm_any_rows_ok(A, lda, strideA, a_kcontig, rnd & A_BF16, B, ldb, strideB, b_kcontig, M, K, act);
+int gemm_any_launch(const GemmCall& c, int rnd) {
+    if ((rnd & OUT_BF16) && c.act == 2) return RESEL_EINVAL;
+    const bool rows = gemm_any_rows_ok(c, rnd & A_BF16);
     if ((rnd & A_BF16) && !rows) return RESEL_EINVAL;
-    AnyParams p{A, B, bias, C, a_kcontig ? lda : 1, a_kcontig ? 1 : lda, b_kcontig ? ldb : 1, b_kcontig ? 1 : ldb, ldc, strideA, strideB, strideC,
-                strideBias, M, N, K, act, K, 1, nullptr, AmaxOut{amax_c, amax_epoch}};
+    AnyParams p{c.A, c.B, c.bias, c.C, c.a_kcontig ? c.lda : 1, c.a_kcontig ? 1 : c.lda, c.b_kcontig ? c.ldb : 1, c.b_kcontig ? 1 : c.ldb, c.ldc,
+                c.strideA, c.strideB, c.strideC, c.strideBias, c.M, c.N, c.K, c.act, c.K, 1, nullptr, AmaxOut{c.amax_c, c.amax_epoch}};
     if (!rows) {
-        p.nz = pick_nz(M, N, K, batch);
+        p.nz = pick_nz(c.M, c.N, c.K, c.batch);
         if (p.nz > 1) {
-            if (!workspace) return RESEL_EINVAL;
-            p.kchunk = ((K + p.nz - 1) / p.nz + 15) / 16 * 16;
-            p.nz = (K + p.kchunk - 1) / p.kchunk;
-            p.part = (float*)workspace;
+            if (!c.workspace) return RESEL_EINVAL;
+            p.kchunk = ((c.K + p.nz - 1) / p.nz + 15) / 16 * 16;
+            p.nz = (c.K + p.kchunk - 1) / p.kchunk;
+            p.part = (float*)c.workspace;
         }
     }
     switch (rnd & 31) {
-        case 0: return launch_any<0>(p, batch, rows, s);
-        case RND_A | RND_B: return launch_any<RND_A | RND_B>(p, batch, rows, s);
-        case RND_A | RND_B | RND_OUT: return launch_any<RND_A | RND_B | RND_OUT>(p, batch, rows, s);
-        case RND_A | RND_B | OUT_BF16: return launch_any<RND_A | RND_B | OUT_BF16>(p, batch, rows, s);
-        case RND_B | OUT_BF16 | A_BF16: return launch_any<RND_B | OUT_BF16 | A_BF16>(p, batch, rows, s);
-        case RND_B | A_BF16: return launch_any<RND_B | A_BF16>(p, batch, rows, s);
-        case RND_B | RND_OUT | A_BF16: return launch_any<RND_B | RND_OUT | A_BF16>(p, batch, rows, s);
+        case 0: return launch_any<0>(p, c.batch, rows, c.s);
+        case RND_A | RND_B: return launch_any<RND_A | RND_B>(p, c.batch, rows, c.s);
+        case RND_A | RND_B | RND_OUT: return launch_any<RND_A | RND_B | RND_OUT>(p, c.batch, rows, c.s);
+        case RND_A | RND_B | OUT_BF16: return launch_any<RND_A | RND_B | OUT_BF16>(p, c.batch, rows, c.s);
+        case RND_B | OUT_BF16 | A_BF16: return launch_any<RND_B | OUT_BF16 | A_BF16>(p, c.batch, rows, c.s);
+        case RND_B | A_BF16: return launch_any<RND_B | A_BF16>(p, c.batch, rows, c.s);
+        case RND_B | RND_OUT | A_BF16: return launch_any<RND_B | RND_OUT | A_BF16>(p, c.batch, rows, c.s);
         default: return RESEL_EINVAL;
     }
 }

@@ -14,7 +14,7 @@
 // Structure = csrc/gemm_bf3.hip with ONE plane: 256 x 128 block tile, 8 waves, K step 32, the same swizzled [row][32 k] bf16 LDS
 // image, two stages, one barrier per step, persistent blocks, K slices of the tail round / of weight gradients summed by a fix-up
 // kernel in a fixed order.  With 8 matrix instructions per wave and K step the kernel runs at the rate its operands arrive.
-#include "resel_common.h"
+#include "gemm_call.h"
 #include <algorithm>
 
 namespace {
@@ -325,10 +325,7 @@ inline Plan make_plan(int M, int N, int K) {
 
 template <typename TA, typename TB>
 void launch_layout(const Params& p, dim3 grid, int akc, int bkc, hipStream_t s) {
-    if (akc && bkc) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, true>), grid, dim3(NTH), 0, s, p);
-    else if (akc) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, false>), grid, dim3(NTH), 0, s, p);
-    else if (bkc) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, false, true>), grid, dim3(NTH), 0, s, p);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, false, false>), grid, dim3(NTH), 0, s, p);
+    with_layout(akc, bkc, [&](auto a, auto b) { hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, a.value, b.value>), grid, dim3(NTH), 0, s, p); });
 }
 
 }  // namespace
@@ -343,19 +340,15 @@ extern "C" int resel_gemm_bf16(const void* A, int64_t lda, int a_kcontig, int a_
                                const float* bias, void* C, int64_t ldc, int c_bf16, void* workspace, int M, int N, int K,
                                resel_stream_t stream) {
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc <= 0) return RESEL_EINVAL;
-    // a thread fetches four consecutive elements of an operand's contiguous axis: extents, leading dimensions and base addresses
-    // must keep those 16-byte (fp32) / 8-byte (bf16) pieces aligned.  Shapes that do not, and the M <= 8 rows of a decode step against
-    // a whole weight matrix, go to gemm_any.hip with the same rounding points (operands and bias rounded to bf16, fp32 accumulation,
+    // Shapes the matrix cores cannot read (gemm_mfma_readable; 8-byte pieces of a bf16 operand) and the M <= 8 rows of a decode step against
+    // a whole weight matrix go to gemm_any.hip with the same rounding points (operands and bias rounded to bf16, fp32 accumulation,
     // result rounded as `c_bf16` says) - fp32 operands only there, except a bf16 A in the rows form (the attention output of a decode step)
-    const bool mfma_ok = !((a_kcontig ? K : M) % 4 || (b_kcontig ? K : N) % 4 || lda % 4 || ldb % 4 ||
-                           (reinterpret_cast<uintptr_t>(A) & (a_bf16 ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(B) & (b_bf16 ? 7u : 15u)) ||
-                           lda >= (int64_t)1 << 22 || ldb >= (int64_t)1 << 22);
-    const bool rows = !b_bf16 && gemm_any_rows_ok(A, lda, 0, a_kcontig, a_bf16, (const float*)B, ldb, 0, b_kcontig, M, K, 0);
-    if (!mfma_ok || rows) {
+    const GemmCall c{A, lda, 0, a_kcontig, (const float*)B, ldb, 0, b_kcontig, bias, 0, 0, C, ldc, 0, workspace, M, N, K, 1,
+                     nullptr, nullptr, nullptr, 0u, (hipStream_t)stream};
+    const bool rows = !b_bf16 && gemm_any_rows_ok(c, a_bf16);
+    if (!gemm_mfma_readable(c, a_bf16, b_bf16) || rows) {
         if (b_bf16 || (a_bf16 && !rows)) return RESEL_EINVAL;
-        const int rnd = (a_bf16 ? 16 : 1) | 2 | (c_bf16 == 1 ? 8 : (c_bf16 == 2 ? 4 : 0));
-        return gemm_any_launch(A, lda, 0, a_kcontig, (const float*)B, ldb, 0, b_kcontig, bias, 0, 0, C, ldc, 0, workspace, M, N, K, 1, rnd, nullptr, 0u,
-                               (hipStream_t)stream);
+        return gemm_any_launch(c, (a_bf16 ? A_BF16 : RND_A) | RND_B | (c_bf16 == 1 ? OUT_BF16 : (c_bf16 == 2 ? RND_OUT : 0)));
     }
     const Plan pl = make_plan(M, N, K);
     if (pl.nsplit && (!workspace || !aligned16(workspace))) return RESEL_EINVAL;

@@ -27,7 +27,7 @@
 // walk, the slice plan and the fix-up kernel are gemm_splitk.h, shared with gemm_f32.hip.
 // SPLIT of gemm_bf3_kernel is 2, 3 or 6; gemm_ws_kernel is mode 2 only (EPI: 0 the plain epilogues, 4 / 5 the fused ones).
 #include "gemm_splitk.h"
-#include <type_traits>
+#include "gemm_call.h"
 
 namespace {
 using namespace resel;
@@ -1334,53 +1334,43 @@ size_t gemm_bf3_workspace_bytes(int M, int N, int K, int batch) {
     return (size_t)pl.nsplit * pl.nsl * TILE * sizeof(float);
 }
 
-// split in {2, 3, 6}, K >= 32; argument checks are the caller's (resel_gemm_f32)
-// the fused epilogues (act 4 / 5) exist on the producer / consumer edition, for whole-K items: mode 2, K a multiple of 32, M > 128
-bool gemm_bf3_fused_ok(int M, int N, int K, int64_t lda, int64_t ldb) {
-    return M > 128 && N >= 4 && K >= BK && K % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
-}
+// whole K steps, also per K slice: what the third edition's (producer / consumer waves, mode 2) items must be
+inline bool whole_k_steps(int K, int kslice) { return K % BK == 0 && kslice % BK == 0; }
 
-int gemm_bf3_launch(const float* A, int64_t lda, int64_t strideA, int a_kcontig, const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
-                    const float* bias, int64_t strideBias, int act, float* C, int64_t ldc, int64_t strideC, void* workspace,
-                    int M, int N, int K, int batch, int split, hipStream_t s, const float* amaxA, const float* amaxB,
-                    unsigned long long* amax_c, unsigned amax_epoch, const float* aux, int64_t ldaux, int64_t strideAux, float* red, int redrows) {
-    if (split == 2 && (!amaxA || !amaxB)) return RESEL_EINVAL;
-    Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
+// the fused epilogues (act 4 / 5) exist on the third edition, for whole-K items (one slice = K): mode 2, M > 128
+bool gemm_bf3_fused_ok(int M, int N, int K) { return M > 128 && N >= 4 && K >= BK && whole_k_steps(K, K); }
+
+int gemm_bf3_launch(const GemmCall& c, int split, const GemmFused& fused) {
+    if (split == 2 && (!c.amax_a || !c.amax_b)) return RESEL_EINVAL;
+    const int M = c.M, N = c.N, K = c.K, act = c.act;
+    Plan pl = make_plan<BM, BN, GRID>(M, N, K, c.batch);
     if (act >= 4) {                                  // every tile whole: the epilogue reductions are written per (tile, wave), no K slices
-        if (split != 2 || !gemm_bf3_fused_ok(M, N, K, lda, ldb) || !aux) return RESEL_EINVAL;
+        if (split != 2 || !gemm_bf3_fused_ok(M, N, K) || !fused.aux) return RESEL_EINVAL;
         if (act == 4 && (M % BM || N % BN)) return RESEL_EINVAL;          // the act 4 epilogue has no edge form (resel_gemm_f32_dact splits the rows)
-        const long nbt = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch;
+        if (!c.a_kcontig) return RESEL_EINVAL;                            // the layouts the trainer uses: A [rows][K]; B either way
+        const long nbt = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN) * c.batch;
         pl = Plan{(int)nbt, 0, 1, (K + BK - 1) / BK * BK};
     }
-    if (pl.nsplit && (!workspace || !aligned16(workspace))) return RESEL_EINVAL;
-    Params p{A, B, bias, C, (float*)workspace, lda, ldb, ldc, strideA, strideB, strideC, strideBias, M, N, K, act,
-             (M + BM - 1) / BM, (N + BN - 1) / BN, pl.nfull, pl.nsplit, pl.nsl, pl.kslice, amaxA, amaxB, AmaxOut{amax_c, amax_epoch}, g_nt,
-             aux, ldaux, strideAux, red, redrows};
-    const int64_t total = (int64_t)pl.nfull + (int64_t)pl.nsplit * pl.nsl;
-    dim3 grid((unsigned)std::min<int64_t>(total, GRID));
-    int rc;
-#define BF3_LAUNCH(SP) \
-    do { if (a_kcontig && b_kcontig) rc = launch_one<true, true, SP>(p, grid, s); \
-         else if (a_kcontig) rc = launch_one<true, false, SP>(p, grid, s); \
-         else if (b_kcontig) rc = launch_one<false, true, SP>(p, grid, s); \
-         else rc = launch_one<false, false, SP>(p, grid, s); } while (0)
-    // third edition: mode 2, whole K steps (also per K slice); row strides within the 24-bit multiply of the piece offsets
-    const bool ws = split == 2 && K % BK == 0 && pl.kslice % BK == 0 && lda < (1 << 22) && ldb < (1 << 22);
-    if (act >= 4) {                                   // fused epilogues: the layouts the trainer uses - A [rows][K]; B either way
-        if (!a_kcontig) return RESEL_EINVAL;
-        if (act == 4) rc = b_kcontig ? launch_ws<true, true, 4>(p, grid, s) : launch_ws<true, false, 4>(p, grid, s);
-        else rc = b_kcontig ? launch_ws<true, true, 5>(p, grid, s) : launch_ws<true, false, 5>(p, grid, s);
-    } else if (ws) {
-        if (a_kcontig && b_kcontig) rc = launch_ws<true, true>(p, grid, s);
-        else if (a_kcontig) rc = launch_ws<true, false>(p, grid, s);
-        else if (b_kcontig) rc = launch_ws<false, true>(p, grid, s);
-        else rc = launch_ws<false, false>(p, grid, s);
-    } else if (split == 3) BF3_LAUNCH(3); else if (split == 2) BF3_LAUNCH(2); else BF3_LAUNCH(6);
-#undef BF3_LAUNCH
+    if (pl.nsplit && (!c.workspace || !aligned16(c.workspace))) return RESEL_EINVAL;
+    Params p{(const float*)c.A, c.B, c.bias, (float*)c.C, (float*)c.workspace, c.lda, c.ldb, c.ldc, c.strideA, c.strideB, c.strideC, c.strideBias,
+             M, N, K, act, (M + BM - 1) / BM, (N + BN - 1) / BN, pl.nfull, pl.nsplit, pl.nsl, pl.kslice, c.amax_a, c.amax_b,
+             AmaxOut{c.amax_c, c.amax_epoch}, g_nt, fused.aux, fused.ldaux, fused.strideAux, fused.red, fused.redrows};
+    dim3 grid((unsigned)std::min<int64_t>((int64_t)pl.nfull + (int64_t)pl.nsplit * pl.nsl, GRID));
+    const bool third = split == 2 && whole_k_steps(K, pl.kslice);
+    const int rc = with_layout(c.a_kcontig, c.b_kcontig, [&](auto akc, auto bkc) {
+        constexpr bool AKC = akc.value, BKC = bkc.value;
+        if constexpr (AKC) {
+            if (act >= 4) return act == 4 ? launch_ws<true, BKC, 4>(p, grid, c.s) : launch_ws<true, BKC, 5>(p, grid, c.s);
+        }
+        if (third) return launch_ws<AKC, BKC>(p, grid, c.s);
+        if (split == 3) return launch_one<AKC, BKC, 3>(p, grid, c.s);
+        if (split == 2) return launch_one<AKC, BKC, 2>(p, grid, c.s);
+        return launch_one<AKC, BKC, 6>(p, grid, c.s);
+    });
     if (rc != RESEL_OK) return rc;
-    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
+    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, c.s, p);
 #ifdef BF3_AB_FIXUP2                    // ablation (right results): every fix-up launched TWICE - what the 86 fix-up launches of an update cost, measured
-    if (pl.nsplit && act != 2) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);   // with the data left intact
+    if (pl.nsplit && act != 2) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, Params>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, c.s, p);   // with the data left intact
 #endif                                  // (skipping the fix-up instead leaves garbage tiles: the degenerate data lowers the chip's power draw, its clock
                                         //  rises and EVERY kernel of the update runs 5-13 % faster - profiles/r06_gemm.md)
     return launch_status();

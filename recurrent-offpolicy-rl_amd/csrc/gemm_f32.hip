@@ -36,16 +36,7 @@
 // Without that the last round cost a full tile time at 4 % occupancy (1044 tiles on 512 slots: 68 % efficiency).
 // Tile ids are XCD-aware: the n-tiles of one m-tile share an L2.
 #include "gemm_splitk.h"
-
-namespace resel {                      // gemm_bf3.hip: the split modes with the operands split once per block (second edition)
-size_t gemm_bf3_workspace_bytes(int M, int N, int K, int batch);
-int gemm_bf3_launch(const float* A, int64_t lda, int64_t strideA, int a_kcontig, const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
-                    const float* bias, int64_t strideBias, int act, float* C, int64_t ldc, int64_t strideC, void* workspace,
-                    int M, int N, int K, int batch, int split, hipStream_t s, const float* amaxA, const float* amaxB,
-                    unsigned long long* amax_c, unsigned amax_epoch, const float* aux = nullptr, int64_t ldaux = 0, int64_t strideAux = 0,
-                    float* red = nullptr, int redrows = 0);
-bool gemm_bf3_fused_ok(int M, int N, int K, int64_t lda, int64_t ldb);
-}
+#include "gemm_call.h"
 
 namespace {
 using namespace resel;
@@ -61,7 +52,7 @@ struct GemmParams {
     float *C, *slab;
     int64_t lda, ldb, ldc, sA, sB, sC, sBias;    // leading dimensions (floats) and per-batch strides
     int M, N, K;
-    int act;                                      // 0 none, 1 ELU, 2 C += product
+    int act;                                      // 0 none, 1 ELU, 2 C += product, 3 softplus
     int mt, nt;                                   // tiles along m and n
     int nfull;                                    // items [0, nfull): whole tiles; then nsplit tiles x nsl K slices of kslice
     int nsplit, nsl, kslice;
@@ -525,6 +516,56 @@ extern "C" size_t resel_gemm_f32_workspace_bytes(int M, int N, int K, int batch)
                     gemm_any_workspace_bytes(M, N, K, batch));
 }
 
+namespace {
+// what every entry checks first: operands, extents, leading dimensions, the alignment of the output's magnitude handle
+bool call_valid(const GemmCall& c) {
+    return c.A && c.B && c.C && c.M > 0 && c.N > 0 && c.K > 0 && c.batch > 0 && c.lda > 0 && c.ldb > 0 && c.ldc > 0 && !(reinterpret_cast<uintptr_t>(c.amax_c) & 7u);
+}
+// Which kernel family runs a product, and in which product mode.  The one place that decides (hip/ops.py `_mode2_shape` mirrors the
+// two shape rules only to spare a pre-pass; gemm_bf3_launch picks between its second and third edition by `whole_k_steps`).
+enum class Family { invalid, rows, tiles, first, second };        // gemm_any.hip: rows form / generic tiles; 128 x 128 tiles (here); gemm_bf3.hip
+struct Route { Family family; int split; };
+Route gemm_route(const GemmCall& c, int split) {
+    if ((split != 0 && split != 2 && split != 3 && split != 6) || (split == 2 && (!c.amax_a || !c.amax_b))) return {Family::invalid, split};
+    if (split == 2 && c.M <= 128) split = 6;       // narrow shapes stay on the first edition's fp32-accurate bf16 split
+    if (c.K < BK) split = 0;                       // the split kernels' scheduled loads assume one whole K step per item
+    // Everything the matrix cores cannot read - the 6-wide heads and their gradients, rank-2 projections, odd action counts - and the
+    // M <= 8 rows of a rollout step against a whole weight matrix go to gemm_any.hip (exact fp32 FMAs, same epilogues, same magnitude
+    // publication): no shape is refused, none is left to a vendor library.
+    if (!gemm_mfma_readable(c)) return {Family::tiles, split};
+    if (gemm_any_rows_ok(c)) return {Family::rows, split};
+    // second edition (256 x 128 tiles) unless half of its tile rows would be padding: M <= 128 (narrow weight gradients) runs
+    // 1.2-1.4x faster on the first edition's 128 x 128 tiles (66 752-token weight gradients [128, 256]: 48 vs 59 us, [80, 512]: 67 vs 95)
+    if (split != 0 && c.M > 128) return {Family::second, split};
+    return {Family::first, split == 3 ? 6 : split};               // the two-plane mode exists on the second-edition kernel only
+}
+// first edition: split 0 (fp32 matrix instruction) or 6
+int gemm_first_launch(const GemmCall& c, int split) {
+    const Plan pl = make_plan<BM, BN, GRID>(c.M, c.N, c.K, c.batch);
+    if (pl.nsplit && (!c.workspace || !aligned16(c.workspace))) return RESEL_EINVAL;
+    GemmParams p{(const float*)c.A, c.B, c.bias, (float*)c.C, (float*)c.workspace, c.lda, c.ldb, c.ldc, c.strideA, c.strideB, c.strideC, c.strideBias,
+                 c.M, c.N, c.K, c.act, (c.M + BM - 1) / BM, (c.N + BN - 1) / BN, pl.nfull, pl.nsplit, pl.nsl, pl.kslice, AmaxOut{c.amax_c, c.amax_epoch}};
+    dim3 grid((unsigned)std::min<int64_t>((int64_t)pl.nfull + (int64_t)pl.nsplit * pl.nsl, GRID));
+    with_layout(c.a_kcontig, c.b_kcontig, [&](auto akc, auto bkc) {
+        if (split == 6) launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<akc.value, bkc.value, 6>, grid, dim3(256), 0, c.s, p);
+        else launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<akc.value, bkc.value, 0>, grid, dim3(256), 0, c.s, p);
+    });
+    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, GemmParams>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, c.s, p);
+    return launch_status();
+}
+// validate, route, launch: resel_gemm_f32x, and the tail rows of resel_gemm_f32_dact
+int gemm_run(const GemmCall& c, int split) {
+    if (!call_valid(c) || c.act < 0 || c.act > 3) return RESEL_EINVAL;
+    const Route r = gemm_route(c, split);
+    switch (r.family) {
+        case Family::rows: case Family::tiles: return gemm_any_launch(c, 0);
+        case Family::first: return gemm_first_launch(c, r.split);
+        case Family::second: return gemm_bf3_launch(c, r.split);
+        default: return RESEL_EINVAL;
+    }
+}
+}  // namespace
+
 extern "C" int resel_gemm_f32(const float* A, int64_t lda, int64_t strideA, int a_kcontig,
                               const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
                               const float* bias, int64_t strideBias, int act,
@@ -541,46 +582,8 @@ extern "C" int resel_gemm_f32x(const float* A, int64_t lda, int64_t strideA, int
                                float* C, int64_t ldc, int64_t strideC, void* workspace,
                                int M, int N, int K, int batch, int split, const float* amax_a, const float* amax_b,
                                void* amax_c, unsigned amax_epoch, resel_stream_t stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || act < 0 || act > 3) return RESEL_EINVAL;
-    if (split != 0 && split != 2 && split != 3 && split != 6) return RESEL_EINVAL;
-    if (split == 2 && (!amax_a || !amax_b)) return RESEL_EINVAL;
-    if (amax_c && (reinterpret_cast<uintptr_t>(amax_c) & 7u)) return RESEL_EINVAL;
-    if (split == 2 && M <= 128) split = 6;         // narrow shapes stay on the first edition's fp32-accurate bf16 split
-    if (K < BK) split = 0;                         // the split kernels' scheduled loads assume one whole K step per item
-    if (lda <= 0 || ldb <= 0 || ldc <= 0) return RESEL_EINVAL;
-    // What the matrix-core editions need: float4 loads along each operand's contiguous axis (16-byte aligned rows, that extent a
-    // multiple of 4), 32-bit piece offsets inside a tile (128 rows or 32 k of the leading dimension).  Everything else - the 6-wide
-    // heads and their gradients, rank-2 projections, odd action counts - and the M <= 8 rows of a rollout step against a whole weight
-    // matrix go to gemm_any.hip (exact fp32 FMAs, same epilogues, same magnitude publication): no shape is refused, none is left to a
-    // vendor library.
-    const bool mfma_ok = !(lda % 4 || ldb % 4 || strideA % 4 || strideB % 4 || !aligned16(A) || !aligned16(B) || (a_kcontig ? K : M) % 4 ||
-                           (b_kcontig ? K : N) % 4 || lda >= (int64_t)1 << 22 || ldb >= (int64_t)1 << 22);
-    if (!mfma_ok || gemm_any_rows_ok(A, lda, strideA, a_kcontig, 0, B, ldb, strideB, b_kcontig, M, K, act))
-        return gemm_any_launch(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, act, C, ldc, strideC, workspace, M, N, K,
-                               batch, 0, (unsigned long long*)amax_c, amax_epoch, (hipStream_t)stream);
-    // second edition (256 x 128 tiles) unless half of its tile rows would be padding: M <= 128 (narrow weight gradients) runs
-    // 1.2-1.4x faster on the first edition's 128 x 128 tiles (66 752-token weight gradients [128, 256]: 48 vs 59 us, [80, 512]: 67 vs 95)
-    if ((split == 2 || split == 3 || split == 6) && M > 128)
-        return gemm_bf3_launch(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, act, C, ldc, strideC, workspace,
-                               M, N, K, batch, split, (hipStream_t)stream, amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch);
-    if (split == 3) split = 6;                     // the two-plane mode exists on the second-edition kernel only: narrow shapes keep mode 6
-    const Plan pl = make_plan<BM, BN, GRID>(M, N, K, batch);
-    if (pl.nsplit && (!workspace || !aligned16(workspace))) return RESEL_EINVAL;
-    GemmParams p{A, B, bias, C, (float*)workspace, lda, ldb, ldc, strideA, strideB, strideC, strideBias, M, N, K, act,
-                 (M + BM - 1) / BM, (N + BN - 1) / BN, pl.nfull, pl.nsplit, pl.nsl, pl.kslice, AmaxOut{(unsigned long long*)amax_c, amax_epoch}};
-    const int64_t total = (int64_t)pl.nfull + (int64_t)pl.nsplit * pl.nsl;
-    dim3 grid((unsigned)std::min<int64_t>(total, GRID));
-    hipStream_t s = (hipStream_t)stream;
-#define RESEL_GEMM_LAUNCH(SP) \
-    do { if (a_kcontig && b_kcontig) launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<true, true, SP>, grid, dim3(256), 0, s, p); \
-         else if (a_kcontig) launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<true, false, SP>, grid, dim3(256), 0, s, p); \
-         else if (b_kcontig) launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<false, true, SP>, grid, dim3(256), 0, s, p); \
-         else launch_timed(RESEL_PROF_GEMM, gemm_f32_kernel<false, false, SP>, grid, dim3(256), 0, s, p); } while (0)
-    if (split == 6) RESEL_GEMM_LAUNCH(6);
-    else RESEL_GEMM_LAUNCH(0);
-#undef RESEL_GEMM_LAUNCH
-    if (pl.nsplit) hipLaunchKernelGGL((gemm_fixup_kernel<BM, BN, GemmParams>), dim3(TILE / 4 / 64, pl.nsplit), dim3(64, 4), 0, s, p);
-    return launch_status();
+    return gemm_run(GemmCall{A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, act, C, ldc, strideC, workspace, M, N, K, batch,
+                             amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch, (hipStream_t)stream}, split);
 }
 
 // ---- fused epilogues of the producer / consumer edition (ABI 7; product mode 2 only) ----------------------------------------------
@@ -595,22 +598,16 @@ __global__ __launch_bounds__(256) void head_fold_kernel(const float* __restrict_
     for (int j = 0; j < parts; ++j) acc += pz[(int64_t)j * M];
     q[(int64_t)z * M + m] = acc;
 }
-bool fused_args_ok(const float* A, int64_t lda, int64_t strideA, int a_kcontig, const float* B, int64_t ldb, int64_t strideB, int b_kcontig,
-                   const float* C, int64_t ldc, int M, int N, int K, int batch, const float* amax_a, const float* amax_b, const void* amax_c,
-                   const void* workspace) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || !amax_a || !amax_b || !workspace || !aligned16(workspace)) return false;
-    if (amax_c && (reinterpret_cast<uintptr_t>(amax_c) & 7u)) return false;
-    if (lda % 4 || ldb % 4 || ldc % 4 || strideA % 4 || strideB % 4 || !aligned16(A) || !aligned16(B) || !aligned16(C)) return false;
-    if ((a_kcontig ? K : M) % 4 || (b_kcontig ? K : N) % 4 || N % 4) return false;
-    if (lda <= 0 || ldb <= 0 || ldc <= 0) return false;
-    return gemm_bf3_fused_ok(M, N, K, lda, ldb);
+// what both fused entries need: mode 2's handles, a workspace, operands and output the third edition reads and writes as float4, its shape rules
+bool fused_args_ok(const GemmCall& c) {
+    return call_valid(c) && c.amax_a && c.amax_b && c.workspace && aligned16(c.workspace) && gemm_mfma_readable(c) && c.ldc % 4 == 0 &&
+           aligned16(c.C) && c.N % 4 == 0 && gemm_bf3_fused_ok(c.M, c.N, c.K);
 }
 }  // namespace
 
 extern "C" int resel_gemm_f32_fused_supported(int kind, int M, int N, int K, int64_t lda, int64_t ldb) {
-    if (kind == 4) return (M >= 256 && N % 128 == 0 && gemm_bf3_fused_ok(M, N, K, lda, ldb)) ? 1 : 0;
-    if (kind == 5) return gemm_bf3_fused_ok(M, N, K, lda, ldb) ? 1 : 0;
-    return 0;
+    if (!gemm_ld_in_reach(lda, ldb) || !gemm_bf3_fused_ok(M, N, K)) return 0;
+    return kind == 5 || (kind == 4 && M >= 256 && N % 128 == 0) ? 1 : 0;
 }
 
 extern "C" size_t resel_gemm_f32_fused_workspace_bytes(int M, int N, int K, int batch, int kind) {
@@ -652,24 +649,26 @@ extern "C" int resel_gemm_f32_dact(const float* A, int64_t lda, int64_t strideA,
                                    float* C, int64_t ldc, int64_t strideC, float* dbias, void* workspace,
                                    int M, int N, int K, int batch, const float* amax_a, const float* amax_b,
                                    void* amax_c, unsigned amax_epoch, resel_stream_t stream) {
-    if (!fused_args_ok(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, C, ldc, M, N, K, batch, amax_a, amax_b, amax_c, workspace)) return RESEL_EINVAL;
+    const GemmCall c{A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, nullptr, 0, 4, C, ldc, strideC, workspace, M, N, K, batch,
+                     amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch, (hipStream_t)stream};
+    if (!fused_args_ok(c)) return RESEL_EINVAL;
     if (!Y || ldy % 4 || strideY % 4 || ldy <= 0 || !aligned16(Y) || !a_kcontig || M < 256 || N % 128) return RESEL_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
     // the fused epilogue takes whole 256-row tiles; the (at most 255) rows behind them: plain product, then one small in-place pass
     const int Mm = M / 256 * 256, tail = M - Mm, rows = 2 * (Mm / 256) + (tail ? 1 : 0);
     float* part = dbias ? (float*)workspace : nullptr;                     // [batch][rows][N]
-    int rc = gemm_bf3_launch(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, nullptr, 0, 4, C, ldc, strideC, nullptr, Mm, N, K, batch, 2,
-                             s, amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch, Y, ldy, strideY, part, rows);
+    GemmCall body = c, rest = c;
+    body.M = Mm; body.workspace = nullptr;
+    int rc = gemm_bf3_launch(body, 2, GemmFused{Y, ldy, strideY, part, rows});
     if (rc != RESEL_OK) return rc;
     if (tail) {
-        char* ws2 = (char*)workspace + ((size_t)rows * N * batch * sizeof(float) + 255) / 256 * 256;
-        rc = resel_gemm_f32x(A + (int64_t)Mm * lda, lda, strideA, 1, B, ldb, strideB, b_kcontig, nullptr, 0, 0, C + (int64_t)Mm * ldc, ldc, strideC, ws2,
-                             tail, N, K, batch, 2, amax_a, amax_b, nullptr, 0u, stream);
+        rest.A = A + (int64_t)Mm * lda; rest.C = C + (int64_t)Mm * ldc; rest.M = tail; rest.act = 0; rest.amax_c = nullptr; rest.amax_epoch = 0u;
+        rest.workspace = (char*)workspace + ((size_t)rows * N * batch * sizeof(float) + 255) / 256 * 256;
+        rc = gemm_run(rest, 2);
         if (rc != RESEL_OK) return rc;
-        hipLaunchKernelGGL(dact_tail_kernel, dim3((N + 63) / 64, batch), dim3(256), 0, s, C + (int64_t)Mm * ldc, ldc, strideC, Y + (int64_t)Mm * ldy, ldy, strideY,
+        hipLaunchKernelGGL(dact_tail_kernel, dim3((N + 63) / 64, batch), dim3(256), 0, c.s, C + (int64_t)Mm * ldc, ldc, strideC, Y + (int64_t)Mm * ldy, ldy, strideY,
                            tail, N, part ? part + (int64_t)(rows - 1) * N : nullptr, (int64_t)rows * N, AmaxOut{(unsigned long long*)amax_c, amax_epoch});
     }
-    if (dbias) launch_colsum(part, N, rows, N, dbias, s, 1, 0, batch);
+    if (dbias) launch_colsum(part, N, rows, N, dbias, c.s, 1, 0, batch);
     return launch_status();
 }
 
@@ -679,12 +678,13 @@ extern "C" int resel_gemm_f32_head(const float* A, int64_t lda, int64_t strideA,
                                    float* C, int64_t ldc, int64_t strideC, float* q, void* workspace,
                                    int M, int N, int K, int batch, const float* amax_a, const float* amax_b,
                                    void* amax_c, unsigned amax_epoch, resel_stream_t stream) {
-    if (!fused_args_ok(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, C, ldc, M, N, K, batch, amax_a, amax_b, amax_c, workspace)) return RESEL_EINVAL;
+    GemmCall c{A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, 5, C, ldc, strideC, workspace, M, N, K, batch,
+               amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch, (hipStream_t)stream};
+    if (!fused_args_ok(c)) return RESEL_EINVAL;
     if (!w3 || !q || strideW3 % 4 || !aligned16(w3)) return RESEL_EINVAL;
-    const int rc = gemm_bf3_launch(A, lda, strideA, a_kcontig, B, ldb, strideB, b_kcontig, bias, strideBias, 5, C, ldc, strideC, nullptr, M, N, K, batch, 2,
-                                   (hipStream_t)stream, amax_a, amax_b, (unsigned long long*)amax_c, amax_epoch, w3, 0, strideW3, (float*)workspace);
+    c.workspace = nullptr;                           // no K slices; the caller's workspace takes the row dots
+    const int rc = gemm_bf3_launch(c, 2, GemmFused{w3, 0, strideW3, (float*)workspace, 0});
     if (rc != RESEL_OK) return rc;
-    hipLaunchKernelGGL(head_fold_kernel, dim3((M + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, (const float*)workspace,
-                       2 * ((N + 127) / 128), M, b3, q);
+    hipLaunchKernelGGL(head_fold_kernel, dim3((M + 255) / 256, batch), dim3(256), 0, c.s, (const float*)workspace, 2 * ((N + 127) / 128), M, b3, q);
     return launch_status();
 }

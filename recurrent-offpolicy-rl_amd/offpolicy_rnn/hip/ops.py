@@ -1105,6 +1105,7 @@ def guard_apply_slots(slots, world, guard):
 ACT_IDS = {None: 0, 'linear': 0, 'elu': 1}
 GEMM_SOFTPLUS = 'softplus'           # resel_gemm_f32x only: softplus(product + bias) (epilogue code 3)
 GEMM_ACCUMULATE = 'accumulate'       # resel_gemm_f32 only: C += product (epilogue code 2)
+GEMM_EPILOGUES = {None: 0, 'linear': 0, 'elu': 1, GEMM_ACCUMULATE: 2, GEMM_SOFTPLUS: 3}      # `act` of resel_gemm_f32x (ACT_IDS: the two bias_act knows)
 
 
 @torch.no_grad()
@@ -1362,7 +1363,7 @@ def gemm_f32_ok(*mats):
 
 def rows_aligned16(*mats):
     """Every row of every operand starts on a 16-byte boundary and is a whole number of float4s: what the matrix-core editions (and their
-    fused epilogues, which have no other form) read."""
+    fused epilogues, which have no other form) read: the host-side mirror of `gemm_mfma_readable` (csrc/gemm_call.h), which decides."""
     return all(t.data_ptr() % 16 == 0 and t.shape[-1] % 4 == 0 and all(st % 4 == 0 for st in t.stride()[:-1])
                and (t.dim() < 2 or t.stride(-2) < (1 << 22)) for t in mats)
 
@@ -1506,7 +1507,6 @@ def gemm_split():
     if GEMM_SPLIT is not None:
         return GEMM_SPLIT
     return 2 if torch.get_float32_matmul_precision() == 'highest' else 3
-
 
 
 _GEMM_WS_BYTES = {}           # (M, N, K, batch) -> workspace bytes of resel_gemm_f32 (a pure function of the shape)
@@ -1776,13 +1776,40 @@ def _prepass(x):
     return h
 
 
-def _verify_operands(A, B, ha, hb, what):
-    amax_check(A, ha, 'A of ' + what)
-    amax_check(B, hb, 'B of ' + what)
+def _mode2_shape(M, K):
+    """False for the shapes the library never runs in product mode 2 (it takes mode 6 for M <= 128 and the fp32 instruction for K < 32):
+    no pre-pass is spent on them.  `gemm_route` in csrc/gemm_f32.hip is the authority; this mirrors its two shape rules and nothing else."""
+    return K >= 32 and M > 128
 
 
-def _gemm_done(out, slot, split):
-    """Tail of the three GEMM forms: the output carries the magnitude its epilogue published."""
+def _gemm_operands(A, B, a_kcontig, b_kcontig):
+    """The one reading of a product's operands (layouts as `gemm_f32` describes them) -> batch, M, N, K, multi, and the argument block every
+    fp32 GEMM entry starts with: (pointer, row stride, batch stride, kcontig) of A and of B.  (Outputs and side operands with the product's
+    shape follow in the same form, (pointer, row stride, batch stride if multi else 0), written out at the call: a helper call is 0.5 us.)"""
+    sa_, sb_, ta, tb = A.shape, B.shape, A.stride(), B.stride()       # one call each: this runs 80 times per update
+    assert ta[-1] == 1 and tb[-1] == 1 and A.dtype == torch.float32 and B.dtype == torch.float32
+    batched = len(sa_) == 3
+    batch = sa_[0] if batched else 1
+    M, K = (sa_[-2], sa_[-1]) if a_kcontig else (sa_[-1], sa_[-2])
+    N = sb_[-2] if b_kcontig else sb_[-1]
+    assert (sb_[-1] if b_kcontig else sb_[-2]) == K and (not batched or sb_[0] == batch)
+    multi = batch > 1
+    return batch, M, N, K, multi, (_p(A), ta[-2], ta[0] if multi else 0, int(a_kcontig), _p(B), tb[-2], tb[0] if multi else 0, int(b_kcontig))
+
+
+def _gemm_run(fn, name, A, B, args, M, N, K, batch, split, ha, hb, out, track=True, amax_out=None, publish=False):
+    """The shared tail of the three GEMM forms.  `args`: everything in front of the handles; ha / hb: the operands' magnitude handles in product
+    mode 2, else None.  The output gets a magnitude slot - max |C| for whoever multiplies C next - while mode 2 is the product mode and it is worth
+    a pass (`track`; amax_out: (handle, pointer, epoch) of a row buffer this product fills a column block of - its producers share one handle)."""
+    GEMM_FLOPS[0] += 2.0 * M * N * K * batch
+    if AMAX_VERIFY and ha is not None:
+        what = f'{name.replace("_f32", "", 1)} M={M} N={N} K={K} batch={batch}'
+        amax_check(A, ha, 'A of ' + what)
+        amax_check(B, hb, 'B of ' + what)
+    slot, slot_p, epoch = amax_out if amax_out is not None else _slot_args(M * N * batch >= (1 << 20) and track and amax_tracking(), A.device)
+    check(fn(*args, _p(ha), _p(hb), slot_p, epoch, _stream()), name)
+    if publish:
+        publish_amax(slot)                           # for `linear_act` / `EnsembleLinear.forward`, which run this product inside a Function
     LAST_SPLIT[0] = split                            # tools/gemm_census.py: which product mode the call took
     return tag_amax(out, slot)
 
@@ -1794,17 +1821,11 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
     A, B, bias [N] / [batch, N], out.  Row stride free (column stride 1); returns C [M, N] / [batch, M, N].
     (The wrapper is on the host's critical path at small batches: 79 calls per update - no temporary views, cached sizes.)"""
     _need_cuda('gemm_f32', A, B)
+    batch, M, N, K, multi, operands = _gemm_operands(A, B, a_kcontig, b_kcontig)
     batched = A.dim() == 3
-    assert A.stride(-1) == 1 and B.stride(-1) == 1 and A.dtype == torch.float32 and B.dtype == torch.float32
-    sa_, sb_ = A.shape, B.shape
-    batch = sa_[0] if batched else 1
-    M, K = (sa_[-2], sa_[-1]) if a_kcontig else (sa_[-1], sa_[-2])
-    N = sb_[-2] if b_kcontig else sb_[-1]
-    assert (sb_[-1] if b_kcontig else sb_[-2]) == K and (not batched or sb_[0] == batch)
     if out is None:
         out = torch.empty((batch, M, N) if batched else (M, N), dtype=torch.float32, device=A.device)
     assert out.stride(-1) == 1
-    GEMM_FLOPS[0] += 2.0 * M * N * K * batch
     L = lib()
     key = (M, N, K, batch)
     nb = _GEMM_WS_BYTES.get(key)
@@ -1813,15 +1834,16 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
     ws = _ws(nb, A.device) if nb else None
     bs = 0
     if bias is not None:
-        bias = bias.reshape(batch, N) if batched else bias.reshape(N)
+        if bias.dim() != (2 if batched else 1):          # [N] / [batch, N] as they are: a reshape is a view, and a view is 3 us of host time
+            bias = bias.reshape(batch, N) if batched else bias.reshape(N)
+        assert bias.shape[-1] == N and (not batched or bias.shape[0] == batch)
         bs = bias.stride(0) if batched else 0
-    multi = batch > 1
     split = gemm_split() if split is None else int(split)
     ha = hb = None
     if split == 2:
         # mode 2 (fp16 planes of the scaled operands) needs a bound on max |A|, max |B| on the device: a producer's tag, the
         # caller's handle, or - when reading the operand once more is cheap next to the GEMM - one resel_amax pass (tagged for reuse)
-        if K < 32 or M <= 128:
+        if not _mode2_shape(M, K):
             split = 6
         else:
             ha, hb = _operand_handles(A, B, amax_a, amax_b)
@@ -1832,19 +1854,9 @@ def gemm_f32(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None
                     ha = _prepass(A) if ha is None else ha
                     hb = _prepass(B) if hb is None else hb
                 else:
-                    split = 6
-    if AMAX_VERIFY and split == 2:
-        _verify_operands(A, B, ha, hb, f'gemm M={M} N={N} K={K} batch={batch}')
-    # max |C| for whoever multiplies C next (only while mode 2 is the product mode, and only for outputs worth a pass)
-    # (amax_out: the (handle, pointer, epoch) of a row buffer this product fills a column block of - its producers share one handle)
-    slot, slot_p, epoch = amax_out if amax_out is not None else \
-        _slot_args(amax_tracking() and act != GEMM_ACCUMULATE and M * N * batch >= (1 << 20), A.device)
-    check(L.resel_gemm_f32x(_p(A), A.stride(-2), A.stride(0) if multi else 0, int(a_kcontig), _p(B), B.stride(-2),
-                            B.stride(0) if multi else 0, int(b_kcontig), _p(bias), bs, 2 if act == GEMM_ACCUMULATE else 3 if act == GEMM_SOFTPLUS else ACT_IDS[act], _p(out), out.stride(-2),
-                            out.stride(0) if multi else 0, _p(ws), M, N, K, batch, split, _p(ha) if split == 2 else None,
-                            _p(hb) if split == 2 else None, slot_p, epoch, _stream()), 'gemm_f32')
-    publish_amax(slot)                               # for `linear_act` / `EnsembleLinear.forward`, which run this product inside a Function
-    return _gemm_done(out, slot, split)
+                    split, ha, hb = 6, None, None
+    return _gemm_run(L.resel_gemm_f32x, 'gemm_f32', A, B, operands + (_p(bias), bs, GEMM_EPILOGUES[act], _p(out), out.stride(-2), out.stride(0) if multi else 0, _p(ws), M, N, K, batch, split),
+                     M, N, K, batch, split, ha, hb, out, act != GEMM_ACCUMULATE, amax_out, True)
 
 
 # ---- fused epilogues of the producer / consumer GEMM (include/resel_hip.h `resel_gemm_f32_dact` / `resel_gemm_f32_head`) ----------
@@ -1871,25 +1883,14 @@ def gemm_f32_dact(A, B, b_kcontig, Y, out, need_dbias=True, amax_a=None, amax_b=
     bias gradient in the GEMM epilogue.  A [batch, M, K] / [M, K] (K contiguous); B [batch, N, K] (b_kcontig) or [batch, K, N]; Y and out
     [batch, M, N] with free row / batch strides.  -> (out, dbias [batch, N] or None)."""
     _need_cuda('gemm_f32_dact', A, B, Y, out)
-    batched = A.dim() == 3
-    batch = A.shape[0] if batched else 1
-    M, K = A.shape[-2], A.shape[-1]
-    N = B.shape[-2] if b_kcontig else B.shape[-1]
-    assert (B.shape[-1] if b_kcontig else B.shape[-2]) == K and Y.shape[-2:] == (M, N) and out.shape[-2:] == (M, N)
-    assert A.stride(-1) == 1 and B.stride(-1) == 1 and Y.stride(-1) == 1 and out.stride(-1) == 1
+    batch, M, N, K, multi, operands = _gemm_operands(A, B, True, b_kcontig)
+    assert Y.shape[-2:] == (M, N) and out.shape[-2:] == (M, N) and Y.stride(-1) == 1 and out.stride(-1) == 1
     ha, hb = _forced_handles(A, B, amax_a, amax_b)
-    if AMAX_VERIFY:
-        _verify_operands(A, B, ha, hb, f'gemm_dact M={M} N={N} K={K} batch={batch}')
-    GEMM_FLOPS[0] += 2.0 * M * N * K * batch
     L = lib()
     ws = _ws(L.resel_gemm_f32_fused_workspace_bytes(M, N, K, batch, 4), A.device)
     dbias = torch.empty(batch, N, dtype=torch.float32, device=A.device) if need_dbias else None
-    multi = batched and batch > 1
-    slot, slot_p, epoch = _slot_args(amax_tracking() and M * N * batch >= (1 << 20), A.device)
-    check(L.resel_gemm_f32_dact(_p(A), A.stride(-2), A.stride(0) if multi else 0, 1, _p(B), B.stride(-2), B.stride(0) if multi else 0, int(b_kcontig),
-                                _p(Y), Y.stride(-2), Y.stride(0) if multi else 0, _p(out), out.stride(-2), out.stride(0) if multi else 0,
-                                _p(dbias), _p(ws), M, N, K, batch, _p(ha), _p(hb), slot_p, epoch, _stream()), 'gemm_f32_dact')
-    return _gemm_done(out, slot, 2), dbias
+    args = operands + (_p(Y), Y.stride(-2), Y.stride(0) if multi else 0, _p(out), out.stride(-2), out.stride(0) if multi else 0, _p(dbias), _p(ws), M, N, K, batch)
+    return _gemm_run(L.resel_gemm_f32_dact, 'gemm_f32_dact', A, B, args, M, N, K, batch, 2, ha, hb, out), dbias
 
 
 @torch.no_grad()
@@ -1898,23 +1899,15 @@ def gemm_f32_head(A, B, b_kcontig, bias, w3, b3, amax_a=None, amax_b=None):
     an efc-E critic head in one GEMM.  A [batch, M, K]; B [batch, N, K] / [batch, K, N]; bias, w3 [batch, N]; b3 [batch] or None.
     -> (a [batch, M, N], q [batch, M])."""
     _need_cuda('gemm_f32_head', A, B, bias, w3)
-    batch, M, K = A.shape
-    N = B.shape[-2] if b_kcontig else B.shape[-1]
-    assert A.stride(-1) == 1 and B.stride(-1) == 1 and w3.shape == (batch, N) and w3.is_contiguous() and bias.shape == (batch, N) and bias.stride(-1) == 1
+    batch, M, N, K, multi, operands = _gemm_operands(A, B, True, b_kcontig)
+    assert A.dim() == 3 and w3.shape == (batch, N) and w3.is_contiguous() and bias.shape == (batch, N) and bias.stride(-1) == 1
     ha, hb = _forced_handles(A, B, amax_a, amax_b)
-    if AMAX_VERIFY:
-        _verify_operands(A, B, ha, hb, f'gemm_head M={M} N={N} K={K} batch={batch}')
-    GEMM_FLOPS[0] += 2.0 * M * N * K * batch
     L = lib()
     ws = _ws(L.resel_gemm_f32_fused_workspace_bytes(M, N, K, batch, 5), A.device)
     a = torch.empty(batch, M, N, dtype=torch.float32, device=A.device)
     q = torch.empty(batch, M, dtype=torch.float32, device=A.device)
-    multi = batch > 1
-    slot, slot_p, epoch = _slot_args(amax_tracking() and M * N * batch >= (1 << 20), A.device)
-    check(L.resel_gemm_f32_head(_p(A), A.stride(-2), A.stride(0) if multi else 0, 1, _p(B), B.stride(-2), B.stride(0) if multi else 0, int(b_kcontig),
-                                _p(bias), bias.stride(0) if multi else 0, _p(w3), N, _p(b3), _p(a), a.stride(-2), a.stride(0) if multi else 0, _p(q), _p(ws),
-                                M, N, K, batch, _p(ha), _p(hb), slot_p, epoch, _stream()), 'gemm_f32_head')
-    return _gemm_done(a, slot, 2), q
+    args = operands + (_p(bias), bias.stride(0) if multi else 0, _p(w3), N, _p(b3), _p(a), a.stride(-2), a.stride(0) if multi else 0, _p(q), _p(ws), M, N, K, batch)
+    return _gemm_run(L.resel_gemm_f32_head, 'gemm_f32_head', A, B, args, M, N, K, batch, 2, ha, hb, a), q
 
 
 # ---- one-token rollout step (T = 1, no autograd) ----------------------------------------------------------------------

@@ -1037,9 +1037,10 @@ def test_encode_concat_padded_block_diagonal_gemm_vs_separate_linears(ops):
 ])
 @pytest.mark.parametrize('split', [0, 6])
 def test_gemm_f32_vs_fp64_product(ops, M, N, K, akc, bkc, bias, act, batch, split):
-    """resel_gemm_f32 against an fp64 product: 1e-5 of the largest output magnitude in every product mode (0: fp32 MFMA, exact
-    products; 9 / 6: exact three-way bf16 operand split on the bf16 MFMA, all nine / the six leading plane products, operands
-    split once per block into bf16 planes in LDS (gemm_bf3.hip); 106: mode 6 on the first-edition kernel); both operand layouts, ragged edges, batch strides, fused bias + ELU, deterministic K split."""
+    """resel_gemm_f32 against an fp64 product: 1e-5 of the largest output magnitude in product modes 0 (fp32 MFMA, exact products) and
+    6 (exact three-way bf16 operand split on the bf16 MFMA, the six leading plane products: operands split once per block into bf16
+    planes in LDS, gemm_bf3.hip, for M > 128; on the first-edition kernel for narrower shapes); both operand layouts, ragged edges, batch
+    strides, fused bias + ELU, deterministic K split."""
     g = torch.Generator().manual_seed(M + N + K)
     sh = (batch,) if batch > 1 else ()
     A = torch.randn(*sh, *((M, K) if akc else (K, M)), generator=g)
