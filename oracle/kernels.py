@@ -13,6 +13,12 @@ import torch
 import torch.nn.functional as F
 
 
+def working(x):
+    """The precision a restatement computes in: fp64 operands stay fp64 (the fp64 oracle of OracleTrainer(dtype=torch.float64)),
+    everything else is taken up to fp32 - the `.float()` the reference's own restatements spell."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 # --------------------------------------------------------------------------------------------
 # smamba: selective scan  (reference spec: offpolicy_rnn/models/smamba/mamba_ssm/ops/
 # selective_scan_interface_new.py:96-166 `selective_scan_ref`; reset semantics :133-135;
@@ -27,26 +33,26 @@ def selective_scan_ref(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, sta
     """
     Bsz, L, Di = u.shape
     N = A.shape[1]
-    u = u.float()
-    delta = delta.float()
+    u = working(u)
+    delta = working(delta)
     if delta_bias is not None:
-        delta = delta + delta_bias.float()                        # :115-116
+        delta = delta + working(delta_bias)                       # :115-116
     if delta_softplus:
         delta = F.softplus(delta)                                 # :117-118
-    h = torch.zeros(Bsz, Di, N, dtype=torch.float32) if h0 is None else h0.float()
+    h = torch.zeros(Bsz, Di, N, dtype=u.dtype) if h0 is None else working(h0)
     ys = []
     for t in range(L):
-        dA = torch.exp(delta[:, t, :, None] * A[None].float())    # :132
+        dA = torch.exp(delta[:, t, :, None] * working(A[None]))   # :132
         if start is not None:
-            dA = dA * (1.0 - start[:, t].float())[:, None, None]  # :133-135
-        dBu = (delta[:, t] * u[:, t])[:, :, None] * Bm[:, t].float()[:, None, :]   # :140
+            dA = dA * (1.0 - working(start[:, t]))[:, None, None] # :133-135
+        dBu = (delta[:, t] * u[:, t])[:, :, None] * working(Bm[:, t])[:, None, :]  # :140
         h = dA * h + dBu                                          # :148
-        ys.append((h * Cm[:, t].float()[:, None, :]).sum(-1))     # :153
+        ys.append((h * working(Cm[:, t])[:, None, :]).sum(-1))    # :153
     y = torch.stack(ys, dim=1)
     if D is not None:
-        y = y + u * D.float()                                     # :162
+        y = y + u * working(D)                                    # :162
     if z is not None:
-        y = y * F.silu(z.float())                                 # :163-164
+        y = y * F.silu(working(z))                                # :163-164
     return y, h
 
 
@@ -76,7 +82,7 @@ def causal_conv1d_silu_ref(x, w, bias=None, mask=None, activation=True):
 # --------------------------------------------------------------------------------------------
 def add_layernorm_ref(x, residual, weight, bias, eps, rms=False):
     """x, residual: [..., C].  Returns (y, residual_out) with residual_out = x + residual (fp32)."""
-    res = x.float() if residual is None else x.float() + residual.float()
+    res = working(x) if residual is None else working(x) + working(residual)
     if rms:
         rstd = 1.0 / torch.sqrt(res.square().mean(-1, keepdim=True) + eps)      # layernorm_cpu.py:32
         y = res * rstd * weight
@@ -262,24 +268,25 @@ def attention_alibi_varlen_ref(q, k, v, cu_seqlens, slopes=None, scale=None, p_d
     result is taken over the unrounded fp32 values."""
     T, H, d = q.shape
     scale = (1.0 / math.sqrt(d)) if scale is None else scale
-    out = torch.zeros(T, H, d, dtype=torch.float32)
+    q, k, v = working(q), working(k), working(v)
+    out = torch.zeros(T, H, d, dtype=q.dtype)
     cu = [int(c) for c in cu_seqlens]
     for s in range(len(cu) - 1):
         a, b = cu[s], cu[s + 1]
         n = b - a
         if n <= 0:
             continue
-        qs, ks, vs = q[a:b].float(), k[a:b].float(), v[a:b].float()
+        qs, ks, vs = q[a:b], k[a:b], v[a:b]
         sc = torch.einsum('ihd,jhd->hij', qs, ks) * scale
         i = torch.arange(n)[:, None]
         j = torch.arange(n)[None, :]
         if slopes is not None:
-            sc = sc - slopes.float()[:, None, None] * (i - j).abs().float()[None]
+            sc = sc - slopes.to(sc.dtype)[:, None, None] * (i - j).abs().to(sc.dtype)[None]
         sc = sc.masked_fill((j > i)[None], float('-inf'))
         if p_bf16:
             e = torch.exp(sc - sc.max(dim=-1, keepdim=True).values)
             inv = 1.0 / e.sum(dim=-1, keepdim=True)
-            e = e.to(torch.bfloat16).float()
+            e = e.to(torch.bfloat16).to(e.dtype)
             if p_drop > 0.0:
                 e = torch.where(attn_dropout_keep(seed, offset, H, a, n, p_drop), e, torch.zeros_like(e))
                 inv = inv / (1.0 - p_drop)
@@ -311,7 +318,7 @@ def mamba_step_ref(conv_state, ssm_state, xz, conv_w, conv_b, xproj_w, dt_w, dt_
     R, N = dt_w.shape[1], ssm_state.shape[-1]
     dt, Bm, Cm = x_db[:, :R], x_db[:, R:R + N], x_db[:, R + N:]
     dt = F.softplus(F.linear(dt, dt_w) + dt_b)                                 # :284,290
-    A = -torch.exp(A_log.float())                                              # :285
+    A = -torch.exp(working(A_log))                                             # :285
     dA = torch.exp(dt.unsqueeze(-1) * A)                                       # :291
     dB = dt.unsqueeze(-1) * Bm.unsqueeze(1)                                    # :292
     ssm_state = ssm_state * dA + x.unsqueeze(-1) * dB                          # :293
@@ -323,11 +330,11 @@ def attn_decode_ref(q, k_cache, v_cache, pos, slopes=None, scale=None):
     """q [B, H, d] at position `pos`; k_cache, v_cache [B, S, H, d] already holding positions 0..pos.  -> [B, H, d]."""
     d = q.shape[-1]
     scale = (1.0 / math.sqrt(d)) if scale is None else scale
-    k, v = k_cache[:, :pos + 1].float(), v_cache[:, :pos + 1].float()
-    sc = torch.einsum('bhd,bjhd->bhj', q.float(), k) * scale
+    k, v = working(k_cache[:, :pos + 1]), working(v_cache[:, :pos + 1])
+    sc = torch.einsum('bhd,bjhd->bhj', working(q), k) * scale
     if slopes is not None:
-        j = torch.arange(pos + 1, dtype=torch.float32)
-        sc = sc - slopes.float()[None, :, None] * (pos - j)[None, None, :]
+        j = torch.arange(pos + 1, dtype=sc.dtype)
+        sc = sc - slopes.to(sc.dtype)[None, :, None] * (pos - j)[None, None, :]
     return torch.einsum('bhj,bjhd->bhd', torch.softmax(sc, dim=-1), v)
 
 

@@ -182,7 +182,7 @@ def conv1d_layer(p, pre, x, flags=None, h0=None):
     B, L, C = x.shape
     w = p[pre + 'conv1d.weight']                                    # [C, 1, K]
     Kw = w.shape[-1]
-    hid = torch.zeros(B, Kw - 1, C) if h0 is None else h0.reshape(B, Kw - 1, C)
+    hid = torch.zeros(B, Kw - 1, C, dtype=x.dtype) if h0 is None else h0.reshape(B, Kw - 1, C)
     if flags is not None and flags.mask is not None:
         x = x * flags.mask                                          # :30-31
     rows = torch.cat((hid, x), dim=1)                               # :32
@@ -200,8 +200,8 @@ def s6_mamba_layer(p, pre, x, cfg, flags=None, h0=None):
     xz = F.linear(h, p[mp + 'in_proj.weight'])
     Di = xz.shape[-1] // 2
     xi, res = xz[..., :Di], xz[..., Di:]
-    ssm0 = torch.zeros(B, Di, N) if h0 is None else h0[:, :Di * N].reshape(B, Di, N)
-    conv0 = torch.zeros(B, Kw - 1, Di) if h0 is None else h0[:, Di * N:].reshape(B, Kw - 1, Di)
+    ssm0 = torch.zeros(B, Di, N, dtype=x.dtype) if h0 is None else h0[:, :Di * N].reshape(B, Di, N)
+    conv0 = torch.zeros(B, Kw - 1, Di, dtype=x.dtype) if h0 is None else h0[:, Di * N:].reshape(B, Kw - 1, Di)
     if flags is not None and flags.mask is not None:
         xi = xi * flags.mask                                        # :131-132
     rows = torch.cat((conv0, xi), dim=1)
@@ -211,9 +211,9 @@ def s6_mamba_layer(p, pre, x, cfg, flags=None, h0=None):
     x_db = F.linear(xc, p[mp + 'x_proj.weight'])
     R = x_db.shape[-1] - 2 * N
     delta = F.softplus(F.linear(x_db[..., :R], p[mp + 'dt_proj.weight'], p[mp + 'dt_proj.bias']))   # :229
-    A = -torch.exp(p[mp + 'A_log'].float())
+    A = -torch.exp(K.working(p[mp + 'A_log']))
     Bm, Cm = x_db[..., R:R + N], x_db[..., R + N:]
-    start = torch.zeros(B, L) if flags is None or flags.rnn_start is None else flags.rnn_start[..., 0]
+    start = torch.zeros(B, L, dtype=x.dtype) if flags is None or flags.rnn_start is None else flags.rnn_start[..., 0]
     state, ys = ssm0, []
     for t in range(L):                                              # cpu_scan.py:41-57
         dA = torch.exp(delta[:, t, :, None] * A) * (1 - start[:, t])[:, None, None]
@@ -242,9 +242,9 @@ def mamba_mixer(p, pre, x, cfg, start, mask):
     R = x_dbl.shape[-1] - 2 * N
     dt = F.linear(x_dbl[..., :R], p[pre + 'dt_proj.weight'])        # :233 (bias goes in as delta_bias)
     Bm, Cm = x_dbl[..., R:R + N], x_dbl[..., R + N:]
-    A = -torch.exp(p[pre + 'A_log'].float())                        # :187
-    y, _ = K.selective_scan_ref(xc, dt, A, Bm, Cm, p[pre + 'D'].float(), z,
-                                p[pre + 'dt_proj.bias'].float(), start, True)    # :238-250
+    A = -torch.exp(K.working(p[pre + 'A_log']))                     # :187
+    y, _ = K.selective_scan_ref(xc, dt, A, Bm, Cm, K.working(p[pre + 'D']), z,
+                                K.working(p[pre + 'dt_proj.bias']), start, True)    # :238-250
     return F.linear(y, p[pre + 'out_proj.weight'])                  # :252
 
 
@@ -384,7 +384,7 @@ def cgpt_layer(p, pre, x, cfg, flags=None, bf16=True):
     for i in range(cfg['nlayer']):
         lp = f'{pre}decoder_layers.{i}.'
         h = _norm(p, lp + 'mha_norm.', t, cfg['ln'])
-        cast = (lambda a: a.to(torch.bfloat16).float()) if bf16 else (lambda a: a)
+        cast = (lambda a: a.to(torch.bfloat16).to(a.dtype)) if bf16 else (lambda a: a)
         qkv = cast(F.linear(cast(h), cast(p[lp + 'mha.Wqkv.weight']), cast(p[lp + 'mha.Wqkv.bias'])))
         qkv = qkv.view(-1, 3, H, hd)
         sd, of = dc.next() if dc is not None else (0, 0)
@@ -477,6 +477,12 @@ def categorical_head(out):
     return dist.mode.unsqueeze(-1), dist.sample().unsqueeze(-1), torch.log(dist.probs)
 
 
+def noise_like(x):
+    """Gaussian noise for a tensor of any working precision: always the fp32 draws (then cast), so that one seed gives an fp32
+    run, an fp64 run and the product the same numbers."""
+    return torch.randn_like(x, dtype=torch.float32).to(x.dtype)
+
+
 def policy_forward(p, cfg, state, lst_state, lst_action, flags=None, reward=None, noise=None,
                    algo='sac', sample_std=0.1, **kw):
     """ContextualSACPolicySingleHead.forward (contextual_sac_policy_single_head.py:92-107) and
@@ -495,11 +501,11 @@ def policy_forward(p, cfg, state, lst_state, lst_action, flags=None, reward=None
         return mean, emb, sample, logp
     if algo == 'td3':
         mean = torch.tanh(out)
-        noise = torch.randn_like(out) if noise is None else noise
+        noise = noise_like(out) if noise is None else noise
         sample = torch.clamp(mean + noise * sample_std, -1, 1)
         return mean, emb, sample, torch.zeros_like(sample)
     logstd, mu = out.chunk(2, dim=-1)                               # :105 (logstd first)
-    noise = torch.randn_like(mu) if noise is None else noise
+    noise = noise_like(mu) if noise is None else noise
     mean, sample, logp = K.tanh_gaussian_ref(mu, logstd, noise)
     return mean, emb, sample, logp
 
@@ -540,10 +546,10 @@ def policy_step(p, cfg, state, lst_state, lst_action, hidden, reward=None, noise
                            torch.cat((uni_in, emb), dim=-1), [])
     if algo == 'td3':
         mean = torch.tanh(out)
-        noise = torch.randn_like(out) if noise is None else noise
+        noise = noise_like(out) if noise is None else noise
         return mean, torch.clamp(mean + noise * sample_std, -1, 1), torch.zeros_like(mean), hidden
     logstd, mu = out.chunk(2, dim=-1)
-    noise = torch.randn_like(mu) if noise is None else noise
+    noise = noise_like(mu) if noise is None else noise
     mean, sample, logp = K.tanh_gaussian_ref(mu, logstd, noise)
     return mean, sample, logp, hidden
 

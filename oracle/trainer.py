@@ -97,7 +97,11 @@ def allow_nest_stack(par) -> bool:
 
 class OracleTrainer:
     def __init__(self, par, obs_dim, act_dim, max_traj_len, smamba_semantics='gpu', gru_impl='ref',
-                 policy_state=None, value_state=None, discrete=False):
+                 policy_state=None, value_state=None, discrete=False, dtype=torch.float32):
+        """dtype: the precision of the whole update - parameters, batch, flags, optimizer state.  torch.float64 is the high-precision
+        oracle (nothing is rounded to fp32 on the way; Gaussian noise is still drawn as fp32 numbers, NW.noise_like, so a seed gives
+        the same draws); the default is the reference's fp32."""
+        self.dtype = dtype
         self.par, self.obs_dim, self.act_dim = par, obs_dim, act_dim
         self.algo = par.base_algorithm
         self.discrete = discrete                                   # act_dim discrete actions (sac.py:49,72-79)
@@ -106,15 +110,15 @@ class OracleTrainer:
         self.fw = dict(smamba_semantics=smamba_semantics, gru_impl=gru_impl)
         self.pcfg = dict(model_cfg(par, obs_dim, act_dim, 'policy'), discrete=discrete)
         self.vcfg = dict(model_cfg(par, obs_dim, act_dim, 'value'), discrete=discrete)
-        clone = lambda sd: {m: {k: v.clone().float() for k, v in d.items()} for m, d in sd.items()}
-        self.policy = clone(policy_state) if policy_state is not None else NW.init_model(self.pcfg, 'policy')
-        self.value = clone(value_state) if value_state is not None else NW.init_model(self.vcfg, 'value')
+        clone = lambda sd: {m: {k: v.clone().to(dtype) for k, v in d.items()} for m, d in sd.items()}
+        self.policy = clone(policy_state if policy_state is not None else NW.init_model(self.pcfg, 'policy'))
+        self.value = clone(value_state if value_state is not None else NW.init_model(self.vcfg, 'value'))
         self.target_value = clone(self.value)                      # sac.py:69 hard update
         for net in (self.policy, self.value):
             for t in NW.flat_params(net):
                 t.requires_grad_(True)
         a0 = math.log(par.sac_alpha) if par.no_alpha_auto_tune else 0.0   # sac.py:75-78
-        self.log_alpha = torch.tensor([a0], dtype=torch.float32, requires_grad=True)
+        self.log_alpha = torch.tensor([a0], dtype=dtype, requires_grad=True)
         if self.algo == 'td3':
             # td3_full_length_rnn_ensembleQ.py:21-22 flips the flag only AFTER SAC.__init__ built log_alpha,
             # so a TD3 trainer starts (and stays) at log_alpha = 0 unless the user passed --no_alpha_auto_tune
@@ -166,7 +170,7 @@ class OracleTrainer:
                 par.sac_batch_size, randomize_mask=par.randomize_mask,
                 valid_number_post_randomized=par.valid_number_post_randomized,
                 equalize_data_of_each_traj=True, nest_stack_trajs=self.nest)
-            n2t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.float32)
+            n2t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dtype)
             (state, last_state, action, last_action, next_state, done, mask, reward, reward_input, timeout,
              rnn_start) = [n2t(getattr(batch, k)) for k in ('state', 'last_state', 'action', 'last_action', 'next_state',
                                                              'done', 'mask', 'reward', 'reward_input', 'timeout', 'start')]
@@ -178,9 +182,9 @@ class OracleTrainer:
             done[timeout > 0] = 0
             alpha = self.log_alpha.exp().detach()
             # per-row sequence tables (:358-366)
-            am = torch.from_numpy(table).to(torch.float32)
-            am = torch.cat((am, torch.zeros(am.shape[0], state.shape[-2] - am.shape[1])), dim=-1)
-            tam = torch.cat((am[..., 1:], torch.zeros(am.shape[0], 1)), dim=-1).to(torch.int)
+            am = torch.from_numpy(table).to(self.dtype)
+            am = torch.cat((am, torch.zeros(am.shape[0], state.shape[-2] - am.shape[1], dtype=self.dtype)), dim=-1)
+            tam = torch.cat((am[..., 1:], torch.zeros(am.shape[0], 1, dtype=self.dtype)), dim=-1).to(torch.int)
             am = am.to(torch.int)
             f_target = NW.Flags(total_start, total_valid, tam)
             f_online = NW.Flags(rnn_start, valid, am)
@@ -254,7 +258,7 @@ class OracleTrainer:
         par = self.par
         if self.discrete:                                           # sac_full_length_rnn_redq.py:52-72
             with torch.no_grad():
-                onehot = F.one_hot(action.squeeze(-1).long(), num_classes=self.act_dim).float()
+                onehot = F.one_hot(action.squeeze(-1).long(), num_classes=self.act_dim).to(self.dtype)
                 _, _, sample, logp = NW.policy_forward(self.policy, self.pcfg, next_state, state, onehot, flags, reward, **self.fw)
                 nq, _ = NW.value_forward(self.target_value, self.vcfg, next_state, state, onehot, sample, flags, reward, **self.fw)
                 idx = np.random.permutation(nq.shape[0])[:par.redq_m]
@@ -264,7 +268,7 @@ class OracleTrainer:
             mean, _, sample, logp = NW.policy_forward(self.policy, self.pcfg, next_state, state, action, flags, reward,
                                                       algo=self.algo, sample_std=par.sample_std, **self.fw)
             if self.algo == 'td3':                                  # td3_full_length_rnn_redq.py:21-25
-                noise = torch.clamp(torch.randn_like(mean) * par.target_action_noise_std,
+                noise = torch.clamp(NW.noise_like(mean) * par.target_action_noise_std,
                                     -par.target_action_noise_clip, par.target_action_noise_clip)
                 sample = torch.clamp(mean + noise, -1, 1)
             nq, _ = NW.value_forward(self.target_value, self.vcfg, next_state, state, action, sample, flags, reward, **self.fw)
