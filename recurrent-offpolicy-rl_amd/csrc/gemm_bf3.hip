@@ -583,13 +583,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
         // first MFMA operand: four consecutive n per lane, 16 float4 stores instead of 64 dword stores) was measured SLOWER
         // (583 -> 618 us at 66 752 x 2048 x 384): a store costs per line touched (32 rows x 32 bytes per instruction there).
         if (cur.split) {
-            float* o = p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) o[(32 * a + (e & 3) + 8 * (e >> 2)) * BN + 32 * b] = acc[a][b][e];
+            slab_store<BN>(p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li, acc);
         } else {
             float* C = p.C + (int64_t)cur.z * p.sC;
             const bool full_m = cur.m0 + BM <= p.M;
@@ -666,7 +660,11 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 //     native 128-bit vectors as asm operands, ONE path through the steady-state loop, the tail behind a drain;
 //   * one `s_barrier` per K step for all eight waves: stage s + 1 written, stage s read;
 //   * whole C tiles leave through a wave-private 5 KB LDS scratch (the third A plane of the stages, unused in mode 2) as 16-byte
-//     stores of eight whole 128-byte lines: 32 store instructions per wave and tile instead of 128 (a wave may have 63 in flight).
+//     stores of eight whole 128-byte lines: 32 store instructions per wave and tile instead of 128 (a wave may have 63 in flight);
+//     edge tiles and the accumulating form leave in the accumulator layout, as in the second edition;
+//   * after the K loop a K slice goes to the slab and a whole-K item through ONE of three separate epilogues, chosen at compile time:
+//     EPI 0 plain (bias, Params::act 0 .. 3), EPI 4 dact (whole tiles only: the host entry refuses other shapes), EPI 5 head (bias, ELU,
+//     row dots; whole and edge tiles).  Each spells out its own tile loop: see the note at EPI 0's whole-tile block.
 // 256 registers, 24 bytes of scratch (EPI 5: 84-92, EPI 4: 288), two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
 // us): fwd [T,384] -> 256 77 -> 67, [T,256] -> 256 55 -> 48, [T,256] -> 1024 171 -> 150, [T,384] -> 2048 420 -> 365.
 constexpr int NTH_WS = 512;
@@ -675,6 +673,7 @@ constexpr int WS_LDS = 2 * STAGE;
 
 template <bool AKC, bool BKC, int EPI = 0>
 __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
+    static_assert(EPI == 0 || EPI == 4 || EPI == 5, "EPI: 0 plain, 4 dact, 5 head (the act codes of the fused host entries)");
     extern __shared__ __attribute__((aligned(16))) char lds[];           // 2 stages
     const int tid = threadIdx.x;
     const int total = p.nfull + p.nsplit * p.nsl;
@@ -929,14 +928,15 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
         if (lane == 0) p.C[(int64_t)cur.m0 * p.ldc + cur.n0 + w] = acc[0][0][0] + acc[1][1][1] + acc[2][0][2] + acc[3][1][3];
         continue;
 #endif
-        // epilogue (as the second edition's, four row tiles)
+        // every item: undo the operand scales (powers of two, exact).  A K slice then leaves for the slab; a whole-K item leaves through ONE
+        // of three epilogues - plain (EPI 0), dact (EPI 4), head (EPI 5) - each ending the item
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[a][b][e] *= unscale;
-        if (cur.split) {
+        if (cur.split) {                                             // slab_store's twin (gemm_splitk.h): through the helper every EPI 0 instantiation changed
             float* o = p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li;
 #pragma unroll
             for (int a = 0; a < 4; ++a)
@@ -946,7 +946,8 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     for (int e = 0; e < 16; ++e) o[(32 * a + (e & 3) + 8 * (e >> 2)) * BN + 32 * b] = acc[a][b][e];
             continue;
         }
-        if constexpr (EPI == 0) {                                    // the plain epilogue, exactly as before the fused forms existed
+        if constexpr (EPI == 0) {
+            // ---- plain: bias, p.act (ELU / accumulate / softplus), exactly as before the fused forms existed
             float* C = p.C + (int64_t)cur.z * p.sC;
             const bool full_m = cur.m0 + BM <= p.M;
             if (full_m && cur.n0 + BN <= p.N && p.act != 2) {
@@ -955,6 +956,8 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                 // instructions per wave and tile instead of 128: a wave may have 63 vector-memory operations in flight, and with four
                 // consumer waves 128 dword stores each stalled on that limit (160 of 415 us at 66 752 x 2048 x 384).
                 // Scratch: the third A plane of the stages, which mode 2 does not use (waves 0, 1 in stage 0's, 2, 3 in stage 1's).
+                // Kept apart from head's whole-tile block (row tiles outermost there): through one shared loop every plain instantiation
+                // changed and its scratch grew from 24 to 92 - 96 bytes.  The same holds for helper functions (profiles/r13_gemm_epilogues.md).
                 char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
                 float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
                 const float4* rdp = reinterpret_cast<const float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
@@ -994,6 +997,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                 }
                 continue;
             }
+            // edge tiles and the accumulating form
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const int n = cur.n0 + wn + 32 * b + li;
@@ -1036,127 +1040,115 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     }
                 }
             }
-        } else {
+        } else if constexpr (EPI == 4) {
+            // ---- dact: C = product * elu'(Y), column sums.  Whole tiles only (the host entry sends the rows past the last whole 256-row
+            // tile elsewhere and refuses N % 128 != 0).  Two phases:
+            //   A  the Y values are loaded IN THE ACCUMULATOR LAYOUT (column = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2): a dword load
+            //      covers two whole 128-byte lines) and multiplied into the accumulators in place, tile by tile with PF tiles of loads in
+            //      flight; column sums and the magnitude come from the same registers;
+            //   B  the tiles leave exactly as in the plain epilogue (LDS turn, 16-byte full-line non-temporal stores).
+            // No store is issued between the loads of an item: a wait for a load also waits for every OLDER store (one in-order counter
+            // per wave), and with loads and stores interleaved per tile every tile waited for the write acknowledgements of the tiles
+            // before it (measured: 650 us against 305 for the product alone; this form: see profiles/r05_gemm.md).  The loads are inline
+            // assembly with a scalar base + ONE per-lane offset register (the compiler formed a 64-bit address pair per load and spilled
+            // accumulators; every scratch reload is a vmcnt(0)); it does not count them: each tile waits for ITS sixteen loads with a
+            // hand-written vmcnt = the loads issued since (foreign vector-memory operations only make a wait stricter).
             float* C = p.C + (int64_t)cur.z * p.sC;
-            const bool full_m = cur.m0 + BM <= p.M;
-            constexpr bool DACT = EPI == 4, HEAD = EPI == 5;               // fused epilogues: Params::aux / red
-            const int act = EPI ? (HEAD ? 1 : 0) : p.act;
-            if constexpr (DACT) {
-                // Whole tiles only (the host entry sends the rows past the last whole 256-row tile elsewhere).  Two phases:
-                //   A  the Y values are loaded IN THE ACCUMULATOR LAYOUT (column = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2): a dword load
-                //      covers two whole 128-byte lines) and multiplied into the accumulators in place, tile by tile with PF tiles of loads in
-                //      flight; column sums and the magnitude come from the same registers;
-                //   B  the tiles leave exactly as in the plain epilogue (LDS turn, 16-byte full-line non-temporal stores).
-                // No store is issued between the loads of an item: a wait for a load also waits for every OLDER store (one in-order counter
-                // per wave), and with loads and stores interleaved per tile every tile waited for the write acknowledgements of the tiles
-                // before it (measured: 650 us against 305 for the product alone; this form: see profiles/r05_gemm.md).  The loads are inline
-                // assembly with a scalar base + ONE per-lane offset register (the compiler formed a 64-bit address pair per load and spilled
-                // accumulators; every scratch reload is a vmcnt(0)); it does not count them: each tile waits for ITS sixteen loads with a
-                // hand-written vmcnt = the loads issued since (foreign vector-memory operations only make a wait stricter).
-                constexpr int PF = 3;
-                // per-lane constants are formed HERE from the lane id (v_mbcnt) and the wave id in a scalar register: kept across the K loop
-                // they were spilled
-                const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                const int li = lane & 31, lh = lane >> 5;
-                const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                const int wm = (w >> 1) * 128, wn = (w & 1) * 64;
-                typedef float f32x4a __attribute__((ext_vector_type(4)));
-                f32x4a yv[8][4];
-                // Y travels as 16-byte loads of whole 128-byte lines (a lane: rows 8 g + (lane >> 3), columns 4 (lane & 7) .. + 3 - the form the C
-                // tiles leave in) and is turned INTO the accumulator layout through the wave's LDS scratch: dword loads in the accumulator
-                // layout cost four times the address work per byte (128 load instructions per item and wave; measured 542 us, this form: r05_gemm.md)
-                char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
-                float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
-                float4* rdp = reinterpret_cast<float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
-                const uint32_t ylane = (uint32_t)(((lane >> 3) * (int)p.ldaux + 4 * (lane & 7)) * 4);
-                const float* ybase = p.aux + (int64_t)cur.z * p.sAux + (int64_t)(cur.m0 + wm) * p.ldaux + cur.n0 + wn;
-                auto yld = [](f32x4a& r, uint32_t off, const float* base) {        // (asm operands inside the generic lambdas below are not captured: a clang quirk)
-                    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(r) : "v"(off), "s"(base) : "memory");
-                };
-                auto ywait = [](f32x4a& r0, f32x4a& r1, f32x4a& r2, f32x4a& r3, auto NC) {
-                    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : "n"(decltype(NC)::value) : "memory");
-                };
-                auto yload = [&](auto TC) {
-                    constexpr int t = decltype(TC)::value;
-                    if constexpr (t < 8) {
-                        const float* yb = ybase + (int64_t)(32 * (t >> 1)) * p.ldaux + 32 * (t & 1);
+            constexpr int PF = 3;
+            // per-lane constants are formed HERE from the lane id (v_mbcnt) and the wave id in a scalar register: kept across the K loop
+            // they were spilled
+            const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const int li = lane & 31, lh = lane >> 5;
+            const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+            const int wm = (w >> 1) * 128, wn = (w & 1) * 64;
+            typedef float f32x4a __attribute__((ext_vector_type(4)));
+            f32x4a yv[8][4];
+            // Y travels as 16-byte loads of whole 128-byte lines (a lane: rows 8 g + (lane >> 3), columns 4 (lane & 7) .. + 3 - the form the C
+            // tiles leave in) and is turned INTO the accumulator layout through the wave's LDS scratch: dword loads in the accumulator
+            // layout cost four times the address work per byte (128 load instructions per item and wave; measured 542 us, this form: r05_gemm.md)
+            char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
+            float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
+            float4* rdp = reinterpret_cast<float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
+            const uint32_t ylane = (uint32_t)(((lane >> 3) * (int)p.ldaux + 4 * (lane & 7)) * 4);
+            const float* ybase = p.aux + (int64_t)cur.z * p.sAux + (int64_t)(cur.m0 + wm) * p.ldaux + cur.n0 + wn;
+            auto yld = [](f32x4a& r, uint32_t off, const float* base) {        // (asm operands inside the generic lambdas below are not captured: a clang quirk)
+                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(r) : "v"(off), "s"(base) : "memory");
+            };
+            auto ywait = [](f32x4a& r0, f32x4a& r1, f32x4a& r2, f32x4a& r3, auto NC) {
+                asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : "n"(decltype(NC)::value) : "memory");
+            };
+            auto yload = [&](auto TC) {
+                constexpr int t = decltype(TC)::value;
+                if constexpr (t < 8) {
+                    const float* yb = ybase + (int64_t)(32 * (t >> 1)) * p.ldaux + 32 * (t & 1);
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) yld(yv[t][g], ylane, yb + (int64_t)(8 * g) * p.ldaux);
-                    }
-                };
-                float cs[2] = {0.f, 0.f}, cmx = 0.f;
-                auto mul = [&](auto TC) {
-                    constexpr int t = decltype(TC)::value;
-                    constexpr int a = t >> 1, b = t & 1;
-                    yload(std::integral_constant<int, t + PF>{});
-                    ywait(yv[t][0], yv[t][1], yv[t][2], yv[t][3], std::integral_constant<int, 4 * ((t + PF < 7 ? t + PF : 7) - t)>{});
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) rdp[g * 8 * 10] = make_float4(yv[t][g].x, yv[t][g].y, yv[t][g].z, yv[t][g].w);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const float y = wr[((e & 3) + 8 * (e >> 2)) * 40];
-                        const float v = acc[a][b][e] * (y > 0.f ? 1.f : y + 1.f);
-                        acc[a][b][e] = v;
-                        cs[b] += v;
-                        cmx = fmaxf(cmx, __builtin_fabsf(v));
-                    }
-                };
-                yload(std::integral_constant<int, 0>{}); yload(std::integral_constant<int, 1>{}); yload(std::integral_constant<int, 2>{});
-                static_assert(PF == 3, "the prologue issues PF tiles");
-                mul(std::integral_constant<int, 0>{}); mul(std::integral_constant<int, 1>{}); mul(std::integral_constant<int, 2>{});
-                mul(std::integral_constant<int, 3>{}); mul(std::integral_constant<int, 4>{}); mul(std::integral_constant<int, 5>{});
-                mul(std::integral_constant<int, 6>{}); mul(std::integral_constant<int, 7>{});
-                if (p.red) {
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        const float c = cs[b] + __shfl_xor(cs[b], 32, 64);       // the two row halves of the accumulator layout
-                        if (lh == 0) p.red[((int64_t)cur.z * p.redrows + 2 * (cur.m0 / BM) + (w >> 1)) * p.N + cur.n0 + wn + 32 * b + li] = c;
-                    }
+                    for (int g = 0; g < 4; ++g) yld(yv[t][g], ylane, yb + (int64_t)(8 * g) * p.ldaux);
                 }
-                amax_publish_wave(cmx, p.amaxC);                         // one conditional atomic per wave and item (a maximum carried across the K loops was spilled)
-                // phase B
+            };
+            float cs[2] = {0.f, 0.f}, cmx = 0.f;
+            auto mul = [&](auto TC) {
+                constexpr int t = decltype(TC)::value;
+                constexpr int a = t >> 1, b = t & 1;
+                yload(std::integral_constant<int, t + PF>{});
+                ywait(yv[t][0], yv[t][1], yv[t][2], yv[t][3], std::integral_constant<int, 4 * ((t + PF < 7 ? t + PF : 7) - t)>{});
+#pragma unroll
+                for (int g = 0; g < 4; ++g) rdp[g * 8 * 10] = make_float4(yv[t][g].x, yv[t][g].y, yv[t][g].z, yv[t][g].w);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float y = wr[((e & 3) + 8 * (e >> 2)) * 40];
+                    const float v = acc[a][b][e] * (y > 0.f ? 1.f : y + 1.f);
+                    acc[a][b][e] = v;
+                    cs[b] += v;
+                    cmx = fmaxf(cmx, __builtin_fabsf(v));
+                }
+            };
+            yload(std::integral_constant<int, 0>{}); yload(std::integral_constant<int, 1>{}); yload(std::integral_constant<int, 2>{});
+            static_assert(PF == 3, "the prologue issues PF tiles");
+            mul(std::integral_constant<int, 0>{}); mul(std::integral_constant<int, 1>{}); mul(std::integral_constant<int, 2>{});
+            mul(std::integral_constant<int, 3>{}); mul(std::integral_constant<int, 4>{}); mul(std::integral_constant<int, 5>{});
+            mul(std::integral_constant<int, 6>{}); mul(std::integral_constant<int, 7>{});
+            if (p.red) {
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
+                    const float c = cs[b] + __shfl_xor(cs[b], 32, 64);       // the two row halves of the accumulator layout
+                    if (lh == 0) p.red[((int64_t)cur.z * p.redrows + 2 * (cur.m0 / BM) + (w >> 1)) * p.N + cur.n0 + wn + 32 * b + li] = c;
+                }
+            }
+            amax_publish_wave(cmx, p.amaxC);                         // one conditional atomic per wave and item (a maximum carried across the K loops was spilled)
+            // phase B
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) {
+            for (int b = 0; b < 2; ++b) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = acc[a][b][e];
-                        float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
+                for (int a = 0; a < 4; ++a) {
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const float4 t = rdp[g * 8 * 10];
-                            typedef float f4v __attribute__((ext_vector_type(4)));
-                            __builtin_nontemporal_store(f4v{t.x, t.y, t.z, t.w}, reinterpret_cast<f4v*>(q + (int64_t)(8 * g) * p.ldc));
-                        }
+                    for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = acc[a][b][e];
+                    float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const float4 t = rdp[g * 8 * 10];
+                        typedef float f4v __attribute__((ext_vector_type(4)));
+                        __builtin_nontemporal_store(f4v{t.x, t.y, t.z, t.w}, reinterpret_cast<f4v*>(q + (int64_t)(8 * g) * p.ldc));
                     }
                 }
-                continue;
             }
-            if (full_m && cur.n0 + BN <= p.N && act != 2) {
-                // whole tiles: every 32 x 32 tile is turned through a wave-private 5 KB LDS scratch (rows of 40 words: the two half-waves of a
-                // dword write hit disjoint banks) and leaves as FOUR 16-byte-per-lane stores of eight whole 128-byte lines each - 32 store
-                // instructions per wave and tile instead of 128: a wave may have 63 vector-memory operations in flight, and with four
-                // consumer waves 128 dword stores each stalled on that limit (160 of 415 us at 66 752 x 2048 x 384).
-                // Scratch: the third A plane of the stages, which mode 2 does not use (waves 0, 1 in stage 0's, 2, 3 in stage 1's).
+        } else {
+            // ---- head: C = a = elu(product + bias), row dots of a with the output layer's weights (aux)
+            float* C = p.C + (int64_t)cur.z * p.sC;
+            const bool full_m = cur.m0 + BM <= p.M;
+            if (full_m && cur.n0 + BN <= p.N) {
+                // whole tiles through the wave's LDS scratch, as in the plain epilogue
                 char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
                 float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
                 const float4* rdp = reinterpret_cast<const float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
-                // one 32 x 32 tile (row tile a, column block b).  In the transposed form a lane holds rows 8 g + (lane >> 3), columns 4 (lane & 7) .. + 3.
-                // DACT: yv = the four float4 of Y at those places (requested before the tile is turned), cs += the lane's share of the column sums;
-                // HEAD: w3 = the output layer's weights of the lane's four columns, qr[g] += the lane's share of the row dots
-                auto tile = [&](int a, int b, const float4 (&yv)[4], float4& cs, const float4& w3, float (&qr)[4]) {
+                // one 32 x 32 tile (row tile a, column block b).  In the turned form a lane holds rows 8 g + (lane >> 3), columns 4 (lane & 7) .. + 3:
+                // w3 = the output layer's weights of the lane's four columns, qr[g] += the lane's share of the row dots
+                auto tile = [&](int a, int b, const float4& w3, float (&qr)[4]) {
                     float v[16];
 #pragma unroll
                     for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
-                    if (act == 1) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
-                    }
-                    if (act == 3) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
-                    }
-                    if (p.amaxC.slot && !DACT) {
+                    for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
+                    if (p.amaxC.slot) {
 #pragma unroll
                         for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
                     }
@@ -1165,14 +1157,8 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        float4 t = rdp[g * 8 * 10];                         // rows 8 g + (lane >> 3): 8 rows x 160 bytes = 80 float4
-                        if (DACT) {
-                            t.x *= yv[g].x > 0.f ? 1.f : yv[g].x + 1.f; t.y *= yv[g].y > 0.f ? 1.f : yv[g].y + 1.f;
-                            t.z *= yv[g].z > 0.f ? 1.f : yv[g].z + 1.f; t.w *= yv[g].w > 0.f ? 1.f : yv[g].w + 1.f;
-                            cs.x += t.x; cs.y += t.y; cs.z += t.z; cs.w += t.w;
-                            if (p.amaxC.slot) cmax = amax4(cmax, t);
-                        }
-                        if (HEAD) qr[g] += (t.x * w3.x + t.y * w3.y) + (t.z * w3.z + t.w * w3.w);
+                        float4 t = rdp[g * 8 * 10];
+                        qr[g] += (t.x * w3.x + t.y * w3.y) + (t.z * w3.z + t.w * w3.w);
                         if (p.ntst) {                                       // streaming stores (RESEL_GEMM_NT): -4 % on the kernel alone at N = 2048
                             typedef float f4v __attribute__((ext_vector_type(4)));
                             __builtin_nontemporal_store(f4v{t.x, t.y, t.z, t.w}, reinterpret_cast<f4v*>(q + (int64_t)(8 * g) * p.ldc));
@@ -1181,50 +1167,32 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                         }
                     }
                 };
-                if constexpr (EPI == 0) {
-                    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float4 nov[4] = {z4, z4, z4, z4};
-                    float4 ncs = z4;
-                    float nq[4] = {0.f, 0.f, 0.f, 0.f};
+                // row tiles outermost: the row dots of a tile's 32 rows complete after its two column blocks (4 registers instead of 16)
+                float4 w3[2];
 #pragma unroll
-                    for (int b = 0; b < 2; ++b)
+                for (int b = 0; b < 2; ++b) w3[b] = ld4(p.aux + (int64_t)cur.z * p.sAux + cur.n0 + wn + 32 * b + 4 * (lane & 7));
 #pragma unroll
-                        for (int a = 0; a < 4; ++a) tile(a, b, nov, ncs, z4, nq);
-                } else {
-                    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    {
-                        // row tiles outermost: the row dots of a tile's 32 rows complete after its two column blocks (4 registers instead of 16)
-                        const float4 nov[4] = {z4, z4, z4, z4};
-                        float4 ncs = z4, w3[2];
+                for (int a = 0; a < 4; ++a) {
+                    float qr[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                        for (int b = 0; b < 2; ++b) w3[b] = ld4(p.aux + (int64_t)cur.z * p.sAux + cur.n0 + wn + 32 * b + 4 * (lane & 7));
+                    for (int b = 0; b < 2; ++b) tile(a, b, w3[b], qr);
+                    // fold the eight column groups (lane bits 0..2): lanes with (lane & 7) == 0 hold a row's dot
+                    float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M + cur.m0 + wm + 32 * a + (lane >> 3);
 #pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            float qr[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) tile(a, b, nov, ncs, w3[b], qr);
-                            // fold the eight column groups (lane bits 0..2): lanes with (lane & 7) == 0 hold a row's dot
-                            float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M + cur.m0 + wm + 32 * a + (lane >> 3);
-#pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                float r = qr[g];
-                                r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64); r += __shfl_xor(r, 4, 64);
-                                if ((lane & 7) == 0) qp[8 * g] = r;
-                            }
-                        }
+                    for (int g = 0; g < 4; ++g) {
+                        float r = qr[g];
+                        r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64); r += __shfl_xor(r, 4, 64);
+                        if ((lane & 7) == 0) qp[8 * g] = r;
                     }
                 }
                 continue;
             }
-            // edge tiles (and the accumulating form): the accumulator layout goes out as it is - column n = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2)
-            float cs1[2] = {0.f, 0.f};
+            // edge tiles: the accumulator layout goes out as it is - column n = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2)
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 float qe[16];
-                if (HEAD) {
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) qe[e] = 0.f;
-                }
+                for (int e = 0; e < 16; ++e) qe[e] = 0.f;
                 const int mb = cur.m0 + wm + 32 * a + 4 * lh;
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -1233,38 +1201,12 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     float v[16];
 #pragma unroll
                     for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
-                    if (act == 1) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
-                    }
-                    if (act == 3) {
+                    for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
+                    const float w3 = p.aux[(int64_t)cur.z * p.sAux + n];
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
-                    }
-                    if (DACT) {
-                        const float* yrow = p.aux + (int64_t)cur.z * p.sAux + (int64_t)mb * p.ldaux + n;
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int dm = (e & 3) + 8 * (e >> 2);
-                            float y = 0.f;
-                            if (mb + dm < p.M) y = yrow[(int64_t)dm * p.ldaux]; else v[e] = 0.f;      // rows past M hold row 0's products: not part of the column sums
-                            v[e] *= y > 0.f ? 1.f : y + 1.f;
-                            cs1[b] += v[e];
-                        }
-                    }
-                    if (HEAD) {
-                        const float w3 = p.aux[(int64_t)cur.z * p.sAux + n];
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) qe[e] += v[e] * w3;
-                    }
+                    for (int e = 0; e < 16; ++e) qe[e] += v[e] * w3;
                     float* crow = C + (int64_t)mb * p.ldc + n;
-                    if (act == 2) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int dm = (e & 3) + 8 * (e >> 2);
-                            if (mb + dm < p.M) v[e] += crow[(int64_t)dm * p.ldc];
-                        }
-                    }
                     if (full_m) {
 #pragma unroll
                         for (int e = 0; e < 16; ++e) crow[(int64_t)((e & 3) + 8 * (e >> 2)) * p.ldc] = v[e];
@@ -1280,24 +1222,14 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                         for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
                     }
                 }
-                if (HEAD) {                                                 // a row's 32 columns of a block sit in the 32 lanes of a half-wave
-                    float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M;
+                float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M;     // a row's 32 columns of a block sit in the 32 lanes of a half-wave
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        float r = qe[e];
+                for (int e = 0; e < 16; ++e) {
+                    float r = qe[e];
 #pragma unroll
-                        for (int o = 1; o < 32; o <<= 1) r += __shfl_xor(r, o, 64);
-                        const int m = mb + (e & 3) + 8 * (e >> 2);
-                        if (li == 0 && m < p.M) qp[m] = r;
-                    }
-                }
-            }
-            if (DACT && p.red) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int n = cur.n0 + wn + 32 * b + li;
-                    const float c = cs1[b] + __shfl_xor(cs1[b], 32, 64);     // the two row halves of the accumulator layout
-                    if (lh == 0 && n < p.N) p.red[((int64_t)cur.z * 2 * p.mt + 2 * (cur.m0 / BM) + (w >> 1)) * p.N + n] = c;
+                    for (int o = 1; o < 32; o <<= 1) r += __shfl_xor(r, o, 64);
+                    const int m = mb + (e & 3) + 8 * (e >> 2);
+                    if (li == 0 && m < p.M) qp[m] = r;
                 }
             }
         }

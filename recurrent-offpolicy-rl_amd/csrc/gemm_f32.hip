@@ -444,13 +444,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
         }
         // epilogue: D layout col = lane & 31 (n), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (m)
         if (cur.split) {                                            // partial sums: dense 128 x 128 slab tile
-            float* o = p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) o[(32 * a + (e & 3) + 8 * (e >> 2)) * BN + 32 * b] = acc[a][b][e];
+            slab_store<BN>(p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li, acc);
         } else {
             float* C = p.C + (int64_t)cur.z * p.sC;
             const bool full_m = cur.m0 + BM <= p.M;

@@ -15,6 +15,18 @@ constexpr int BK = 32;                 // K step of every kernel that walks thes
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : fast_exp(x) - 1.f; }
 
+// Partial sums of a K slice: the wave's NA x 2 accumulator tiles (D layout: column = lane & 31, rows (e & 3) + 8 (e >> 2) + 4 (lane >> 5))
+// -> the item's dense slab tile of BN columns; o = the lane's place in the wave's first tile.  gemm_ws_kernel keeps its own copy.
+template <int BN, typename ACC, int NA>
+__device__ __forceinline__ void slab_store(float* o, const ACC (&acc)[NA][2]) {
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[(32 * a + (e & 3) + 8 * (e >> 2)) * BN + 32 * b] = acc[a][b][e];
+}
+
 // tile t (member-major) -> member z, tile origin (m0, n0).  XCD-aware: the tiles of one XCD (ids congruent mod 8) walk the
 // n-tiles of one m-tile after another.
 template <int BM, int BN, typename P>

@@ -16,9 +16,41 @@ import torch.nn as nn
 from ..hip import ops
 
 
-def _unit(t):
-    """t with unit stride along its last axis (what `ops.gemm_f32` describes by row / member strides); a copy only for exotic views."""
-    return t if t.stride(-1) == 1 else t.contiguous()
+_unit = ops._unit
+
+
+def _shared_fwd(x2, weight, bias, act, ax):
+    """Shared-input layer, ONE GEMM [M, in] x [in, E*out] with bias / ELU in its epilogue (837 us against the library's 995 at
+    66 752 x 384 -> 2048) -> x2 with unit column stride, w_cat [in, E*out], y2 [M, E*out], the magnitude handle of x2."""
+    E, n_in, n_out = weight.shape
+    w_cat = weight.permute(1, 0, 2).reshape(n_in, E * n_out)                     # weights only: tiny copy
+    x2 = _unit(x2)
+    y2 = ops.gemm_f32(x2, w_cat, True, False, None if bias is None else bias.reshape(E * n_out), act, amax_a=ax,
+                      amax_b=ops.weight_amax(weight))                  # w_cat holds the same values as the parameter
+    return x2, w_cat, y2, ax if ax is not None else ops.amax_of(x2)
+
+
+def _shared_grads(g2, x2, w_cat, E, ax, part, need_x, need_w, need_part):
+    """Of a shared-input layer with output gradient g2 [M, E*out]: dX = g2 w_cat^T (sums over the ensemble), dW [E, in, out] = x2^T g2
+    (ax: the live handle of x2) and, for part = (col0, k, shape), the column block col0 .. col0 + k of dX alone."""
+    dx = ops.gemm_f32(g2, w_cat, True, True) if need_x else None
+    dw = None
+    if need_w:
+        dw = ops.gemm_f32(x2, g2, False, False, amax_a=ax).view(w_cat.shape[0], E, -1).permute(1, 0, 2)
+    dpart = None
+    if part is not None and need_part:
+        col0, k, shape = part
+        dpart = ops.gemm_f32(g2, w_cat[col0:col0 + k], True, True).view(shape)
+    return dx, dw, dpart
+
+
+def _head_grads(gq, a, w3v, need_b3):
+    """Of q = a w3 + b3 with a = elu(.) [E, M, H]: gy = gq w3 elu'(a) (tagged with its magnitude), db2 [E, 1, H], dw3 [E, H, 1], db3."""
+    E, M, H = a.shape
+    gq2 = gq.reshape(E, M)
+    gy, db2, dw3 = ops.ensemble_head_bwd(gq2, a, w3v)
+    db3 = gq2.sum(dim=1).view(E, 1, 1) if need_b3 else None
+    return gy, db2.view(E, 1, H), dw3.view(E, H, 1), db3
 
 
 class _SharedInput(torch.autograd.Function):
@@ -30,12 +62,7 @@ class _SharedInput(torch.autograd.Function):
     def forward(ctx, x2, weight, bias, act, x_part=None, col0=0, ax=None):
         """ax: magnitude handle of x2 (ops.amax_of) when the caller has one - saved tensors and reshaped views lose their tags."""
         E, n_in, n_out = weight.shape
-        w_cat = weight.permute(1, 0, 2).reshape(n_in, E * n_out)                 # [in, E*out] (weights only: tiny copy)
-        x2 = x2 if x2.stride(-1) == 1 else x2.contiguous()
-        # bias + ELU in the GEMM's epilogue (837 us against the library's 995 at 66 752 x 384 -> 2048)
-        y2 = ops.gemm_f32(x2, w_cat, True, False, None if bias is None else bias.reshape(E * n_out), act, amax_a=ax,
-                          amax_b=ops.weight_amax(weight))              # w_cat holds the same values as the parameter
-        ax = ax if ax is not None else ops.amax_of(x2)
+        x2, w_cat, y2, ax = _shared_fwd(x2, weight, bias, act, ax)
         ctx.save_for_backward(x2, w_cat, y2 if act is not None else None)
         ctx.ax = ops.keep_handles(ax)[0]
         ctx.dims = (E, n_in, n_out, bias is not None, act)
@@ -46,25 +73,14 @@ class _SharedInput(torch.autograd.Function):
     def backward(ctx, g):
         x2, w_cat, y2 = ctx.saved_tensors
         E, n_in, n_out, has_bias, act = ctx.dims
+        need = ctx.needs_input_grad
         g2 = g.transpose(0, 1).reshape(-1, E * n_out)                             # a view when g kept y's strides
-        need_db = has_bias and ctx.needs_input_grad[2]
+        need_db = has_bias and need[2]
         if act is not None:
             g2, db = ops.bias_act_bwd(g2, y2, g2.shape[0], act, need_db)
         else:
             db = g2.sum(dim=0, keepdim=True) if need_db else None
-        g2 = g2 if g2.stride(-1) == 1 else g2.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:                                               # sums over the ensemble
-            dx = ops.gemm_f32(g2, w_cat, True, True)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = ops.gemm_f32(x2, g2, False, False, amax_a=ops.handle_alive(ctx.ax))
-            dw = dw.view(n_in, E, n_out).permute(1, 0, 2)
-        dpart = None
-        if ctx.part is not None and ctx.needs_input_grad[4]:
-            col0, k, shape = ctx.part
-            wp = w_cat[col0:col0 + k]
-            dpart = ops.gemm_f32(g2, wp, True, True).view(shape)
+        dx, dw, dpart = _shared_grads(_unit(g2), x2, w_cat, E, ops.handle_alive(ctx.ax), ctx.part, need[0], need[1], need[4])
         return dx, dw, None if db is None else db.view(E, 1, n_out), None, dpart, None, None
 
 
@@ -140,13 +156,10 @@ class _Head(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gq):
         x3, w2, w3v, a = ctx.saved_tensors
-        E, M, H = a.shape
-        gq2 = gq.reshape(E, M)
-        gy, db2, dw3 = ops.ensemble_head_bwd(gq2, a, w3v)
+        gy, db2, dw3, db3 = _head_grads(gq, a, w3v, ctx.has_b3)
         dx = _member_dgrad(gy, w2, x3) if ctx.needs_input_grad[0] else None
         dw2 = _member_wgrad(x3, gy, ops.handle_alive(ctx.ax))
-        db3 = gq2.sum(dim=1).view(E, 1, 1) if ctx.has_b3 else None
-        return dx, dw2, db2.view(E, 1, H), dw3.view(E, H, 1), db3, None
+        return dx, dw2, db2, dw3, db3, None
 
 
 class _CriticMLP(torch.autograd.Function):
@@ -164,9 +177,7 @@ class _CriticMLP(torch.autograd.Function):
         E, n_in, H1 = W1.shape
         H2 = W2.shape[2]
         M = x2.shape[0]
-        w_cat = W1.permute(1, 0, 2).reshape(n_in, E * H1)                          # [in, E H1] (weights only: tiny copy)
-        y2 = ops.gemm_f32(x2, w_cat, True, False, b1.reshape(E * H1), 'elu', amax_a=ax, amax_b=ops.weight_amax(W1))
-        h_x = ax if ax is not None else ops.amax_of(x2)
+        x2, w_cat, y2, h_x = _shared_fwd(x2, W1, b1, 'elu', ax)
         h_a1 = ops.amax_of(y2)
         a1 = y2.view(M, E, H1).transpose(0, 1)                                     # [E, M, H1] view of the shared layer's output
         w3v = W3.reshape(E, H2)
@@ -174,35 +185,26 @@ class _CriticMLP(torch.autograd.Function):
                                   amax_b=ops.weight_amax(W2))
         ctx.save_for_backward(x2, w_cat, y2, W2, w3v, a2)
         ctx.handles = ops.keep_handles(h_x, h_a1)
-        ctx.dims = (E, n_in, H1, H2, M, b3 is not None)
+        ctx.dims = (E, H1, M, b3 is not None)
         ctx.part = None if x_part is None else (col0, x_part.shape[-1], tuple(x_part.shape))
         return q.view(E, M, 1)
 
     @staticmethod
     def backward(ctx, gq):
         x2, w_cat, y2, W2, w3v, a2 = ctx.saved_tensors
-        E, n_in, H1, H2, M, has_b3 = ctx.dims
+        E, H1, M, has_b3 = ctx.dims
         h_x, h_a1 = ops.live_handles(ctx.handles)
         need = ctx.needs_input_grad
-        gq2 = gq.reshape(E, M)
-        gy2, db2, dw3 = ops.ensemble_head_bwd(gq2, a2, w3v)                        # gy2 [E, M, H2] = gq w3 elu'(a2); tagged with its magnitude
+        gy2, db2, dw3, db3 = _head_grads(gq, a2, w3v, has_b3 and need[6])          # gy2 [E, M, H2] = gq w3 elu'(a2)
         a1 = y2.view(M, E, H1).transpose(0, 1)
         dw2 = _member_wgrad(a1, gy2, h_a1) if need[3] else None
-        db3 = gq2.sum(dim=1).view(E, 1, 1) if (has_b3 and need[6]) else None
         g1 = torch.empty(M, E, H1, dtype=torch.float32, device=x2.device).transpose(0, 1)      # written in the shared layer's [M, E H1] layout
         _, db1 = ops.gemm_f32_dact(gy2, W2, True, a1, g1, need_dbias=bool(need[2]), amax_b=ops.weight_amax(W2))
         g2 = g1.transpose(0, 1).reshape(M, E * H1)                                  # a view
         ops.tag_amax(g2, ops.amax_of(g1))
-        dx = ops.gemm_f32(g2, w_cat, True, True) if need[0] else None              # sums over the ensemble
-        dw1 = None
-        if need[1]:
-            dw1 = ops.gemm_f32(x2, g2, False, False, amax_a=h_x).view(n_in, E, H1).permute(1, 0, 2)
-        dpart = None
-        if ctx.part is not None and need[7]:
-            col0, k, shape = ctx.part
-            dpart = ops.gemm_f32(g2, w_cat[col0:col0 + k], True, True).view(shape)
-        return (dx, dw1, None if db1 is None else db1.view(E, 1, H1), dw2, db2.view(E, 1, H2) if need[4] else None,
-                dw3.view(E, H2, 1) if need[5] else None, db3, dpart, None, None)
+        dx, dw1, dpart = _shared_grads(g2, x2, w_cat, E, h_x, ctx.part, need[0], need[1], need[7])
+        return (dx, dw1, None if db1 is None else db1.view(E, 1, H1), dw2, db2 if need[4] else None, dw3 if need[5] else None, db3, dpart,
+                None, None)
 
 
 def critic_mlp_fusable(l0, act0, l1, act1, l2, act2, x) -> bool:
