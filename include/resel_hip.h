@@ -553,6 +553,16 @@ int resel_colsum_bf16(const uint16_t* x, int64_t ld, int M, int N, float* out, v
 int resel_gather_trajs(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows, int Tp,
                        int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
                        float* out, resel_stream_t stream);
+/* The same gather with a SELECTION of loss positions (randomised loss masks, reference nested_replay_memory.py:165-168: the host
+ * draws which positions of each sampled trajectory keep their loss mask and ships the result with the plan).
+ * sel [sel_words] int32 = [off_0 ... off_{nseg-1} | bitmap words]: off_s is the index of segment s's first bitmap word relative
+ * to the start of the words part; bit (p & 31) of word off_s + (p >> 5) is 1 where data position p (0 ... length - skip - 1) of
+ * segment s keeps its stored mask and 0 where its mask column becomes 0.  The validity column (W) receives the stored mask either
+ * way.  A dropped plan entry never reads `sel`; a segment whose bitmap would reach outside the sel_words - nseg words keeps all
+ * its masks.  sel == NULL: exactly the gather above (which forwards here).  sel_words < nseg is RESEL_EINVAL. */
+int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows, int Tp,
+                           int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
+                           const int* sel, int sel_words, float* out, resel_stream_t stream);
 
 /* ---- one-token rollout step (T = 1): the policy forward between updates -------------------------------------------
  * Reference: the outer loop calls policy.forward once per environment step (algorithm/sac.py:319-326), which reaches

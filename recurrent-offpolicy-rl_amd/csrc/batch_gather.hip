@@ -7,7 +7,9 @@
 //   init     out[r, t, :] = 0, start = 1                      (padding is "start" everywhere)
 //   segments slots [pos, pos+skip-1): start = 1; slot pos+skip-1 (PRE-STEP): next_state <- s_0, reward <- r_in0,
 //            state <- last_state_0 (column pairs passed by the host), start = 1; slots [pos+skip, pos+n): the transitions,
-//            validity column W <- their mask
+//            validity column W <- their mask; with a selection bitmap (`sel`, randomised loss masks: the host draws which positions
+//            keep their loss mask - reference :165-168 - and ships one bit per data position with the plan) the mask column of a
+//            position whose bit is 0 becomes 0, validity keeps the stored mask
 //   flags    column W+1 = validity extended one slot earlier, column W+2 = start with the last 1 before data cleared
 //            (the target pass's flags, reference sac_full_length_rnn_ensembleQ.py:338-342), done <- 0 where timeout > 0
 // One float per thread along the contiguous column axis: every wave access is a fully used row segment.
@@ -22,10 +24,10 @@ __global__ void gather_init_kernel(float* __restrict__ out, int64_t ntok, int WO
     out[i] = (int)(i % WO) == c_start ? 1.f : 0.f;
 }
 
-// grid = (ceil(maxlen * W / 256), nseg)
+// grid = (ceil(maxlen * W / 256), nseg); sel (or null) = [nseg word offsets | bitmap words], sel_words ints in all
 __global__ void gather_segments_kernel(const float* __restrict__ buffer, int W, int64_t capacity, const int* __restrict__ seg, int skip,
                                        int rows, int Tp, int c_mask, int c_start, const int* __restrict__ pre_pairs, int npairs,
-                                       float* __restrict__ out) {
+                                       const int* __restrict__ sel, int sel_words, float* __restrict__ out) {
     const int4 sg = reinterpret_cast<const int4*>(seg)[blockIdx.y];       // row, pos, n, first transition
     // a plan entry that does not fit the output / the ring is dropped (its slots stay padding) instead of written out of bounds
     if (sg.x < 0 || sg.x >= rows || sg.y < 0 || sg.z < skip || (int64_t)sg.y + sg.z > Tp || sg.w < 0 ||
@@ -37,8 +39,18 @@ __global__ void gather_segments_kernel(const float* __restrict__ buffer, int W, 
     float* dst = out + ((int64_t)sg.x * Tp + sg.y + i) * WO;
     if (i >= skip) {
         const float v = buffer[(int64_t)(sg.w + i - skip) * W + col];
-        dst[col] = v;
-        if (col == c_mask) dst[W] = v;
+        float m = v;
+        if (col == c_mask) {
+            dst[W] = v;
+            if (sel) {
+                // a bitmap that would reach outside the words part keeps every mask of its segment instead of reading out of bounds
+                const int nseg = (int)gridDim.y, p = i - skip, off = sel[blockIdx.y];
+                if (off >= 0 && (int64_t)off + ((sg.z - skip + 31) >> 5) <= (int64_t)sel_words - nseg &&
+                    !((sel[nseg + off + (p >> 5)] >> (p & 31)) & 1))
+                    m = 0.f;
+            }
+        }
+        dst[col] = m;
     } else if (i == skip - 1) {
         float v = col == c_start ? 1.f : 0.f;
         const float* first = buffer + (int64_t)sg.w * W;
@@ -69,20 +81,27 @@ __global__ void gather_flags_kernel(float* __restrict__ out, int rows, int Tp, i
 
 }  // namespace
 
-extern "C" int resel_gather_trajs(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows, int Tp,
-                                  int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
-                                  float* out, resel_stream_t stream) {
+extern "C" int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows,
+                                      int Tp, int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
+                                      const int* sel, int sel_words, float* out, resel_stream_t stream) {
     if (!buffer || !segments || !out || W <= 0 || capacity <= 0 || nseg <= 0 || max_len <= 0 || skip < 1 || rows <= 0 || Tp <= 0) return RESEL_EINVAL;
     if (c_mask < 0 || c_mask >= W || c_start < 0 || c_start >= W || c_done < 0 || c_done >= W || c_timeout >= W || (npairs > 0 && !pre_pairs))
         return RESEL_EINVAL;
-    if (!aligned16(segments)) return RESEL_EINVAL;
+    if (!aligned16(segments) || (sel && sel_words < nseg)) return RESEL_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int WO = W + 3;
     const int64_t ntok = (int64_t)rows * Tp;
     hipLaunchKernelGGL(gather_init_kernel, dim3((unsigned)((ntok * WO + 255) / 256)), dim3(256), 0, s, out, ntok, WO, c_start);
     hipLaunchKernelGGL(gather_segments_kernel, dim3((unsigned)(((int64_t)max_len * W + 255) / 256), nseg), dim3(256), 0, s, buffer, W,
-                       capacity, segments, skip, rows, Tp, c_mask, c_start, pre_pairs, npairs, out);
+                       capacity, segments, skip, rows, Tp, c_mask, c_start, pre_pairs, npairs, sel, sel_words, out);
     hipLaunchKernelGGL(gather_flags_kernel, dim3((unsigned)((ntok + 255) / 256)), dim3(256), 0, s, out, rows, Tp, W, c_start, c_done,
                        c_timeout);
     return launch_status();
+}
+
+extern "C" int resel_gather_trajs(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows, int Tp,
+                                  int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
+                                  float* out, resel_stream_t stream) {
+    return resel_gather_trajs_sel(buffer, W, capacity, segments, nseg, max_len, skip, rows, Tp, c_mask, c_start, c_done, c_timeout, pre_pairs,
+                                  npairs, nullptr, 0, out, stream);
 }

@@ -3,7 +3,9 @@
 
 What varies from update to update is moved OUT of the captured region into static buffers that the host refreshes before each replay:
   * the sampling plan - the host half of `sample_trajs_device` (trajectory choice, numpy RNG, packing plan) runs as in the eager update
-    and writes the int32 plan into a pinned buffer; the graph holds the H2D copy node and the gather kernel;
+    and writes the int32 plan into a pinned buffer; the graph holds the H2D copy node and the gather kernel; with randomised loss masks
+    (`randomize_mask`) the plan's selection of loss positions (`sel`, nested_replay_memory.py) travels the same way into a static
+    buffer of fixed capacity, so the gather node's arguments never vary;
   * the REDQ critic subset - drawn on the host from the same numpy stream as the eager update, copied into static index tensors;
   * the step-dependent AdamW factors - `FlatAdamW.prepare_step()` (device-resident bias corrections), torch's `capturable` AdamW for
     the entropy coefficient;
@@ -47,8 +49,9 @@ fallback through `step()` draws exactly what a replay would.
 Gradient clipping (reference :239-250, 274-287) stays on the device: norm -> coefficient -> the scale word the flat AdamW kernel reads.
 Data-parallel groups: the recording is CUT at each gradient exchange (`cut`) - an update is then three graphs replayed back to back with
 the two all-reduces issued eagerly between them on the same stream (works with every backend; nothing waits on the host).
-Refused at construction (use the eager `train_one_batch`): utd != 1, randomised masks / truncation, the three-phase Q-guard exchange
-(RESEL_DP_GUARD=allreduce)."""
+Randomised loss masks change the values of one column and no shape or launch; random truncation changes batch shapes like any ragged
+workload (exact keys: most of its updates fall to `step()`'s eager launch; buckets absorb it).
+Refused at construction (use the eager `train_one_batch`): utd != 1, the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce)."""
 import os
 from collections import OrderedDict
 
@@ -157,10 +160,14 @@ class GraphedUpdate:
                 st['step'] = st['step'].to(self.device)
         self._plan_dev = torch.empty((self.PLAN_CAPACITY, 4), dtype=torch.int32, device=self.device)
         self._log_dev = torch.zeros(64, dtype=torch.float32, device=self.device)    # static target of the graph's log node
+        # randomised loss masks: one word offset per plan entry + the bitmap words of every entry at the ring's row capacity
+        self._sel_capacity = self.PLAN_CAPACITY * (1 + (alg.replay_buffer.max_traj_step + 31) // 32) if alg.parameter.randomize_mask else 0
+        self._sel_dev = torch.zeros(self._sel_capacity, dtype=torch.int32, device=self.device) if self._sel_capacity else None
         self._ring = [dict(plan=torch.empty((self.PLAN_CAPACITY, 4), dtype=torch.int32, pin_memory=True),
                            sub=torch.empty(self.subset_np.size, dtype=torch.int32, pin_memory=True),
                            bc=torch.empty(4, dtype=torch.float32, pin_memory=True),
                            log=torch.empty(64, dtype=torch.float32, pin_memory=True),
+                           sel=torch.empty(self._sel_capacity, dtype=torch.int32, pin_memory=True) if self._sel_capacity else None,
                            evt=torch.cuda.Event(), used=False, handed=None) for _ in range(self.RING)]
         self._turn = 0
         self._slot = self._ring[0]
@@ -238,8 +245,8 @@ class GraphedUpdate:
             return 'not a full-trajectory trainer'
         if alg.grad_sync.active and os.environ.get('RESEL_DP_GUARD', 'bucket') == 'allreduce':
             return 'the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce) issues collectives inside the target computation'
-        if par.utd != 1 or par.randomize_mask or par.random_trunc_traj:
-            return 'utd != 1 or randomised masks / truncation change the launch sequence from update to update'
+        if par.utd != 1:
+            return 'utd != 1'
         if not (getattr(alg, 'device_replay', False) and alg.replay_buffer.device_supported(randomize_mask=par.randomize_mask)):
             return 'needs the device-resident replay ring'
         return None
@@ -248,7 +255,9 @@ class GraphedUpdate:
     def gather(self):
         pl = self._plan
         n = pl['seg'].shape[0]
-        dev = self.alg.replay_buffer.gather_planned(self.device, self._plan_dev[:n], pl['max_len'], pl['nrow'], pl['longest'])
+        # the whole static selection buffer: its capacity, not this plan's size, is the `sel_words` baked into the graph node
+        dev = self.alg.replay_buffer.gather_planned(self.device, self._plan_dev[:n], pl['max_len'], pl['nrow'], pl['longest'],
+                                                    sel_dev=self._sel_dev)
         return dev, pl['total_size'], pl['table']
 
     def cut(self, exchange):
@@ -295,7 +304,8 @@ class GraphedUpdate:
     def _prepare(self):
         alg, par = self.alg, self.alg.parameter
         pl = alg.replay_buffer.plan_trajs_device(par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj,
-                                                 nest_stack_trajs=alg.allow_nest_stack, buckets=self.buckets == 'on')
+                                                 nest_stack_trajs=alg.allow_nest_stack, buckets=self.buckets == 'on',
+                                                 randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized)
         built = None
         if self.buckets == 'auto':
             if self._drop_base is not None and self.seq_buckets:            # the exact key of attention layers holds the table sizes too
@@ -307,6 +317,9 @@ class GraphedUpdate:
         n = pl['seg'].shape[0]
         if n > self.PLAN_CAPACITY:
             raise RuntimeError(f'GraphedUpdate: {n} plan segments exceed the static plan buffer ({self.PLAN_CAPACITY})')
+        n_sel = pl['sel'].size if 'sel' in pl else 0
+        if n_sel > self._sel_capacity:
+            raise RuntimeError(f'GraphedUpdate: {n_sel} selection words exceed the static selection buffer ({self._sel_capacity})')
         # bucketed: `max_len` is the row length (it only sizes the gather grid)
         key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else (pl['nrow'], pl['longest'], pl['max_len'], n)
         if self._drop_base is not None and built is None:
@@ -325,6 +338,9 @@ class GraphedUpdate:
             key = key + self._prepare_seqs(built)
         slot['plan'].numpy()[:n] = pl['seg']
         self._plan_dev[:n].copy_(slot['plan'][:n], non_blocking=True)        # stream-ordered: behind the previous update's gather
+        if n_sel:
+            slot['sel'].numpy()[:n_sel] = pl['sel']
+            self._sel_dev[:n_sel].copy_(slot['sel'][:n_sel], non_blocking=True)
         self._plan = pl
         sub = np.ascontiguousarray(np.asarray(self._draw(self.E)), dtype=np.int32)
         slot['sub'].numpy()[...] = sub

@@ -510,7 +510,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
                     raise RuntimeError('shape_buckets: ' + NO_SEQ_BUCKETS)
                 dev, batch_size, table = self.replay_buffer.sample_trajs_device(
                     self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack,
-                    buckets=self.shape_buckets)
+                    buckets=self.shape_buckets, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized)
                 real_rows = self.replay_buffer._last_real_rows
                 self.timer.register_end(level=2)
                 b = self._batch_views(dev, table)

@@ -138,10 +138,12 @@ class NestedMemoryArray(MemoryArray):
         return result, total_size, valid, traj_len_array
 
     # ------------------------------------------------------------------ device-resident variant
-    def device_supported(self, randomize_mask=False, **_):
-        """The device packer covers every sampling mode whose randomness lives in the PLAN (which trajectories, truncated
-        lengths, row packing); per-transition mask randomisation stays on the host path."""
-        return not randomize_mask
+    def device_supported(self, randomize_mask=False, equalize_data_of_each_traj=True, **_):
+        """The device packer covers every sampling mode whose randomness lives in the PLAN: which trajectories, truncated lengths,
+        row packing, and the randomised loss mask in its equalised form (a count and one permutation per trajectory, shipped as the
+        plan's `sel` bitmap - the only form the trainers request).  The whole-batch form (`_mask_rnd_select`, which needs the packed
+        mask itself) stays on the host path."""
+        return not randomize_mask or bool(equalize_data_of_each_traj)
 
     def _mirror(self, device):
         """Device copy of the ring, refreshed for the rows written since the last call (a rollout adds one trajectory
@@ -161,11 +163,15 @@ class NestedMemoryArray(MemoryArray):
         return st['buf']
 
     def plan_trajs_device(self, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False, nest_stack_trajs=True,
-                          buckets=False):
+                          buckets=False, randomize_mask=False, valid_number_post_randomized=0):
         """Host half of `sample_trajs_device`: the same sampling decisions (and numpy RNG consumption) as `sample_trajs`.  Returns a dict
         with the int32 plan `seg` [nseg, 4] = (row, first slot, length incl. skip, first transition) and the scalars the gather needs.
         `buckets`: the same plan padded into its shape bucket (shape_buckets.py) - rows, row length and plan entries rounded up, the
-        drawn values kept in `nrow_real` / `longest_real`."""
+        drawn values kept in `nrow_real` / `longest_real`.
+        `randomize_mask`: what `sample_trajs(..., equalize_data_of_each_traj=True)` draws, draw for draw, as one more int32 array `sel` =
+        [off_0 ... off_{nseg-1} | words]: `off_s` is the index of segment s's first bitmap word relative to the words part, bit `p & 31`
+        of word `off_s + (p >> 5)` is 1 where data position p of the segment keeps its stored mask (bits behind the last position are
+        0).  Without the flag there is no `sel` key."""
         skip = self._skip_step
         if get_all:
             picked = np.arange(self.available_traj_num)
@@ -178,14 +184,24 @@ class NestedMemoryArray(MemoryArray):
         else:
             lens = [self.trajectory_length[i] + skip for i in picked]
         starts = [self.trajectory_start[i] for i in picked]
+        valid_nums = self.get_equalized_valid_num_each_traj(lens, valid_number_post_randomized) if randomize_mask else None
         groups = self.load_equalize(lens, self.max_traj_step) if nest_stack_trajs else [[i] for i in range(len(lens))]
         nrow = len(groups)
         total_size = int(sum(lens) - len(lens) * skip)
         plan, table, longest = [], [], 0
+        offs, words, nword = [], [], 0
         for r, grp in enumerate(groups):
             pos, seq = 0, [1]
             for j in grp:
                 plan.append((r, pos, lens[j], starts[j]))
+                if valid_nums is not None:
+                    zero = np.random.permutation(lens[j] - skip)[:-valid_nums[j]]      # the host path's expression, quirks included
+                    keep = np.zeros((lens[j] - skip + 31) // 32 * 32, dtype=np.uint8)
+                    keep[:lens[j] - skip] = 1
+                    keep[zero] = 0
+                    offs.append(nword)
+                    words.append(np.packbits(keep, bitorder='little').view('<u4'))
+                    nword += words[-1].size
                 seq.append(lens[j])
                 pos += lens[j]
             longest = max(longest, pos)
@@ -196,6 +212,8 @@ class NestedMemoryArray(MemoryArray):
             traj_len_array[r, :len(seq)] = seq
         seg = np.asarray(plan, dtype=np.int32)
         pl = dict(seg=seg, max_len=int(seg[:, 2].max()), nrow=nrow, longest=longest, total_size=total_size, table=traj_len_array)
+        if valid_nums is not None:
+            pl['sel'] = np.concatenate([np.asarray(offs, dtype=np.uint32)] + words).view(np.int32)
         return pad_plan(pl, self.max_traj_step) if buckets else pl
 
     def _gather_pairs(self, device):
@@ -210,30 +228,38 @@ class NestedMemoryArray(MemoryArray):
             st.update(device=device, pairs=torch.tensor(pairs, dtype=torch.int32).to(device), ring=PinnedRing(torch.int32, depth=4))
         return st
 
-    def gather_planned(self, device, seg_dev, max_len, nrow, longest):
-        """Device half: the packed batch [rows, T', W + 3] assembled on the GPU from the device mirror of the ring and the plan."""
+    def gather_planned(self, device, seg_dev, max_len, nrow, longest, sel_dev=None):
+        """Device half: the packed batch [rows, T', W + 3] assembled on the GPU from the device mirror of the ring and the plan
+        (`sel_dev`: the plan's `sel` on the device, or a longer buffer that begins with it)."""
         from ...hip import ops
         R = self.name2range
         st = self._gather_pairs(device)
         out = ops.gather_trajs(self._mirror(device), seg_dev, max_len, self._skip_step, nrow, longest, R['mask'][0], R['start'][0],
-                               R['done'][0], R['timeout'][0] if R['timeout'][1] > R['timeout'][0] else -1, st['pairs'])
+                               R['done'][0], R['timeout'][0] if R['timeout'][1] > R['timeout'][0] else -1, st['pairs'], sel=sel_dev)
         self._last_batch_shape = (nrow, longest)
         return out
 
     def sample_trajs_device(self, device, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False,
-                            nest_stack_trajs=True, buckets=False):
+                            nest_stack_trajs=True, buckets=False, randomize_mask=False, valid_number_post_randomized=0):
         """Same sampling decisions (and numpy RNG consumption) as `sample_trajs`, but the batch array is assembled on the
         device by `ops.gather_trajs` from the device mirror of the ring: returns (batch [rows, T', W + 3] on `device`,
         total_size, traj_len_array).  `buckets`: the batch padded into its shape bucket (empty rows and trailing slots are
-        `mask = 0, start = 1`); the number of rows drawn is left in `_last_real_rows`."""
+        `mask = 0, start = 1`); the number of rows drawn is left in `_last_real_rows`.  `randomize_mask`: the equalised randomised
+        loss mask of `sample_trajs`, applied by the gather from the plan's `sel`."""
         import torch
-        pl = self.plan_trajs_device(batch_size, max_sample_size, get_all, random_trunc_traj, nest_stack_trajs, buckets=buckets)
+        pl = self.plan_trajs_device(batch_size, max_sample_size, get_all, random_trunc_traj, nest_stack_trajs, buckets=buckets,
+                                    randomize_mask=randomize_mask, valid_number_post_randomized=valid_number_post_randomized)
         self._last_real_rows = pl.get('nrow_real', pl['nrow'])
-        seg = pl['seg']
+        seg, sel = pl['seg'], pl.get('sel')
         st = self._gather_pairs(device)
-        # the plan block is rewritten on every sample while earlier copies may still be queued: one event per block
-        host = st['ring'].stage(seg.size, device, 1024).view(-1, 4)
-        host.copy_(torch.from_numpy(seg))
-        seg_dev = st['ring'].upload(host, device)
-        out = self.gather_planned(device, seg_dev, pl['max_len'], pl['nrow'], pl['longest'])
+        # the plan block is rewritten on every sample while earlier copies may still be queued: one event per block; the selection
+        # rides behind the plan in the same block (one copy)
+        n_sel = 0 if sel is None else sel.size
+        host = st['ring'].stage(seg.size + n_sel, device, 1024)
+        host[:seg.size].view(-1, 4).copy_(torch.from_numpy(seg))
+        if sel is not None:
+            host[seg.size:].copy_(torch.from_numpy(sel))
+        both = st['ring'].upload(host, device)
+        seg_dev, sel_dev = both[:seg.size].view(-1, 4), (both[seg.size:] if sel is not None else None)
+        out = self.gather_planned(device, seg_dev, pl['max_len'], pl['nrow'], pl['longest'], sel_dev=sel_dev)
         return out, pl['total_size'], pl['table']

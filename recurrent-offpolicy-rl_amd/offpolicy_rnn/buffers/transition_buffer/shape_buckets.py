@@ -44,7 +44,8 @@ def pad_plan(pl, row_cap):
     """The plan of `plan_trajs_device` moved into its bucket: same sampled trajectories at the same slots; `seg` padded with (-1, 0, 0, 0)
     (dropped by the gather kernel), `table` with a row [1, 0, ...] per empty row (the leading dummy sequence every row has);
     `nrow` / `longest` / `max_len` become the bucket's (`max_len` only sizes the gather grid), the drawn values stay in `nrow_real` /
-    `longest_real`."""
+    `longest_real`.  A plan with a selection of loss positions (`sel` = [one word offset per entry | bitmap words], offsets relative to
+    the words part): the offset header is padded with zeros to the bucketed entry count, the words follow unchanged."""
     seg, table = pl['seg'], pl['table']
     rows, row_len, nseg = bucket_shape(pl['nrow'], pl['longest'], seg.shape[0], row_cap)
     # the gather kernel drops what does not fit its output: a row longer than the planner may emit must be an error here, not lost data
@@ -55,7 +56,11 @@ def pad_plan(pl, row_cap):
     table_b = np.zeros((rows, table.shape[1]), dtype=table.dtype)
     table_b[:table.shape[0]] = table
     table_b[table.shape[0]:, 0] = 1
-    return dict(pl, seg=seg_b, table=table_b, nrow=rows, longest=row_len, max_len=row_len, nrow_real=pl['nrow'], longest_real=pl['longest'])
+    out = dict(pl, seg=seg_b, table=table_b, nrow=rows, longest=row_len, max_len=row_len, nrow_real=pl['nrow'], longest_real=pl['longest'])
+    if 'sel' in pl:
+        sel, n = pl['sel'], seg.shape[0]
+        out['sel'] = np.concatenate((sel[:n], np.zeros(nseg - n, dtype=sel.dtype), sel[n:]))
+    return out
 
 
 def pad_seq_tables(built, rows, row_len):

@@ -100,6 +100,7 @@ SIGNATURES = {
     'resel_colsum_bf16_workspace_bytes': (c_size_t, [I, I]),
     'resel_colsum_bf16': (c_int, [P, L, I, I, P, P, S]),
     'resel_gather_trajs': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, S]),
+    'resel_gather_trajs_sel': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, I, P, S]),
     'resel_mamba_conv_step': (c_int, [P, L, P, L, P, L, L, L, I, P, P, P, I, I, I, I, S]),
     'resel_selective_state_update': (c_int, [P, L, P, L, P, P, L, P, P, P, P, P, L, P, I, I, I, I, S]),
     'resel_atb_workspace_bytes': (c_size_t, [L, I, I]),

@@ -1396,16 +1396,19 @@ def wgrad(gy, x2, amax_x=None):
 
 
 @torch.no_grad()
-def gather_trajs(buffer, segments, max_len, skip, rows, row_len, c_mask, c_start, c_done, c_timeout, pre_pairs):
+def gather_trajs(buffer, segments, max_len, skip, rows, row_len, c_mask, c_start, c_done, c_timeout, pre_pairs, sel=None):
     """Packed batch [rows, row_len, W + 3] from the device ring `buffer` [capacity, W] and the int32 plan `segments` [nseg, 4]
-    (row, first slot, length incl. skip, first transition); see include/resel_hip.h `resel_gather_trajs`."""
-    _need_cuda('gather_trajs', buffer, segments, pre_pairs)
+    (row, first slot, length incl. skip, first transition); see include/resel_hip.h `resel_gather_trajs`.  `sel`: the int32 selection
+    of loss positions that goes with the plan ([nseg word offsets | bitmap words], `resel_gather_trajs_sel`; it may be longer than the
+    plan needs - a static buffer)."""
+    _need_cuda('gather_trajs', buffer, segments, pre_pairs, *(() if sel is None else (sel,)))
     assert buffer.dtype == torch.float32 and buffer.is_contiguous() and segments.dtype == torch.int32 and segments.is_contiguous()
+    assert sel is None or (sel.dtype == torch.int32 and sel.dim() == 1 and sel.is_contiguous())
     W = buffer.shape[1]
     out = torch.empty(rows, row_len, W + 3, dtype=torch.float32, device=buffer.device)
-    check(lib().resel_gather_trajs(_p(buffer), W, buffer.shape[0], _p(segments), segments.shape[0], int(max_len), int(skip), int(rows), int(row_len),
-                                   int(c_mask), int(c_start), int(c_done), int(c_timeout), _p(pre_pairs), pre_pairs.shape[0], _p(out),
-                                   _stream()), 'gather_trajs')
+    check(lib().resel_gather_trajs_sel(_p(buffer), W, buffer.shape[0], _p(segments), segments.shape[0], int(max_len), int(skip), int(rows),
+                                       int(row_len), int(c_mask), int(c_start), int(c_done), int(c_timeout), _p(pre_pairs), pre_pairs.shape[0],
+                                       None if sel is None else _p(sel), 0 if sel is None else sel.numel(), _p(out), _stream()), 'gather_trajs')
     return out
 
 
