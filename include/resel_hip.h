@@ -584,7 +584,23 @@ int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const i
  *   returns softmax_j<=pos(scale q.k_j - slope_h (pos - j)) v_j as out [B, H, hd] bf16.  qkv [B, 3, H, hd] bf16 (row stride
  *   ld_qkv).  pos = *pos_dev when pos_dev != NULL (device step counter: graph replay), else pos_host.  hd in {32, 64}.
  *   pos >= max_seqlen: RESEL_EINVAL for a host position; with a device counter the output row is NaN (the reference's
- *   flash-attn asserts on a full cache). */
+ *   flash-attn asserts on a full cache).
+ * resel_attn_decode_rows: resel_attn_decode with ONE POSITION PER ROW - pos_rows [B] int32 on the device replaces pos_dev / pos_host.
+ *   Row b appends its k, v at pos_rows[b] of its own cache slab and attends over keys 0..pos_rows[b] of that slab; its arithmetic
+ *   depends on its own position only, so its output equals what resel_attn_decode gives for that row alone, bit for bit.  A row
+ *   whose position is outside [0, max_seqlen) gets the NaN pattern in its own output rows and writes nothing else; the other rows
+ *   are unaffected.  Rows of one graph replay may so be at different points of their episodes.
+ * resel_step_state_reset: the start of an episode for SOME rows of a B-row step, as one kernel (one launch, nothing else on the
+ *   stream, no allocation: capturable).  flags [B] int32 on the device, non-zero = row b starts an episode.  For every flagged row b:
+ *   zeros over base[b * row_stride .. + width) of each of the nseg <= 16 segments (fp32; row_stride >= width, in elements - state
+ *   tensors may be column views of wider rows; base 4-byte aligned) and 0 to pos[b] of each of the ncounters <= 8 int32 position
+ *   arrays (the cgpt positions above).  Unflagged rows, and the gaps between the rows of a view, are not touched.  Both tables
+ *   travel by value.  16-byte stores over the 16-byte aligned part of a row, 4-byte stores on its head and tail. */
+#define RESEL_RESET_MAX_SEGS 16
+#define RESEL_RESET_MAX_COUNTERS 8
+typedef struct { float* base; int64_t row_stride; int32_t width; } resel_reset_seg_t;
+typedef struct { resel_reset_seg_t seg[RESEL_RESET_MAX_SEGS]; } resel_reset_segs_t;
+typedef struct { int32_t* pos[RESEL_RESET_MAX_COUNTERS]; } resel_reset_counters_t;
 int resel_mamba_conv_step(const float* x, int64_t ldx, const float* state_in, int64_t ld_in, float* state_out, int64_t ld_out,
                           int64_t stride_d, int64_t stride_k, int W, const float* w, const float* bias, float* xc, int B, int Di,
                           int K, int act, resel_stream_t stream);
@@ -595,6 +611,10 @@ int resel_selective_state_update(const float* state_in, int64_t ld_in, float* st
 int resel_attn_decode(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_dev, int pos_host,
                       const float* slopes, uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen,
                       resel_stream_t stream);
+int resel_attn_decode_rows(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_rows, const float* slopes,
+                           uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen, resel_stream_t stream);
+int resel_step_state_reset(const int32_t* flags, int B, resel_reset_segs_t segs, int nseg, resel_reset_counters_t counters,
+                           int ncounters, resel_stream_t stream);
 
 /* ---- C = W^T N over a very long reduction dimension (weight gradients of the narrow Mamba projections) ----------------
  * Replaces autograd's `grad.t() @ input` of the x_proj / dt_proj F.linear calls (reference

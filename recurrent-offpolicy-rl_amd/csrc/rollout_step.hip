@@ -8,6 +8,8 @@
 //                                                                                      mamba_ssm/ops/triton/selective_state_update.py:123-154)
 //   attn_decode              KV-cache append + one causal ALiBi attention row           (flash_attn MHA with inference_params,
 //                                                                                      TransformerFlashAttention.py:76-81)
+//   attn_decode_rows         the same kernel with one cache position per row (rows at different points of their episodes)
+//   step_state_reset         zero state + position of the rows that start an episode on this step, inside the graph
 #include <hip/hip_bf16.h>
 #include "resel_common.h"
 
@@ -96,14 +98,15 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
 }
 struct alignas(16) bf16x8 { uint16_t v[8]; };
 
-template <int HD>
+// ROWS: pos_dev holds one position per row (pos_dev[b]) instead of one for all rows; the arithmetic of a row is the same either way.
+template <int HD, bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const uint16_t* __restrict__ qkv, int64_t ld_qkv, uint16_t* __restrict__ cache,
                                                           const int* __restrict__ pos_dev, int pos_host, const float* __restrict__ slopes,
                                                           uint16_t* __restrict__ out, float scale, int H, int S) {
     __shared__ float s_m[4], s_l[4], s_acc[4][HD];
     const int h = blockIdx.x, b = blockIdx.y;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pos = pos_dev ? *pos_dev : pos_host;      // tokens already in the cache == position of this token
+    const int pos = ROWS ? pos_dev[b] : (pos_dev ? *pos_dev : pos_host);      // tokens already in the cache == position of this token
     const uint16_t* qrow = qkv + (int64_t)b * ld_qkv + (int64_t)h * HD;
     const uint16_t* krow = qrow + (int64_t)H * HD;
     const uint16_t* vrow = krow + (int64_t)H * HD;
@@ -176,6 +179,26 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const uint16_t* __rest
     }
 }
 
+// ---- per-row episode start: zero the flagged rows of every state segment and position array ---------------------------
+// grid (max(nseg, 1), B), 256 threads: block (s, b) clears row b of segment s; block (0, b) also clears the positions.
+// A row is [head | 16-byte body | tail]: 4-byte stores up to the first 16-byte boundary and after the last, float4 stores between.
+__global__ __launch_bounds__(256) void state_reset_kernel(const int* __restrict__ flags, resel_reset_segs_t segs, int nseg,
+                                                          resel_reset_counters_t counters, int ncounters) {
+    const int s = blockIdx.x, b = blockIdx.y;
+    if (flags[b] == 0) return;
+    if (s == 0 && (int)threadIdx.x < ncounters) counters.pos[threadIdx.x][b] = 0;
+    if (s >= nseg) return;
+    float* row = segs.seg[s].base + (int64_t)b * segs.seg[s].row_stride;
+    const int w = segs.seg[s].width;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3u);
+    const int head = min(w, (4 - mis) & 3);
+    const int body = (w - head) >> 2;                   // float4 stores
+    for (int i = threadIdx.x; i < head; i += 256) row[i] = 0.f;
+    float4* row4 = reinterpret_cast<float4*>(row + head);
+    for (int i = threadIdx.x; i < body; i += 256) row4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = head + body * 4 + threadIdx.x; i < w; i += 256) row[i] = 0.f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,22 +226,51 @@ int resel_selective_state_update(const float* state_in, int64_t ld_in, float* st
     return launch_status();
 }
 
-int resel_attn_decode(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_dev, int pos_host, const float* slopes,
-                      uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen, resel_stream_t stream) {
+static int attn_decode_launch(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_dev, int pos_host, bool rows,
+                              const float* slopes, uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen,
+                              resel_stream_t stream) {
     if (!qkv || !kv_cache || !out) return RESEL_EINVAL;
     if (B <= 0 || H <= 0 || max_seqlen <= 0) return RESEL_EINVAL;
     if (!aligned16(qkv) || !aligned16(kv_cache) || (ld_qkv % 8) != 0) return RESEL_EINVAL;
-    if (!pos_dev && (pos_host < 0 || pos_host >= max_seqlen)) return RESEL_EINVAL;
+    if (rows ? !pos_dev : (!pos_dev && (pos_host < 0 || pos_host >= max_seqlen))) return RESEL_EINVAL;
     const dim3 grid(H, B), block(256);
     auto q = qkv;
     auto c = kv_cache;
     auto o = out;
     hipStream_t s = (hipStream_t)stream;
+#define RESEL_DECODE(HD, ROWS) \
+    hipLaunchKernelGGL((attn_decode_kernel<HD, ROWS>), grid, block, 0, s, q, ld_qkv, c, pos_dev, pos_host, slopes, o, scale, H, max_seqlen)
     switch (head_dim) {
-        case 32: hipLaunchKernelGGL(attn_decode_kernel<32>, grid, block, 0, s, q, ld_qkv, c, pos_dev, pos_host, slopes, o, scale, H, max_seqlen); break;
-        case 64: hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, s, q, ld_qkv, c, pos_dev, pos_host, slopes, o, scale, H, max_seqlen); break;
+        case 32: if (rows) RESEL_DECODE(32, true); else RESEL_DECODE(32, false); break;
+        case 64: if (rows) RESEL_DECODE(64, true); else RESEL_DECODE(64, false); break;
         default: return RESEL_EINVAL;
     }
+#undef RESEL_DECODE
+    return launch_status();
+}
+
+int resel_attn_decode(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_dev, int pos_host, const float* slopes,
+                      uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen, resel_stream_t stream) {
+    return attn_decode_launch(qkv, ld_qkv, kv_cache, pos_dev, pos_host, false, slopes, out, scale, B, H, head_dim, max_seqlen, stream);
+}
+
+int resel_attn_decode_rows(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cache, const int32_t* pos_rows, const float* slopes,
+                           uint16_t* out, float scale, int B, int H, int head_dim, int max_seqlen, resel_stream_t stream) {
+    return attn_decode_launch(qkv, ld_qkv, kv_cache, pos_rows, 0, true, slopes, out, scale, B, H, head_dim, max_seqlen, stream);
+}
+
+int resel_step_state_reset(const int32_t* flags, int B, resel_reset_segs_t segs, int nseg, resel_reset_counters_t counters, int ncounters,
+                           resel_stream_t stream) {
+    if (!flags || B <= 0 || nseg < 0 || nseg > RESEL_RESET_MAX_SEGS || ncounters < 0 || ncounters > RESEL_RESET_MAX_COUNTERS) return RESEL_EINVAL;
+    if (nseg + ncounters == 0) return RESEL_EINVAL;
+    for (int i = 0; i < nseg; ++i) {
+        const resel_reset_seg_t& g = segs.seg[i];
+        if (!g.base || g.width <= 0 || g.row_stride < g.width || (reinterpret_cast<uintptr_t>(g.base) & 3u)) return RESEL_EINVAL;
+    }
+    for (int i = 0; i < ncounters; ++i)
+        if (!counters.pos[i]) return RESEL_EINVAL;
+    hipLaunchKernelGGL(state_reset_kernel, dim3(nseg > 0 ? nseg : 1, B), dim3(256), 0, (hipStream_t)stream, flags, segs, nseg, counters,
+                       ncounters);
     return launch_status();
 }
 

@@ -1,7 +1,10 @@
 """SAC base trainer: construction (env, seeds, actor / critics, optimizers, replay buffer), the environment loop and
 checkpoint I/O (reference offpolicy_rnn/algorithm/sac.py:33-420).  The per-update work lives in the full-trajectory
-sub-classes (`train_one_batch`).  Out of scope here, as in SURVEY.md section 8: the evaluation worker pool
-(`eval_inprocess`, sac.py:285-300,364-379) - `train()` logs training returns only."""
+sub-classes (`train_one_batch`).  Evaluation (reference sac.py:284-300,364-379): at the start of every iteration `train()` runs
+`test_nprocess * test_nrollout` deterministic episodes of the current policy and logs them as `performance/EpRetTest` and
+`performance/EpLenTest` at its end.  The reference's CPU worker pool (`eval_inprocess`) has no counterpart here - this build has no
+CPU forward; the episodes run synchronously on the device instead, up to 64 environments per graph replay
+(utility/policy_eval.py `BatchedPolicyEval`, hip/graph_step.py `row_reset`)."""
 import math
 import os
 import random
@@ -86,6 +89,8 @@ class SAC:
         if self.sample_device.type == 'cuda' and os.environ.get('RESEL_GRAPH_ROLLOUT', '1') != '0' and not self.discrete_env:
             from ..hip.graph_step import GraphedPolicyStep
             self.graph_step = GraphedPolicyStep(self.policy, self.sample_device, batch_size=1)
+        self.evaluator = None                   # BatchedPolicyEval, built by the first evaluate()
+        self._eval_refusal_logged = False
         self.sample_num = 0
         self.grad_num = 0
         self.start_time = time.time()
@@ -232,9 +237,40 @@ class SAC:
             if graphed is not None:             # detach the process-wide dropout base: later eager trainers of this process draw from torch's generator again
                 graphed.close()
 
+    # ------------------------------------------------------------------------------------------ evaluation
+    def eval_refusal(self):
+        """Why `train()` does not evaluate the policy (None: it does)."""
+        if self.sample_device.type != 'cuda':
+            return 'the policy does not sample on a CUDA device (evaluation replays a hipGraph of the policy step)'
+        if self.discrete_env:
+            return 'discrete action heads are outside the graphed policy step'
+        if getattr(self.parameter, 'test_nprocess', 0) * getattr(self.parameter, 'test_nrollout', 0) <= 0:
+            return 'test_nprocess * test_nrollout is 0'
+        return None
+
+    def evaluate(self):
+        """`test_nprocess * test_nrollout` deterministic episodes of the current policy on the evaluation environment (reference
+        `eval_inprocess` / `policy_eval`, utility/sample_utility.py:38-131), min(that, 64) environments per graph replay.
+        -> {'EpRetTest': [...], 'EpLenTest': [...], ...}.  Touches no global random stream."""
+        why = self.eval_refusal()
+        if why:
+            raise RuntimeError(f'SAC.evaluate: {why}')
+        n = self.parameter.test_nprocess * self.parameter.test_nrollout
+        if self.evaluator is None:
+            from ..utility.policy_eval import BatchedPolicyEval
+            self.evaluator = BatchedPolicyEval(self.policy, lambda: make_env(self.env_name, self.env_info['seed'])['eval_env'], self.act_dim,
+                                               min(n, 64), self.sample_device, seed=self.parameter.seed,
+                                               eval_tasks=self.env_info.get('eval_tasks'))
+        return self.evaluator.evaluate(n)
+
     def _train_loop(self, update):
         ep_ret, ep_len = 0.0, 0
+        why_no_eval = self.eval_refusal()
+        if why_no_eval and not self._eval_refusal_logged:
+            self.logger(f'the policy is not evaluated during training ({why_no_eval})')
+            self._eval_refusal_logged = True
         for it in range(self.parameter.total_iteration):
+            test_log = None if why_no_eval else self.evaluate()   # the policy at the start of the iteration (reference :284-300)
             self.policy.train()
             self.policy.to(self.sample_device)
             for _ in range(self.parameter.step_per_iteration):
@@ -252,6 +288,8 @@ class SAC:
                     self.logger.add_tabular_data(tb_prefix='train', **update())
                     self.grad_num += 1
                 self.sample_num += 1
+            if test_log is not None:
+                self.logger.add_tabular_data(tb_prefix='performance', **test_log)
             self.logger.log_tabular('iteration', it, tb_prefix='timestep')
             self.logger.log_tabular('timestep', self.sample_num, tb_prefix='timestep')
             self.logger.log_tabular('grad_num', self.grad_num, tb_prefix='timestep')
@@ -275,6 +313,8 @@ class SAC:
             self.policy.load(path, map_location=self.sample_device)
             if self.graph_step is not None:
                 self.graph_step.invalidate()
+            if self.evaluator is not None:
+                self.evaluator.invalidate()
         if load_value:
             for i in range(len(self.values)):
                 self.values[i].load(path, index=f'{i}', map_location=self.device)

@@ -9,11 +9,27 @@ from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RESEL_HIP_LIBRARY') or os.path.join(_HERE, 'libresel_hip.so')      # override: ablation builds (tools/gemm_ablate.sh)
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 P, I, L, F, S, U = c_void_p, c_int, c_int64, c_float, c_void_p, c_uint64
 E = ctypes.c_uint                # epoch of a magnitude slot
+
+# by-value tables of resel_step_state_reset (resel_reset_seg_t / resel_reset_segs_t / resel_reset_counters_t of the header)
+RESET_MAX_SEGS, RESET_MAX_COUNTERS = 16, 8
+
+
+class ResetSeg(ctypes.Structure):
+    _fields_ = [('base', c_void_p), ('row_stride', c_int64), ('width', ctypes.c_int32)]
+
+
+class ResetSegs(ctypes.Structure):
+    _fields_ = [('seg', ResetSeg * RESET_MAX_SEGS)]
+
+
+class ResetCounters(ctypes.Structure):
+    _fields_ = [('pos', c_void_p * RESET_MAX_COUNTERS)]
+
 
 # name -> (restype, argtypes); order and types mirror include/resel_hip.h
 SIGNATURES = {
@@ -106,6 +122,8 @@ SIGNATURES = {
     'resel_atb_workspace_bytes': (c_size_t, [L, I, I]),
     'resel_atb': (c_int, [P, L, I, P, L, I, P, I, P, L, S]),
     'resel_attn_decode': (c_int, [P, L, P, P, I, P, P, F, I, I, I, I, S]),
+    'resel_attn_decode_rows': (c_int, [P, L, P, P, P, P, F, I, I, I, I, S]),
+    'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),
 }
 
 

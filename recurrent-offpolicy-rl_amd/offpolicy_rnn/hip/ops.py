@@ -1960,16 +1960,53 @@ def mamba_step(hidden, xz, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, d_conv
 @torch.no_grad()
 def attn_decode(qkv, kv_cache, pos, slopes, scale):
     """Append this token's k, v to kv_cache [Bmax, S, 2, H, hd] (bf16, in place) and attend over positions 0..pos.
-    qkv [B, 3, H, hd] bf16; pos: host int, or an int32 device tensor (graph replay).  -> [B, H, hd] bf16."""
+    qkv [B, 3, H, hd] bf16; pos: host int, or an int32 device tensor (graph replay) - of one element: the position of all rows; of
+    B > 1 elements: one position per row (rows at different points of their episodes, `resel_attn_decode_rows`).  -> [B, H, hd] bf16."""
     _need_cuda('attn_decode', qkv, kv_cache)
     B, _, H, hd = qkv.shape
     assert qkv.dtype == torch.bfloat16 and kv_cache.dtype == torch.bfloat16 and qkv.is_contiguous() and kv_cache.is_contiguous()
     assert kv_cache.shape[0] >= B and kv_cache.shape[2:] == (2, H, hd)
     out = torch.empty((B, H, hd), dtype=torch.bfloat16, device=qkv.device)
     dev = pos if torch.is_tensor(pos) else None
+    if dev is not None and dev.numel() > 1:
+        assert dev.dtype == torch.int32 and dev.is_cuda and dev.is_contiguous() and dev.numel() == B, 'one int32 position per row'
+        check(lib().resel_attn_decode_rows(_p(qkv), 3 * H * hd, _p(kv_cache), _p(dev), _p(slopes), _p(out), float(scale), B, H, hd,
+                                           kv_cache.shape[1], _stream()), 'attn_decode_rows')
+        return out
     check(lib().resel_attn_decode(_p(qkv), 3 * H * hd, _p(kv_cache), _p(dev), 0 if dev is not None else int(pos), _p(slopes), _p(out),
                                   float(scale), B, H, hd, kv_cache.shape[1], _stream()), 'attn_decode')
     return out
+
+
+@torch.no_grad()
+def step_state_reset(flags, tensors, counters):
+    """Episode start for some rows of a B-row step: for every row b with flags[b] != 0, zeros over row b of every tensor in `tensors`
+    and 0 to c[b] of every int32 [B] array in `counters`; other rows untouched.  flags int32 [B] on the device.  A tensor is fp32 with
+    shape [B, W] or [1, B, W], unit stride along W and any row stride >= W (a column view of wider rows is fine).  One launch per 16
+    tensors / 8 counters, nothing else on the stream, no allocation: capturable."""
+    from ._lib import RESET_MAX_COUNTERS, RESET_MAX_SEGS, ResetCounters, ResetSegs
+    _need_cuda('step_state_reset', flags, *tensors, *counters)
+    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
+    B = flags.numel()
+    segs = []
+    for t in tensors:
+        assert t.dtype == torch.float32 and t.dim() >= 2 and t.shape[-2] == B and t.numel() == B * t.shape[-1], 'state rows are [B, W] fp32'
+        W = t.shape[-1]
+        assert W > 0 and (t.stride(-1) == 1 or W == 1) and (t.stride(-2) >= W or B == 1), 'unit stride along a row, rows do not overlap'
+        segs.append((t.data_ptr(), max(t.stride(-2), W), W))
+    for c in counters:
+        assert c.dtype == torch.int32 and c.is_contiguous() and c.numel() == B, 'one int32 position per row'
+    counters = [c.data_ptr() for c in counters]
+    L, s0, c0 = lib(), 0, 0
+    while s0 < len(segs) or c0 < len(counters):
+        st, ct = ResetSegs(), ResetCounters()
+        part, cpart = segs[s0:s0 + RESET_MAX_SEGS], counters[c0:c0 + RESET_MAX_COUNTERS]
+        for i, (base, stride, width) in enumerate(part):
+            st.seg[i].base, st.seg[i].row_stride, st.seg[i].width = base, stride, width
+        for i, ptr in enumerate(cpart):
+            ct.pos[i] = ptr
+        check(L.resel_step_state_reset(_p(flags), B, st, len(part), ct, len(cpart), _stream()), 'step_state_reset')
+        s0, c0 = s0 + len(part), c0 + len(cpart)
 
 
 @torch.no_grad()

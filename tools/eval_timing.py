@@ -1,0 +1,79 @@
+"""Wall time of one policy evaluation (`SAC.evaluate`'s work): 10 episodes of 1000 synthetic steps at the published width (D = 256),
+(a) 10 rows in ONE graphed step with per-row episode starts (utility/policy_eval.py `BatchedPolicyEval`), against
+(b) the 10 episodes one after another through the B = 1 graphed step with `load_hidden(None)` between them - the only form there
+    was before `row_reset`.
+Both run the same host loop (`run_episodes`), the same environments and the policy in eval mode.
+
+    python tools/eval_timing.py [--rnn smamba_s32_c16_b2_nln cgpt_h8_l6_p0.1_ml1024_rms] [--episodes 10] [--steps 1000] [--n 3]
+
+Prints one JSON line per layer id: median / min / max seconds per evaluation over `--n` evaluations behind one warm-up evaluation
+(which captures the graph), and microseconds per graph replay."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'recurrent-offpolicy-rl_amd')]
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--rnn', nargs='+', default=['smamba_s32_c16_b2_nln', 'cgpt_h8_l6_p0.1_ml1024_rms'])
+ap.add_argument('--episodes', type=int, default=10)
+ap.add_argument('--steps', type=int, default=1000)
+ap.add_argument('--n', type=int, default=3)
+args = ap.parse_args()
+
+import numpy as np
+import torch
+import bench
+from offpolicy_rnn import alg_init
+from offpolicy_rnn.env_utils.make_env import make_env
+from offpolicy_rnn.hip.graph_step import GraphedPolicyStep
+from offpolicy_rnn.utility.policy_eval import BatchedPolicyEval, run_episodes
+
+
+def timed(fn):
+    out = []
+    for i in range(args.n + 1):                              # the first one captures
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t)
+        assert res['EpLenTest'] == [args.steps] * args.episodes, res['EpLenTest']
+    return out[1:]
+
+
+for rnn in args.rnn:
+    torch.manual_seed(1234)
+    np.random.seed(1234)
+    par = bench.make_parameter(rnn, 2, args.steps, algo='td3' if rnn.startswith('cgpt') else 'sac')
+    alg = alg_init(par)
+    factory = lambda: make_env(par.env_name, 0)['eval_env']
+    batched = BatchedPolicyEval(alg.policy, factory, bench.ACT, args.episodes, alg.device)
+    t_rows = timed(lambda: batched.evaluate(args.episodes))
+
+    single = GraphedPolicyStep(alg.policy, alg.device, batch_size=1)
+    env = factory()
+    env.seed(5)
+
+    def one_by_one():
+        def step(state, lst_state, lst_action, reward, reset):
+            if reset[0]:
+                single.load_hidden(None)
+            return single(state, lst_state, lst_action, reward)[0]
+        alg.policy.eval()
+        try:
+            return run_episodes(step, [env], args.episodes, bench.OBS, bench.ACT, lambda e: e.reset())[0]
+        finally:
+            alg.policy.train()
+    t_one = timed(one_by_one)
+    med = statistics.median
+    print(json.dumps(dict(
+        rnn=rnn, episodes=args.episodes, steps=args.steps, n=args.n,
+        rows_graph_s=dict(median=round(med(t_rows), 4), min=round(min(t_rows), 4), max=round(max(t_rows), 4)),
+        one_by_one_s=dict(median=round(med(t_one), 4), min=round(min(t_one), 4), max=round(max(t_one), 4)),
+        us_per_replay=dict(rows_graph=round(1e6 * med(t_rows) / args.steps, 1), one_by_one=round(1e6 * med(t_one) / (args.steps * args.episodes), 1)),
+        ratio=round(med(t_one) / med(t_rows), 2))), flush=True)
