@@ -616,6 +616,23 @@ int resel_attn_decode_rows(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_cac
 int resel_step_state_reset(const int32_t* flags, int B, resel_reset_segs_t segs, int nseg, resel_reset_counters_t counters,
                            int ncounters, resel_stream_t stream);
 
+/* Categorical head of one policy step: policy_value_models/contextual_sac_discrete_policy.py:106-121 (softmax, probability floor,
+ * renormalisation, torch.distributions.Categorical's own renormalisation, .mode, .sample(), log of all probabilities) as ONE launch
+ * on `stream` - no LDS, no atomics, no allocation, nothing read from the host: capturable.  Per row of logits [M, A] (row stride
+ * ld_logits):  s = softmax(x) (max-shifted, accurate expf);  t = s + floor;  p = t / sum(t);  p = p / sum(p);  logp = log(p).
+ *   logp   [M, A] (row stride ld_logp);
+ *   mode   [M]: the lowest index among the maxima of p;
+ *   sample [M]: the smallest k with u[m] < p_0 + ... + p_k, clamped to A - 1; u [M] holds one uniform draw in [0, 1) per row and
+ *               comes from the caller, as the noise of the tanh-Gaussian head does.
+ * mode and sample are written as fp32 at mode[m * ld_idx] / sample[m * ld_idx], so that both may be columns of the row block that
+ * also holds logp (the output block of a graphed step).  1 <= A <= RESEL_CATEGORICAL_MAX_ACTIONS, M >= 0 (M = 0: nothing is
+ * launched, returns 0); anything else, a NULL pointer, ld_logits < A, ld_logp < A or ld_idx < 1: RESEL_EINVAL before the device
+ * is touched.  A row that holds a NaN (or +inf) logit gets NaN in all of its logp, mode 0 and sample A - 1; the other rows are
+ * unaffected and nothing asserts on the device. */
+#define RESEL_CATEGORICAL_MAX_ACTIONS 4096
+int resel_categorical_step(const float* logits, int64_t ld_logits, const float* u, float floor, float* logp, int64_t ld_logp,
+                           float* mode, float* sample, int64_t ld_idx, int M, int A, resel_stream_t stream);
+
 /* ---- C = W^T N over a very long reduction dimension (weight gradients of the narrow Mamba projections) ----------------
  * Replaces autograd's `grad.t() @ input` of the x_proj / dt_proj F.linear calls (reference
  * models/smamba/mamba_ssm/ops/selective_scan_interface_new.py:261-335; models/smamba/mamba.py:231-233).

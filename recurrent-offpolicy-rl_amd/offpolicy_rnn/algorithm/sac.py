@@ -86,7 +86,7 @@ class SAC:
         self.sample_hidden = None
         # on the GPU the per-step policy forward is replayed as one hipGraph (hip/graph_step.py); RESEL_GRAPH_ROLLOUT=0: eager
         self.graph_step = None
-        if self.sample_device.type == 'cuda' and os.environ.get('RESEL_GRAPH_ROLLOUT', '1') != '0' and not self.discrete_env:
+        if self.sample_device.type == 'cuda' and os.environ.get('RESEL_GRAPH_ROLLOUT', '1') != '0':
             from ..hip.graph_step import GraphedPolicyStep
             self.graph_step = GraphedPolicyStep(self.policy, self.sample_device, batch_size=1)
         self.evaluator = None                   # BatchedPolicyEval, built by the first evaluate()
@@ -170,7 +170,8 @@ class SAC:
             self.graph_step.load_hidden(self.sample_hidden)
 
     def sample_action(self) -> np.ndarray:
-        """One policy step on the current rollout state (reference sac.py:319-326) -> sampled action [1, act_dim]."""
+        """One policy step on the current rollout state (reference sac.py:319-326) -> sampled action [1, act_dim]; discrete actions:
+        the sampled index, int64 [1, 1], whichever way the step is launched."""
         if self.graph_step is not None:
             return self.graph_step(self.state_np, self.last_state_np, self.last_action_np, self.reward_np)[1].reshape(1, -1)
         with torch.no_grad():
@@ -242,8 +243,6 @@ class SAC:
         """Why `train()` does not evaluate the policy (None: it does)."""
         if self.sample_device.type != 'cuda':
             return 'the policy does not sample on a CUDA device (evaluation replays a hipGraph of the policy step)'
-        if self.discrete_env:
-            return 'discrete action heads are outside the graphed policy step'
         if getattr(self.parameter, 'test_nprocess', 0) * getattr(self.parameter, 'test_nrollout', 0) <= 0:
             return 'test_nprocess * test_nrollout is 0'
         return None
@@ -260,7 +259,7 @@ class SAC:
             from ..utility.policy_eval import BatchedPolicyEval
             self.evaluator = BatchedPolicyEval(self.policy, lambda: make_env(self.env_name, self.env_info['seed'])['eval_env'], self.act_dim,
                                                min(n, 64), self.sample_device, seed=self.parameter.seed,
-                                               eval_tasks=self.env_info.get('eval_tasks'))
+                                               eval_tasks=self.env_info.get('eval_tasks'), discrete=self.discrete_env)
         return self.evaluator.evaluate(n)
 
     def _train_loop(self, update):
@@ -276,7 +275,7 @@ class SAC:
             for _ in range(self.parameter.step_per_iteration):
                 act_sample = self.sample_action()
                 act_env = unorm_act(act_sample[0], self.env.action_space)
-                next_state, reward, done, _ = self.env.step(int(act_env) if self.discrete_env else act_env)
+                next_state, reward, done, _ = self.env.step(int(np.asarray(act_env).reshape(-1)[0]) if self.discrete_env else act_env)
                 ep_ret += reward
                 ep_len += 1
                 self._push(act_sample, next_state, reward, done, ep_len)

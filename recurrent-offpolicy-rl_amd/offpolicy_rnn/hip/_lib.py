@@ -9,7 +9,7 @@ from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RESEL_HIP_LIBRARY') or os.path.join(_HERE, 'libresel_hip.so')      # override: ablation builds (tools/gemm_ablate.sh)
-ABI_VERSION = 10
+ABI_VERSION = 11
 _lib = None
 
 P, I, L, F, S, U = c_void_p, c_int, c_int64, c_float, c_void_p, c_uint64
@@ -124,6 +124,7 @@ SIGNATURES = {
     'resel_attn_decode': (c_int, [P, L, P, P, I, P, P, F, I, I, I, I, S]),
     'resel_attn_decode_rows': (c_int, [P, L, P, P, P, P, F, I, I, I, I, S]),
     'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),
+    'resel_categorical_step': (c_int, [P, L, P, F, P, L, P, P, L, I, I, S]),
 }
 
 

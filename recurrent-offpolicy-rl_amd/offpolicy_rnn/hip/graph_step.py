@@ -10,6 +10,10 @@ the new recurrent state over the old one - and replays it with one `hipGraphLaun
     position from a device counter (`InferenceParams.device_offset`) that the graph advances;
   * the outputs (mean | sample | log-prob) land in one device block, copied back with a single D2H.
 
+A categorical policy (discrete actions, `policy.categorical`) replays the same way.  Its last-action input is the one-hot of the
+previous index, so the input block is unchanged; its output block is [B, 2 + A] = (mode | sample | logp[A]), which the head kernel
+(`ops.categorical_step`) fills directly - the indices travel as fp32 and come back as int64.
+
 `row_reset=True` lets the B rows run episodes that start at different steps (batched evaluation, utility/policy_eval.py): the input
 block carries one reset flag per row, the FIRST node of the graph (`ops.step_state_reset`) zeroes the recurrent state and the cgpt
 position of the flagged rows, and every cgpt KV cache takes one position per row (`device_offset` int32 [B],
@@ -33,6 +37,7 @@ class GraphedPolicyStep:
             raise RuntimeError('GraphedPolicyStep replays a hipGraph: it needs a CUDA (ROCm) device')
         self.policy, self.device, self.B, self._warmup = policy, torch.device(device), batch_size, warmup
         self.row_reset = bool(row_reset)
+        self.categorical = bool(getattr(policy, 'categorical', False))
         self._row_pos = np.zeros(batch_size, dtype=np.int64)      # row_reset: host mirror of the per-row cgpt positions
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._hidden: Optional[RNNHidden] = None
@@ -73,11 +78,16 @@ class GraphedPolicyStep:
         x = self._in_dev.unsqueeze(1)           # [B, 1, .]: B environments, one token each (a 2-D input would be ONE sequence of length B)
         state, lst_state = x[..., :o], x[..., o:2 * o]
         lst_action, reward = x[..., 2 * o:2 * o + a], x[..., 2 * o + a:2 * o + a + 1]
-        mean, _, sample, logp, new_hidden, _ = self.policy.forward(state=state, lst_state=lst_state, lst_action=lst_action,
-                                                                   rnn_memory=self._hidden, reward=reward)
-        self._out_dev[:, :a].copy_(mean.reshape(self.B, a))
-        self._out_dev[:, a:2 * a].copy_(sample.reshape(self.B, a))
-        self._out_dev[:, 2 * a:].copy_(logp.reshape(self.B, -1)[:, :1])
+        if self.categorical:                    # the policy's forward with the head writing (mode | sample | logp) into the block
+            emb_in = self.policy.get_embedding_input(state, lst_state, lst_action, reward)
+            logits, new_hidden, _, _ = self.policy.meta_forward(emb_in, state, self._hidden, False)
+            self.policy.step_head(logits, out=self._out_dev)
+        else:
+            mean, _, sample, logp, new_hidden, _ = self.policy.forward(state=state, lst_state=lst_state, lst_action=lst_action,
+                                                                       rnn_memory=self._hidden, reward=reward)
+            self._out_dev[:, :a].copy_(mean.reshape(self.B, a))
+            self._out_dev[:, a:2 * a].copy_(sample.reshape(self.B, a))
+            self._out_dev[:, 2 * a:].copy_(logp.reshape(self.B, -1)[:, :1])
         for i, h in enumerate(self._hidden._data):
             if torch.is_tensor(h):                   # (conv1d / mamba return the reference's [B, 1, W]: the same memory layout as [1, B, W])
                 h.copy_(new_hidden[i].reshape(h.shape))
@@ -97,8 +107,9 @@ class GraphedPolicyStep:
         if self.row_reset:
             self._flags_host = self._blk_host[self.B * width:].view(torch.int32)
             self._flags_dev = self._blk_dev[self.B * width:].view(torch.int32)
-        self._out_dev = torch.zeros((self.B, 2 * act_dim + 1), dtype=torch.float32, device=self.device)
-        self._out_host = torch.zeros((self.B, 2 * act_dim + 1), dtype=torch.float32).pin_memory()
+        out_width = 2 + act_dim if self.categorical else 2 * act_dim + 1
+        self._out_dev = torch.zeros((self.B, out_width), dtype=torch.float32, device=self.device)
+        self._out_host = torch.zeros((self.B, out_width), dtype=torch.float32).pin_memory()
         if self._hidden is None:
             self.load_hidden(None)
         keep = [h.clone() if torch.is_tensor(h) else None for h in self._hidden._data]
@@ -130,7 +141,8 @@ class GraphedPolicyStep:
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()
     def __call__(self, state, lst_state, lst_action, reward, reset=None):
-        """Numpy / CPU rows [B, dim] in -> (action_mean, action_sample, log_prob) as numpy rows.  One H2D, one graph launch,
+        """Numpy / CPU rows [B, dim] in -> (action_mean, action_sample, log_prob) as numpy rows; a categorical policy takes one-hot
+        last actions [B, A] and returns (mode int64 [B, 1], sample int64 [B, 1], logp float32 [B, A]).  One H2D, one graph launch,
         one D2H.  reset (row_reset=True only): bool / int [B], non-zero = this row starts an episode from the zero state on this step."""
         if reset is not None and not self.row_reset:
             raise ValueError('reset= needs GraphedPolicyStep(..., row_reset=True); without it use load_hidden() for a joint reset')
@@ -168,4 +180,6 @@ class GraphedPolicyStep:
             for ip in self._counters():
                 ip.seqlen_offset += 1
         out = self._out_host.numpy()
+        if self.categorical:
+            return out[:, :1].astype(np.int64), out[:, 1:2].astype(np.int64), out[:, 2:].copy()
         return out[:, :a].copy(), out[:, a:2 * a].copy(), out[:, 2 * a:].copy()

@@ -2010,6 +2010,35 @@ def step_state_reset(flags, tensors, counters):
 
 
 @torch.no_grad()
+def categorical_step(logits, u, floor=0.01, out=None):
+    """Categorical head of one policy step (reference contextual_sac_discrete_policy.py:106-121) as one launch: per row of logits [M, A]
+    p = renormalised twice (softmax + floor), logp = log p, mode = lowest argmax of p, sample = the first k with u < p_0 + ... + p_k.
+    u [M]: one uniform draw in [0, 1) per row.  out: an fp32 block [M, 2 + A] with unit column stride that receives
+    (mode | sample | logp[A]) - the output block of a graphed step; None: logp is a dense [M, A].
+    -> (mode [M], sample [M], logp [M, A]); the indices are fp32 (views of `out` when it is given).  Nothing else on the stream, no
+    host read, no device assert: capturable, and a NaN row shows up as NaN log-probabilities."""
+    _need_cuda('categorical_step', logits, u, out)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and u.dtype == torch.float32
+    M, A = logits.shape
+    if logits.stride(1) != 1 and A > 1:
+        logits = logits.contiguous()
+    u = u.reshape(-1).contiguous()
+    assert u.numel() == M, 'one uniform draw per row'
+    if out is None:
+        logp = torch.empty((M, A), dtype=torch.float32, device=logits.device)
+        idx = torch.empty((M, 2), dtype=torch.float32, device=logits.device)
+        mode, sample = idx[:, 0], idx[:, 1]
+    else:
+        assert out.dtype == torch.float32 and out.shape == (M, 2 + A) and out.stride(1) == 1 and (M <= 1 or out.stride(0) >= 2 + A)
+        mode, sample, logp = out[:, 0], out[:, 1], out[:, 2:]
+    if M == 0:                                           # empty tensors have no address to hand over
+        return mode, sample, logp
+    check(lib().resel_categorical_step(_p(logits), max(logits.stride(0), A), _p(u), float(floor), _p(logp), max(logp.stride(0), A),
+                                       _p(mode), _p(sample), max(mode.stride(0), 1), M, A, _stream()), 'categorical_step')
+    return mode, sample, logp
+
+
+@torch.no_grad()
 def soft_update_(target_flat, online_flat, tau):
     _need_cuda('soft_update', target_flat, online_flat)
     PARAM_EPOCH[0] += 1

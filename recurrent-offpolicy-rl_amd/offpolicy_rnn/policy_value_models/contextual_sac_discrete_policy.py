@@ -1,6 +1,7 @@
 """Categorical actor for discrete action spaces (reference
 offpolicy_rnn/policy_value_models/contextual_sac_discrete_policy.py:13-138): logits -> softmax, mixed with a 0.01 floor
-and renormalised; returns (argmax, sample, log-probabilities of ALL actions)."""
+and renormalised; returns (argmax, sample, log-probabilities of ALL actions).  A one-token call on the device without autograd - a
+rollout or evaluation step, eager or captured - runs the head as one HIP kernel (`ops.categorical_step`)."""
 from typing import Optional, Tuple
 
 import torch
@@ -15,6 +16,8 @@ from .utils import nearest_power_of_two, nearest_power_of_two_half
 class ContextualSACDiscretePolicy(ContextualModel):
     MAX_LOG_STD = 2.0
     MIN_LOG_STD = -15.0
+    PROB_FLOOR = 0.01                    # mixed into the softmax before it is renormalised (reference :114)
+    categorical = True                   # the head returns action indices and the log-probabilities of all actions
 
     def __init__(self, state_dim, action_dim, embedding_size, embedding_hidden, embedding_activations, embedding_layer_type,
                  uni_model_hidden, uni_model_activations, uni_model_layer_type, fix_rnn_length, uni_model_input_mapping_dim: int = 0,
@@ -46,9 +49,23 @@ class ContextualSACDiscretePolicy(ContextualModel):
         action_mean, action_sample, log_probs, _ = self.process_model_out(out)
         return action_mean, emb, action_sample, log_probs, rnn_memory, full
 
+    def step_head(self, model_output, out=None):
+        """The head of a one-token call as one kernel: logits [..., 1, A] -> fp32 (mode [M], sample [M], logp [M, A]) over the
+        M = prod(...) rows, written into `out` [M, 2 + A] when given (hip/graph_step.py).  One uniform draw per row from the device
+        generator, so the draws of a captured step advance with the replays as the continuous head's noise does."""
+        from ..hip import ops
+        logits = model_output.reshape(-1, model_output.shape[-1]).float()
+        u = torch.rand(logits.shape[0], dtype=torch.float32, device=logits.device)
+        return ops.categorical_step(logits, u, self.PROB_FLOOR, out=out)
+
     def process_model_out(self, model_output):
+        if model_output.is_cuda and not torch.is_grad_enabled() and model_output.dim() >= 2 and model_output.shape[-2] == 1:
+            mode, sample, logp = self.step_head(model_output)        # a step, not a whole-row pass (the layers' own test)
+            lead = model_output.shape[:-1] + (1,)
+            logp = logp.reshape(model_output.shape)
+            return mode.long().reshape(lead), sample.long().reshape(lead), logp, logp.exp()
         probs = torch.softmax(model_output, dim=-1)                  # reference :112-113 (max-shifted exp / sum)
-        probs = probs + 0.01
+        probs = probs + self.PROB_FLOOR
         probs = probs / probs.sum(dim=-1, keepdim=True)
         probs = probs / probs.sum(dim=-1, keepdim=True)              # torch.distributions.Categorical normalises once more (:116)
         action_mean = probs.argmax(dim=-1, keepdim=True)             # Categorical.mode

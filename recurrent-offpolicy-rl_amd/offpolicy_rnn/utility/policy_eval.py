@@ -17,7 +17,7 @@ import torch
 from .sample_utility import unorm_act
 
 
-def run_episodes(step: Callable, envs: List, n_episodes: int, obs_dim: int, act_dim: int, reset_env: Callable):
+def run_episodes(step: Callable, envs: List, n_episodes: int, obs_dim: int, act_dim: int, reset_env: Callable, discrete: bool = False):
     """The reference's `policy_eval` loop (sample_utility.py:50-100) over len(envs) rows at once.
 
     step(state, lst_state, lst_action, reward, reset) -> action means [rows, act_dim]; `reset` [rows] bool marks the rows that start
@@ -25,6 +25,8 @@ def run_episodes(step: Callable, envs: List, n_episodes: int, obs_dim: int, act_
     first), environments are reset in that order too, and no environment is stepped between its `done` and its next reset.  A row's
     first step sees zero last state / last action / reward (:59-61).  A row without an episode is fed zeros with its flag set on every
     step (a cgpt position never runs away); what the step returns for it is ignored.
+    discrete (reference :75-76,82-84): step returns the action indices [rows, 1] instead, the environment gets `int(index)` and the
+    next step's lst_action is the one-hot of it over act_dim actions.
     -> ({'EpRetTest': [...], 'EpLenTest': [...], '<key>Test': [...]} in episode order, [row that ran each episode]); an info entry
     holds, per episode that reported the key, the value of its last report (the reference keeps the last report only, :93-96)."""
     rows = len(envs)
@@ -50,15 +52,21 @@ def run_episodes(step: Callable, envs: List, n_episodes: int, obs_dim: int, act_
     for r in range(rows):
         begin(r)
     while any(k >= 0 for k in episode):
-        mean = np.asarray(step(state, lst_state, lst_action, reward, reset)).reshape(rows, act_dim)
+        mean = np.asarray(step(state, lst_state, lst_action, reward, reset)).reshape(rows, 1 if discrete else act_dim)
         reset[:] = False
         for r in range(rows):
             k = episode[r]
             if k < 0:
                 reset[r] = True
                 continue
-            act = mean[r].copy()
-            next_state, rew, done, info = envs[r].step(unorm_act(act, envs[r].action_space))
+            if discrete:
+                index = int(unorm_act(mean[r, 0], envs[r].action_space))
+                act = np.zeros(act_dim)
+                act[index] = 1
+                next_state, rew, done, info = envs[r].step(index)
+            else:
+                act = mean[r].copy()
+                next_state, rew, done, info = envs[r].step(unorm_act(act, envs[r].action_space))
             lst_state[r] = state[r]
             state[r] = np.asarray(next_state).reshape(-1)
             reward[r], lst_action[r] = rew, act
@@ -90,14 +98,15 @@ class BatchedPolicyEval:
     private stream the way the reference's `eval_inprocess` seeds its own, sample_utility.py:127-129) and nothing else.
 
     eval_tasks: task list of a meta environment (reference :53-56) - a reset draws one from the private stream.
+    discrete: a categorical policy - act_dim actions, the step's first output is the mode index (`run_episodes(discrete=True)`).
     step: a replacement for the graphed step with the same call signature (host tests)."""
 
     def __init__(self, policy, env_factory: Callable, act_dim: int, rows: int, device, seed: int = 0, eval_tasks=None,
-                 step: Optional[Callable] = None):
+                 step: Optional[Callable] = None, discrete: bool = False):
         assert rows > 0
         self.policy, self.env_factory, self.act_dim, self.rows = policy, env_factory, act_dim, int(rows)
         self.device = torch.device(device)
-        self.eval_tasks = eval_tasks
+        self.eval_tasks, self.discrete = eval_tasks, bool(discrete)
         self.rs = np.random.RandomState(seed)
         self.step, self.envs, self.env_seeds = step, None, []
         self.last_rows: List[int] = []                     # row that ran each episode of the last evaluation
@@ -129,8 +138,8 @@ class BatchedPolicyEval:
     def evaluate(self, n_episodes: int) -> Dict[str, list]:
         """n_episodes deterministic episodes (action = the policy's mean) of the current parameters, which the graph reads through
         their storage.  The step is captured and replayed with the policy in eval mode; its previous mode comes back afterwards, and
-        so does the state of Python's, numpy's and torch's CPU and device generators (the graph's unused action-noise draws advance the
-        device generator; reading its state is one device sync)."""
+        so does the state of Python's, numpy's and torch's CPU and device generators (the graph's unused action-noise draws - or a categorical
+        head's uniform draws - advance the device generator; reading its state is one device sync)."""
         cuda = self.device.type == 'cuda'
         saved = (random.getstate(), np.random.get_state(), torch.get_rng_state(), torch.cuda.get_rng_state(self.device) if cuda else None)
         was_training = _is_training(self.policy) if self.policy is not None else False
@@ -143,7 +152,8 @@ class BatchedPolicyEval:
             def step(state, lst_state, lst_action, reward, reset):
                 return self.step(state, lst_state, lst_action, reward, reset=reset)[0]
 
-            out, self.last_rows = run_episodes(step, self.envs, int(n_episodes), obs_dim, self.act_dim, self._reset_env)
+            out, self.last_rows = run_episodes(step, self.envs, int(n_episodes), obs_dim, self.act_dim, self._reset_env,
+                                               discrete=self.discrete)
             return out
         finally:
             if self.policy is not None:

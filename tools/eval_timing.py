@@ -2,9 +2,12 @@
 (a) 10 rows in ONE graphed step with per-row episode starts (utility/policy_eval.py `BatchedPolicyEval`), against
 (b) the 10 episodes one after another through the B = 1 graphed step with `load_hidden(None)` between them - the only form there
     was before `row_reset`.
-Both run the same host loop (`run_episodes`), the same environments and the policy in eval mode.
+Both run the same host loop (`run_episodes`), the same environments and the policy in eval mode.  `--env synthetic-o17-d6-T1000` (any
+synthetic name, make_env.py) replaces the benchmark's environment; a `-d<n>-` name is a discrete-action run: categorical policy, the
+evaluator's discrete form.
 
     python tools/eval_timing.py [--rnn smamba_s32_c16_b2_nln cgpt_h8_l6_p0.1_ml1024_rms] [--episodes 10] [--steps 1000] [--n 3]
+                                [--env synthetic-o17-d6-T1000]
 
 Prints one JSON line per layer id: median / min / max seconds per evaluation over `--n` evaluations behind one warm-up evaluation
 (which captures the graph), and microseconds per graph replay."""
@@ -23,6 +26,7 @@ ap.add_argument('--rnn', nargs='+', default=['smamba_s32_c16_b2_nln', 'cgpt_h8_l
 ap.add_argument('--episodes', type=int, default=10)
 ap.add_argument('--steps', type=int, default=1000)
 ap.add_argument('--n', type=int, default=3)
+ap.add_argument('--env', default=None, help='synthetic-o<obs>-[ad]<act>-T<len>: replaces the benchmark environment and --steps')
 args = ap.parse_args()
 
 import numpy as np
@@ -49,10 +53,15 @@ def timed(fn):
 for rnn in args.rnn:
     torch.manual_seed(1234)
     np.random.seed(1234)
-    par = bench.make_parameter(rnn, 2, args.steps, algo='td3' if rnn.startswith('cgpt') else 'sac')
+    discrete = args.env is not None and '-d' in args.env
+    par = bench.make_parameter(rnn, 2, args.steps, algo='td3' if rnn.startswith('cgpt') and not discrete else 'sac')
+    if args.env is not None:
+        par.env_name = args.env
+        args.steps = make_env(args.env, 0)['max_trajectory_len']
     alg = alg_init(par)
+    assert alg.discrete_env == discrete
     factory = lambda: make_env(par.env_name, 0)['eval_env']
-    batched = BatchedPolicyEval(alg.policy, factory, bench.ACT, args.episodes, alg.device)
+    batched = BatchedPolicyEval(alg.policy, factory, alg.act_dim, args.episodes, alg.device, discrete=discrete)
     t_rows = timed(lambda: batched.evaluate(args.episodes))
 
     single = GraphedPolicyStep(alg.policy, alg.device, batch_size=1)
@@ -66,13 +75,13 @@ for rnn in args.rnn:
             return single(state, lst_state, lst_action, reward)[0]
         alg.policy.eval()
         try:
-            return run_episodes(step, [env], args.episodes, bench.OBS, bench.ACT, lambda e: e.reset())[0]
+            return run_episodes(step, [env], args.episodes, alg.obs_dim, alg.act_dim, lambda e: e.reset(), discrete=discrete)[0]
         finally:
             alg.policy.train()
     t_one = timed(one_by_one)
     med = statistics.median
     print(json.dumps(dict(
-        rnn=rnn, episodes=args.episodes, steps=args.steps, n=args.n,
+        rnn=rnn, env=par.env_name, episodes=args.episodes, steps=args.steps, n=args.n,
         rows_graph_s=dict(median=round(med(t_rows), 4), min=round(min(t_rows), 4), max=round(max(t_rows), 4)),
         one_by_one_s=dict(median=round(med(t_one), 4), min=round(min(t_one), 4), max=round(max(t_one), 4)),
         us_per_replay=dict(rows_graph=round(1e6 * med(t_rows) / args.steps, 1), one_by_one=round(1e6 * med(t_one) / (args.steps * args.episodes), 1)),
