@@ -58,17 +58,21 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from ..buffers.transition_buffer.shape_buckets import pad_plan, pad_seq_tables
+from ..buffers.transition_buffer.shape_buckets import NO_SEQ_BUCKETS, pad_plan, pad_seq_tables
 from ..hip import ops
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
-from .sac_full_length_rnn_ensembleQ import NO_SEQ_BUCKETS, DeferredLog
+from ..models.rnn_base import training_pass
+from ..utility.deferred_log import DeferredLog
 
 
-class _StaticLog(DeferredLog):
-    def __init__(self, keys, buf, event, host_items):
-        dict.__init__(self)
-        self._keys, self._buf, self._event = keys, buf, event
-        self.set_host(host_items)
+def _exact_batch_key(pl):
+    """The batch's part of the graph key without buckets: rows, row length, longest drawn row, plan segments."""
+    return pl['nrow'], pl['longest'], pl['max_len'], pl['seg'].shape[0]
+
+
+def _exact_table_key(built):
+    """The sequence tables' part of the graph key without buckets: tokens, cu entries and longest sequence of both descriptions."""
+    return tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
 
 
 class GraphedUpdate:
@@ -110,7 +114,7 @@ class GraphedUpdate:
             raise ValueError(f'GraphedUpdate: buckets={buckets!r} (off, on, auto)')
         # read HERE, not by the caller: `train()` builds `GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())`
         self.seq_buckets = self.seq_buckets_from_env() if seq_buckets is None else bool(seq_buckets)
-        if buckets == 'on' and getattr(alg, '_needs_seq_table', False) and not self.seq_buckets:
+        if buckets == 'on' and alg._needs_seq_table and not self.seq_buckets:
             raise RuntimeError('GraphedUpdate: ' + self.NO_SEQ_BUCKETS)
         self.alg, self.device = alg, alg.device
         self.graphs = OrderedDict()                   # batch shape key -> CUDAGraph, least recently used first
@@ -136,14 +140,12 @@ class GraphedUpdate:
             alg.values[0].store.ensure_grad_extra(4 + 4 * alg.grad_sync.world)
         E = alg.target_values[0].uni_network.layer_list[-1].num_ensemble
         self.E = E
-        self._draw = type(alg)._select_target_ensemble.__get__(alg)         # the trainer's own host draw
-        # static subset buffers sized WITHOUT consuming a draw: evaluate the draw on a scratch numpy stream and put the stream back
+        # static subset buffers sized WITHOUT consuming a draw: make the trainer's host draw once and put both numpy streams back
         st_np = np.random.get_state()
-        if hasattr(alg, '_subset_stream'):
-            alg._subset_stream()                      # data-parallel ranks create their shared stream on first use: create it BEFORE its state is saved
-        rng_own = getattr(alg, '_subset_rng', None)
+        alg._subset_stream()                          # data-parallel ranks create their shared stream on first use: create it BEFORE its state is saved
+        rng_own = alg._subset_rng
         st_own = None if rng_own is None else rng_own.get_state()
-        first = np.asarray(self._draw(E))
+        first = np.asarray(alg._select_target_ensemble(E))
         np.random.set_state(st_np)
         if st_own is not None:
             rng_own.set_state(st_own)
@@ -171,11 +173,15 @@ class GraphedUpdate:
                            evt=torch.cuda.Event(), used=False, handed=None) for _ in range(self.RING)]
         self._turn = 0
         self._slot = self._ring[0]
+        self._plan = None                             # the sampling plan of the update being prepared / launched (_prepare)
+        self._log_keys = self._log_items = None       # device scalars / host entries of the launch sequence last recorded or replayed (log_node, step)
+        self._capture_stream = None                   # side stream the recordings are made on (created by the first one)
         # attention layers: static sequence tables (two descriptions per batch: the batch and its one-slot shift) and the dropout base
         self._seq = None
+        self._seq_now = None                          # per description: (tokens, cu entries, longest sequence, table, padded) of this update (_prepare_seqs)
         self._drop_base = None
         self._drop_seed = 0
-        if getattr(alg, '_needs_seq_table', False):
+        if alg._needs_seq_table:
             self._drop_base = torch.zeros(1, dtype=torch.int64, device=self.device)
             ops.dropout_offset_base(self._drop_base)
             if not torch.cuda.default_generators:
@@ -207,12 +213,8 @@ class GraphedUpdate:
 
     @staticmethod
     def _build_seqs(pl):
-        """Host half of `_batch_views` for attention layers (runs while the previous replay is still on the GPU)."""
-        rows, T, table = pl['nrow'], pl['longest'], pl['table']
-        am = np.zeros((rows, T), dtype=np.int32)
-        am[:, :table.shape[1]] = table
-        tam = np.concatenate((am[:, 1:], np.zeros((rows, 1), dtype=np.int32)), axis=1)
-        return [PackedSeqs.build_host(a, T) for a in (am, tam)]
+        """Host half of the sequence tables of attention layers (runs while the previous replay is still on the GPU)."""
+        return PackedSeqs.build_host_pair(pl['table'], pl['nrow'], pl['longest'])
 
     def _prepare_seqs(self, built, padded_key=None):
         """Both descriptions into the pinned buffers (the previous replay has read them); returns their part of the shape key
@@ -227,12 +229,14 @@ class GraphedUpdate:
             sq['idx_dev'][i][:idx.size].copy_(sq['idx_host'][k][i][:idx.size], non_blocking=True)      # stream-ordered, outside the graph
             sq['cu_dev'][i][:cu.size].copy_(sq['cu_host'][k][i][:cu.size], non_blocking=True)
         self._seq_now = [(b[0].size, b[1].size, b[2], b[3], padded_key is not None) for b in built]
-        return padded_key if padded_key is not None else tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
+        return padded_key if padded_key is not None else _exact_table_key(built)
 
     def packed_seqs(self):
-        """Called by the trainer's `_batch_views` while this object drives the update: views of the static device tables (refreshed by
-        `_prepare_seqs` before the replay)."""
+        """Called by the trainer's `_sample` while this object drives the update: views of the static device tables (refreshed by
+        `_prepare_seqs` before the replay); None without attention layers."""
         sq = self._seq
+        if sq is None:
+            return None
         return [PackedSeqs.from_static(sq['idx_dev'][i][:n_idx], sq['cu_dev'][i][:n_cu], mx, tb, padded=padded)
                 for i, (n_idx, n_cu, mx, tb, padded) in enumerate(self._seq_now)]
 
@@ -247,7 +251,7 @@ class GraphedUpdate:
             return 'the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce) issues collectives inside the target computation'
         if par.utd != 1:
             return 'utd != 1'
-        if not (getattr(alg, 'device_replay', False) and alg.replay_buffer.device_supported(randomize_mask=par.randomize_mask)):
+        if not (alg.device_replay and alg.replay_buffer.device_supported(randomize_mask=par.randomize_mask)):
             return 'needs the device-resident replay ring'
         return None
 
@@ -258,7 +262,12 @@ class GraphedUpdate:
         # the whole static selection buffer: its capacity, not this plan's size, is the `sel_words` baked into the graph node
         dev = self.alg.replay_buffer.gather_planned(self.device, self._plan_dev[:n], pl['max_len'], pl['nrow'], pl['longest'],
                                                     sel_dev=self._sel_dev)
-        return dev, pl['total_size'], pl['table']
+        return dev, pl['total_size'], pl.get('nrow_real', pl['nrow'])
+
+    def target_subset(self):
+        """The trainer's `_target_subset`: the constructor's draw (its size is every draw's) and the static device copies of the
+        subset `_prepare` drew for this update."""
+        return self.subset_np, lambda as_long=False: self.subset_i64 if as_long else self.subset_i32
 
     def cut(self, exchange):
         """Called by the trainer where ranks exchange gradients (`_finish_step`).  Recording: the graph being captured ends here, the
@@ -277,7 +286,9 @@ class GraphedUpdate:
         """Record one update as a list of (graph, exchange) segments; one segment unless the trainer cuts (data parallel)."""
         torch.cuda.synchronize(self.device)
         torch.cuda.empty_cache()
-        side = self.__dict__.setdefault('_capture_stream', torch.cuda.Stream(device=self.device))
+        if self._capture_stream is None:
+            self._capture_stream = torch.cuda.Stream(device=self.device)
+        side = self._capture_stream
         side.wait_stream(torch.cuda.current_stream(self.device))
         rec = self._rec = dict(segs=[], g=torch.cuda.CUDAGraph())
         try:
@@ -294,10 +305,9 @@ class GraphedUpdate:
         torch.cuda.synchronize(self.device)
         return dict(segs=rec['segs'], log_keys=self._log_keys, log_items=self._log_items)
 
-    def log_node(self, keys, packed, host, items):
-        self._log_keys = keys
+    def log_node(self, keys, packed, host_items):
+        self._log_keys, self._log_items = keys, host_items
         self._log_dev[:packed.numel()].copy_(packed)                         # a node of the graph; the read-back follows the replay (_finish)
-        self._log_items = dict(host, **items)
         return None
 
     # ---- host side of one update ----------------------------------------------------------------------------------------------
@@ -321,7 +331,7 @@ class GraphedUpdate:
         if n_sel > self._sel_capacity:
             raise RuntimeError(f'GraphedUpdate: {n_sel} selection words exceed the static selection buffer ({self._sel_capacity})')
         # bucketed: `max_len` is the row length (it only sizes the gather grid)
-        key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else (pl['nrow'], pl['longest'], pl['max_len'], n)
+        key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else _exact_batch_key(pl)
         if self._drop_base is not None and built is None:
             built = self._build_seqs(pl)
         # staging slot of this update: its copies of three updates ago have long run; the log handed out then is read out before its block is reused
@@ -342,12 +352,12 @@ class GraphedUpdate:
             slot['sel'].numpy()[:n_sel] = pl['sel']
             self._sel_dev[:n_sel].copy_(slot['sel'][:n_sel], non_blocking=True)
         self._plan = pl
-        sub = np.ascontiguousarray(np.asarray(self._draw(self.E)), dtype=np.int32)
+        sub = np.ascontiguousarray(np.asarray(alg._select_target_ensemble(self.E)), dtype=np.int32)
         slot['sub'].numpy()[...] = sub
         self.subset_i32.copy_(slot['sub'], non_blocking=True)
         self.subset_i64.copy_(self.subset_i32)
-        # is the actor step due in this update (reference :450-452 with utd = 1)?  Part of the key: the two launch sequences are two graphs
-        actor_due = alg.grad_num % par.policy_update_per == 0 and par.policy_utd > 0
+        # is the actor step due in this update (utd = 1: its one critic step, no actor step yet)?  Part of the key: the two launch sequences are two graphs
+        actor_due = alg._actor_due(0, 0)
         for i, opt in enumerate((alg.optimizer_value, alg.optimizer_policy)):
             if i == 0 or actor_due:
                 opt.prepare_step(slot['bc'][2 * i:2 * i + 2])
@@ -357,10 +367,9 @@ class GraphedUpdate:
     def _count_shape(self, pl, built=None):
         """'auto': True once, when this exact shape is one more than the graphs can hold (`max_graphs` over the launch sequences) - the
         workload is ragged, exact keys would leave most updates eager.  Drops what was recorded and counted for exact keys."""
-        if getattr(self.alg, '_needs_seq_table', False) and not self.seq_buckets:      # attention layers: no buckets (NO_SEQ_BUCKETS)
+        if self.alg._needs_seq_table and not self.seq_buckets:      # attention layers: no buckets (NO_SEQ_BUCKETS)
             return False
-        tables = () if built is None else tuple(x for b in built for x in (b[0].size, b[1].size, b[2]))
-        self._shapes.add((pl['nrow'], pl['longest'], pl['max_len'], pl['seg'].shape[0]) + tables)
+        self._shapes.add(_exact_batch_key(pl) + (() if built is None else _exact_table_key(built)))
         if len(self._shapes) <= max(1, self.max_graphs // self._sequences):
             return False
         self.buckets = 'on'
@@ -377,7 +386,6 @@ class GraphedUpdate:
     def _body(self):
         alg = self.alg
         alg._graph = self
-        alg._select_target_ensemble = lambda E: self.subset_np
         for opt in (alg.optimizer_value, alg.optimizer_policy):
             opt.device_factors_active = True
         if self._drop_base is not None:
@@ -386,11 +394,11 @@ class GraphedUpdate:
             ops.amax_arena_zero(self.device)          # first node: a replay publishes operand magnitudes into the slots / epochs baked into the graph
             if self._drop_base is not None:
                 self._drop_base.add_(self.DROP_STRIDE)                       # a node: every replay moves the masks of the whole update on
-            alg.train_one_batch()
+            with training_pass():
+                alg._train_one_batch()                # below the eager entry's update-boundary work: `step()` does that itself
         finally:
             ops.DROP_OVERRIDE = None
             alg._graph = None
-            del alg._select_target_ensemble
             for opt in (alg.optimizer_value, alg.optimizer_policy):
                 opt.device_factors_active = False
 
@@ -400,11 +408,9 @@ class GraphedUpdate:
         slot['log'][:n].copy_(self._log_dev[:n], non_blocking=True)          # behind the update on the stream
         slot['evt'].record()
         slot['used'] = True
-        items = dict(self._log_items)
         pl = self._plan                               # the host entries of THIS update (the captured dict holds the recorded update's)
-        items.update(real_batch_size=pl['total_size'], real_batch_traj_num=pl.get('nrow_real', pl['nrow']),
-                     average_traj_len=self.alg.replay_buffer.size / len(self.alg.replay_buffer))
-        slot['handed'] = _StaticLog(list(self._log_keys), slot['log'][:n], slot['evt'], items)
+        items = dict(self._log_items, **self.alg._host_log(pl['total_size'], pl.get('nrow_real', pl['nrow'])))
+        slot['handed'] = DeferredLog(list(self._log_keys), slot['log'][:n], slot['evt'], items)
         return slot['handed']
 
     def step(self):

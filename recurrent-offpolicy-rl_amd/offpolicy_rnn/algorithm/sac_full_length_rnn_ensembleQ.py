@@ -18,28 +18,30 @@ What is organised differently for the MI355X:
 """
 from typing import Dict
 
+import contextlib
+import functools
+import itertools
+import math
 import os
 
 import numpy as np
 import torch
 
 from ..buffers.transition_buffer.nested_replay_memory import NestedMemoryArray as NestedTransitionMemoryArray
-from ..buffers.transition_buffer.shape_buckets import pad_seq_tables
+from ..buffers.transition_buffer.shape_buckets import NO_SEQ_BUCKETS, pad_seq_tables
 from ..hip import ops
 from ..models.contextual_model import ContextualModel
+from ..models.ensemble_linear_model import EnsembleLinear
 from ..models.flash_attention.TransformerFlashAttention import PackedSeqs
+from ..models.rnn_base import training_pass
 from ..parallel.data_parallel import GradSync
 from ..policy_value_models.make_models import make_policy_model
+from ..utility.deferred_log import DeferredLog
 from ..utility.pinned import PinnedRing
-
-FUSED_LOSSES = FUSED_Q = FUSED_A = True      # the masked losses as one forward + one backward kernel each (csrc/losses.hip); CPU tensors keep the torch spelling
 from ..utility.q_value_guard import QValueGuard
 from .sac import SAC
 
 FIELDS = ('state', 'last_state', 'action', 'last_action', 'next_state', 'done', 'mask', 'reward', 'reward_input', 'timeout', 'start')
-
-
-import contextlib
 
 
 @contextlib.contextmanager
@@ -56,7 +58,6 @@ def _frozen_parameters(model):
 
 @contextlib.contextmanager
 def _ensemble_subset(model, member_index):
-    from ..models.ensemble_linear_model import EnsembleLinear
     layers = [l for l in model.uni_network.layer_list if isinstance(l, EnsembleLinear)]
     for l in layers:
         l.member_index = member_index
@@ -65,75 +66,6 @@ def _ensemble_subset(model, member_index):
     finally:
         for l in layers:
             l.member_index = None
-
-
-NO_SEQ_BUCKETS = 'shape buckets do not cover layers that need sequence tables (cgpt): the token and cu_seqlens tables vary with the batch ' \
-                 'and are bucketed only with seq_buckets (RESEL_GRAPH_SEQ_BUCKETS=1)'
-
-
-class DeferredLog(dict):
-    """The update's log dict.  Host-side entries are plain items; the device scalars travel in one asynchronous copy into
-    pinned memory and become floats on first access (`resolve()`), so a caller that does not read them - a training loop
-    logging every n-th update, bench.py - never stalls the launch queue on the update it has just enqueued."""
-
-    def __init__(self, keys, packed, pinned):
-        super().__init__()
-        self._keys = keys
-        if pinned:
-            self._buf = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=True)
-            self._buf.copy_(packed, non_blocking=True)
-            self._event = torch.cuda.Event()
-            self._event.record()
-        else:
-            self._buf, self._event = packed.detach().cpu(), None
-
-    def set_host(self, items):
-        dict.update(self, items)
-
-    def resolve(self):
-        if self._keys is not None:
-            if self._event is not None:
-                self._event.synchronize()
-            vals = dict(zip(self._keys, self._buf.tolist()))
-            if 'actor_loss' in vals:
-                vals['actor_loss'] = (vals['actor_loss'],)      # a 1-tuple upstream (reference :430); kept
-            self._keys = None
-            pending = dict(self)                                # host entries override / follow, as in the reference order
-            dict.clear(self)
-            dict.update(self, vals)
-            dict.update(self, pending)
-        return self
-
-    def __getitem__(self, k):
-        if not dict.__contains__(self, k):
-            self.resolve()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        if not dict.__contains__(self, k):
-            self.resolve()
-        return dict.get(self, k, default)
-
-    def __contains__(self, k):
-        return dict.__contains__(self, k) or dict.__contains__(self.resolve(), k)
-
-    def __iter__(self):
-        return dict.__iter__(self.resolve())
-
-    def __len__(self):
-        return dict.__len__(self.resolve())
-
-    def keys(self):
-        return dict.keys(self.resolve())
-
-    def items(self):
-        return dict.items(self.resolve())
-
-    def values(self):
-        return dict.values(self.resolve())
-
-    def __repr__(self):
-        return dict.__repr__(self.resolve())
 
 
 class SACFullLengthRNNEnsembleQ(SAC):
@@ -149,7 +81,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
             if hasattr(net, 'in_proj') and hasattr(net.in_proj, 'desire_ndim'):
                 net.in_proj.desire_ndim = 4
         self.logger(f'replay buffer skip len: {self._get_skip_len()}')
-        self.amp_scalar = self.amp_scalar_critic = None            # fp32 / bf16 paths need no loss scaling
         self.replay_buffer = NestedTransitionMemoryArray(self.parameter.max_buffer_transition_num, self.env_info['max_trajectory_len'],
                                                          additional_history_len=self._get_skip_len())
         self.Q_guard = QValueGuard(guard_min=True, guard_max=True, decay_ratio=1.0 if self.discrete_env else 1 - 1e-3,
@@ -162,8 +93,8 @@ class SACFullLengthRNNEnsembleQ(SAC):
         self.grad_sync = GradSync()
         self._graph = None                             # set while a captured update is being recorded / replayed (graphed_update.py)
         # eager updates pad their batch into its shape bucket (shape_buckets.py; tests, tools).  Device replay ring only, and not with
-        # attention layers unless `seq_buckets` is set as well (then `_batch_views` pads their sequence tables into buckets,
-        # shape_buckets.pad_seq_tables, and the decoder takes its padded path): `_train_one_batch` raises otherwise
+        # attention layers unless `seq_buckets` is set as well (then `_packed_seqs` pads their sequence tables into buckets,
+        # shape_buckets.pad_seq_tables, and the decoder takes its padded path): `_sample` raises otherwise
         self.shape_buckets = False
         self.seq_buckets = False
         self._subset_rng = None                        # REDQ subset stream: None = numpy's global stream (see _subset_stream)
@@ -172,8 +103,10 @@ class SACFullLengthRNNEnsembleQ(SAC):
                                                                        self.policy.uni_network, self.policy.embedding_network)
                                     for lid in net.layer_type)
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
-        self._shared_policy_out = None
-        self._share_this_update = False
+        self._planar_idx = {}                          # (flag names, device) -> their column indices on the device (_batch_views)
+        self._subset_tables, self._subset_cache = {}, {}     # device copies of critic-subset index vectors (_subset_on_device)
+        self._guard_ext = None                         # data parallel: this rank's Q-guard extrema on their way into the critic's gradient bucket
+        self._guard_ext_fresh = False                  # ... written by this update's target and not yet exchanged (_guard_exchange, _finish_step)
         self.share_policy_pass = self._policy_pass_shareable()
         # RESEL_GRU_BATCH (default on): the independent embedding passes of a phase (latency-bound gru value embeddings) walk their towers
         # in lockstep and their recurrences share ONE launch (ContextualModel.prefetch_embeddings).  0: serial, one recurrence after
@@ -184,6 +117,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
 
     step = property(lambda self: self.train_one_batch)          # north_star's "algorithm.step()" alias
     device_replay = True        # keep a device mirror of the replay ring and assemble sampled batches on the GPU (CUDA only)
+    defer_log = False           # True: the log's device scalars stay in flight until first read (DeferredLog); False: floats on return, as the reference
 
     def _get_skip_len(self):
         skip = 0
@@ -196,9 +130,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
                 elif 'conv1d' in lid:
                     skip = max(net.layer_list[i].d_conv, skip)
         return skip + 1
-
-    def _get_whether_require_amp(self):
-        return False
 
     # state cleared / masked at the first token of a trajectory; cgpt attends inside per-trajectory segments whose table
     # is shifted with the tokens (`target_attention_mask`, reference :358-366)
@@ -227,9 +158,6 @@ class SACFullLengthRNNEnsembleQ(SAC):
                     return False
         return not any(isinstance(m, torch.nn.Dropout) and m.p > 0 for mod in self.policy.contextual_modules.values() for m in mod.modules())
 
-    def _mask_mean(self, data: torch.Tensor, mask: torch.Tensor, valid_num) -> torch.Tensor:
-        return (data * mask).sum() / valid_num
-
     # ------------------------------------------------------------------------------------------ batch
     def _upload_batch(self, batch, valid, table):
         """Host fix-ups + ONE host->device copy.  Returns dict of device views."""
@@ -251,10 +179,24 @@ class SACFullLengthRNNEnsembleQ(SAC):
         d0, t0 = R['done'][0], R['timeout'][0]
         host[..., d0][arr[..., t0] > 0] = 0                          # time-limit terminations bootstrap
         dev = self._pinned.upload(staged, self.device)
-        return self._batch_views(dev, table)
+        return self._batch_views(dev, self._packed_seqs(table, rows, T))
 
-    def _batch_views(self, dev, table):
-        """Field / flag views of the device batch array (rows, T', W + 3)."""
+    def _packed_seqs(self, table, rows, T):
+        """Eager updates: the per-row sequence-length table (reference :358-366) as the pair of device descriptions attention layers
+        consume - the batch and its one-slot shift; None for every other layer.  Built on the host (the table is host data anyway): token
+        indices + cu_seqlens for the var-len attention kernel."""
+        if not self._needs_seq_table:
+            return None
+        built = PackedSeqs.build_host_pair(table, rows, T)
+        padded = self.shape_buckets and self.seq_buckets
+        if padded:
+            built, _ = pad_seq_tables(built, rows, T)
+        return [PackedSeqs.from_static(torch.from_numpy(idx).to(self.device), torch.from_numpy(cu).to(self.device), mx, tb, padded=padded)
+                for idx, cu, mx, tb in built]
+
+    def _batch_views(self, dev, seqs):
+        """Field / flag views of the device batch array (rows, T', W + 3); `seqs`: the pair of `PackedSeqs` of the batch and of its
+        one-slot shift (attention layers only), or None."""
         rows, T = dev.shape[:2]
         W = dev.shape[2] - 3
         R = self.replay_buffer.name2range
@@ -266,30 +208,14 @@ class SACFullLengthRNNEnsembleQ(SAC):
         ones = [n for n in out if out[n].shape[-1] == 1]
         if ones and dev.is_cuda:
             key = (tuple(ones), dev.device)
-            idx = self.__dict__.setdefault('_planar_idx', {}).get(key)
+            idx = self._planar_idx.get(key)
             if idx is None:
                 cols = [R[n][0] if n in R else {'valid': W, 'total_valid': W + 1, 'total_start': W + 2}[n] for n in ones]
                 idx = self._planar_idx[key] = torch.tensor(cols, dtype=torch.int64, device=dev.device)
             planar = dev.view(rows * T, W + 3).index_select(1, idx).t().contiguous()          # [k, rows * T]
             for i, n in enumerate(ones):
                 out[n] = planar[i].view(rows, T, 1)
-        # per-row sequence-length tables (reference :358-366) are consumed by attention layers only
-        out['attention_mask'] = out['target_attention_mask'] = None
-        if self._needs_seq_table and self._graph is not None:
-            # captured update: the tables were built by GraphedUpdate._prepare into pinned buffers; copy nodes + static device views
-            out['attention_mask'], out['target_attention_mask'] = self._graph.packed_seqs()
-        elif self._needs_seq_table:
-            am = np.zeros((rows, T), dtype=np.int32)
-            am[:, :table.shape[1]] = table
-            tam = np.concatenate((am[:, 1:], np.zeros((rows, 1), dtype=np.int32)), axis=1)
-            # built on the host (the table is host data anyway): token indices + cu_seqlens for the var-len attention kernel
-            if self.shape_buckets and self.seq_buckets:
-                built, _ = pad_seq_tables([PackedSeqs.build_host(a, T) for a in (am, tam)], rows, T)
-                out['attention_mask'], out['target_attention_mask'] = [
-                    PackedSeqs.from_static(torch.from_numpy(idx).to(self.device), torch.from_numpy(cu).to(self.device), mx, tb, padded=True)
-                    for idx, cu, mx, tb in built]
-                return out
-            out['attention_mask'], out['target_attention_mask'] = PackedSeqs(am, T, self.device), PackedSeqs(tam, T, self.device)
+        out['attention_mask'], out['target_attention_mask'] = seqs or (None, None)
         return out
 
     def _make_hidden(self, model, rows, start, mask, attn):
@@ -319,13 +245,9 @@ class SACFullLengthRNNEnsembleQ(SAC):
         """int32 device copy of a critic-subset index vector without a per-update host->device copy (a pageable copy blocks
         the host until the launch queue has drained): all ordered subsets of that size are uploaded ONCE as a table
         (8 critics, REDQ pairs: 56 rows) and a row view is returned; oversized tables fall back to a per-subset cache."""
-        import itertools
-        import math
-        if self._graph is not None and subset is self._graph.subset_np:   # captured update: the drawn subset sits in static buffers
-            return self._graph.subset_i64 if as_long else self._graph.subset_i32
         sub = np.ascontiguousarray(subset, dtype=np.int32)
         m, E = int(sub.size), int(max(num_ensemble, sub.max() + 1))
-        tables = self.__dict__.setdefault('_subset_tables', {})
+        tables = self._subset_tables
         if (E, m) not in tables:
             rows = None
             if math.perm(E, m) <= 4096:
@@ -336,7 +258,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
         rows = tables[(E, m)]
         if rows is not None and tuple(sub.tolist()) in rows[0]:
             return rows[2 if as_long else 1][rows[0][tuple(sub.tolist())]]
-        cache = self.__dict__.setdefault('_subset_cache', {})
+        cache = self._subset_cache
         key = (sub.tobytes(), as_long)
         if key not in cache:
             t = torch.from_numpy(sub.copy()).to(self.device)
@@ -364,10 +286,29 @@ class SACFullLengthRNNEnsembleQ(SAC):
             return {}
         if os.environ.get('RESEL_DP_GUARD', 'bucket') == 'allreduce':
             return dict(reduce_max=self.grad_sync.all_reduce_max_)
-        if getattr(self, '_guard_ext', None) is None or self._guard_ext.device != self.Q_guard.state.device:
+        if self._guard_ext is None or self._guard_ext.device != self.Q_guard.state.device:
             self._guard_ext = torch.zeros(4, dtype=torch.float32, device=self.Q_guard.state.device)
         self._guard_ext_fresh = True
         return dict(local_ext=self._guard_ext)
+
+    def _target_subset(self, num_ensemble: int):
+        """The critics this update's target takes its minimum over -> (host index vector: its SIZE decides whether all members are
+        evaluated, `index(as_long=False)`: the drawn indices on the device)."""
+        if self._graph is not None:                    # captured update: drawn by GraphedUpdate._prepare into static buffers, no draw here
+            return self._graph.target_subset()
+        subset = np.asarray(self._select_target_ensemble(num_ensemble))
+        return subset, functools.partial(self._subset_on_device, subset, num_ensemble)
+
+    def _target_critics(self, b, action, sample, hidden):
+        """Q'(s', a') of the drawn target critics -> (q, index).  REDQ (fewer drawn than there are): only those are evaluated (same
+        numbers: the others were never used), q holds them in draw order and `index` is None; otherwise q holds every member and
+        `index` (`_target_subset`) names the drawn ones."""
+        tv = self.target_values[0]
+        subset, index = self._target_subset(tv.uni_network.layer_list[-1].num_ensemble)
+        if subset.size < tv.uni_network.layer_list[-1].num_ensemble:
+            with _ensemble_subset(tv, index(as_long=True)):
+                return tv.forward(b['next_state'], b['state'], action, sample, hidden, b['reward'])[0], None
+        return tv.forward(b['next_state'], b['state'], action, sample, hidden, b['reward'])[0], index
 
     def _target_Q_discrete(self, b, policy_hidden, target_hiddens, stats):
         """Discrete-action target (reference sac_full_length_rnn_redq.py:52-72): V(s') = sum_a pi(a|s') (min_subset Q'(s', a) -
@@ -376,51 +317,40 @@ class SACFullLengthRNNEnsembleQ(SAC):
         with torch.no_grad():
             onehot = self.policy.action2onehot(b['action'])
             _, _, sample, logp, _, _ = self.policy.forward(b['next_state'], b['state'], onehot, policy_hidden, b['reward'])
-            tv = self.target_values[0]
-            E = tv.uni_network.layer_list[-1].num_ensemble
-            subset = np.asarray(self._select_target_ensemble(E))
-            if subset.size < E:
-                with _ensemble_subset(tv, self._subset_on_device(subset, E, as_long=True)):
-                    q = tv.forward(b['next_state'], b['state'], onehot, sample, target_hiddens[0], b['reward'])[0]
-            else:
-                q = tv.forward(b['next_state'], b['state'], onehot, sample, target_hiddens[0], b['reward'])[0][self._subset_on_device(subset, E, as_long=True)]
+            q, index = self._target_critics(b, onehot, sample, target_hiddens[0])
+            if index is not None:
+                q = q[index(as_long=True)]
             alpha = self.log_sac_alpha.detach().exp()
             v = ((q.min(dim=0).values - alpha * logp) * logp.exp()).sum(dim=-1, keepdim=True)
             return ops.sac_target(v.unsqueeze(0).contiguous(), self._subset_on_device(np.arange(1), 1), None, self.log_sac_alpha.detach(),
                                   b['reward'], b['done'], b['mask'], self.parameter.gamma, self.Q_guard.state, stats, **self._guard_exchange())
 
-    def get_target_Q(self, b, policy_hidden, target_hiddens, stats):
+    def get_target_Q(self, b, policy_hidden, target_hiddens, stats, share_policy_pass=False):
+        """-> (target, the policy's head outputs on (s', s, a) WITH a graph for the actor step to reuse one slot later - None unless
+        `share_policy_pass`)."""
         if self.discrete_env:
-            return self._target_Q_discrete(b, policy_hidden, target_hiddens, stats)
-        self._shared_policy_out = None
-        if self._share_this_update:
+            return self._target_Q_discrete(b, policy_hidden, target_hiddens, stats), None
+        shared_out = None
+        if share_policy_pass:
             with torch.enable_grad():           # one policy forward with a graph: the actor step reuses it one slot later
                 emb_in = self.policy.get_embedding_input(b['next_state'], b['state'], b['action'], b['reward'])
-                self._shared_policy_out = self.policy.meta_forward(emb_in, b['next_state'], policy_hidden, False)[0]
+                shared_out = self.policy.meta_forward(emb_in, b['next_state'], policy_hidden, False)[0]
         with torch.no_grad():
-            if self._shared_policy_out is not None:     # same head, same random draws as policy.forward would make
-                sample, logp = self._target_action(*self.policy.process_model_out(self._shared_policy_out.detach()))
+            if shared_out is not None:          # same head, same random draws as policy.forward would make
+                sample, logp = self._target_action(*self.policy.process_model_out(shared_out.detach()))
             else:
                 sample, logp = self._next_action(b, policy_hidden)
-            tv = self.target_values[0]
-            E = tv.uni_network.layer_list[-1].num_ensemble
-            subset = np.asarray(self._select_target_ensemble(E))
-            if subset.size < E:
-                # REDQ: only the sampled target critics are evaluated (same numbers: the others were never used)
-                with _ensemble_subset(tv, self._subset_on_device(subset, E, as_long=True)):
-                    q = tv.forward(b['next_state'], b['state'], b['action'], sample, target_hiddens[0], b['reward'])[0]
-                idx = self._subset_on_device(np.arange(subset.size), subset.size)
-            else:
-                q = tv.forward(b['next_state'], b['state'], b['action'], sample, target_hiddens[0], b['reward'])[0]
-                idx = self._subset_on_device(subset, E)
-            return ops.sac_target(q, idx, logp if self.base_algorithm == 'sac' else None, self.log_sac_alpha.detach(), b['reward'],
-                                  b['done'], b['mask'], self.parameter.gamma, self.Q_guard.state, stats, **self._guard_exchange())
+            q, index = self._target_critics(b, b['action'], sample, target_hiddens[0])
+            idx = self._subset_on_device(np.arange(q.shape[0]), q.shape[0]) if index is None else index()
+            target = ops.sac_target(q, idx, logp if self.base_algorithm == 'sac' else None, self.log_sac_alpha.detach(), b['reward'],
+                                    b['done'], b['mask'], self.parameter.gamma, self.Q_guard.state, stats, **self._guard_exchange())
+        return target, shared_out
 
     # ------------------------------------------------------------------------------------------ losses
     actor_q_reduce = 'min'                           # how the actor objective reduces the critics (REDQ trainers: 'mean'); names the fused kernel's mode
 
     def _q_for_policy(self, qs: torch.Tensor) -> torch.Tensor:
-        return qs.min(dim=0).values                                  # (REDQ trainers use the ensemble mean)
+        return qs.min(dim=0).values if self.actor_q_reduce == 'min' else qs.mean(dim=0)
 
     def _actor_objective(self, alpha, logp, q_pi):
         return alpha * logp - q_pi                                   # (TD3 trainers drop the entropy term)
@@ -457,7 +387,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
         joins before anything reads the reduced buffer."""
         store.collect_grads()
         gs = self.grad_sync
-        guard_slots = gs.active and guard and getattr(self, '_guard_ext_fresh', False)
+        guard_slots = gs.active and guard and self._guard_ext_fresh
         if guard_slots:                                # this rank's row of the [world][4] extrema block behind the four standing slots
             store.ensure_grad_extra(4 + 4 * gs.world)
             o = store.numel + 4 + 4 * gs.rank
@@ -481,166 +411,186 @@ class SACFullLengthRNNEnsembleQ(SAC):
 
     # ------------------------------------------------------------------------------------------ the update
     def train_one_batch(self) -> Dict:
-        from ..models.rnn_base import training_pass
         with training_pass():                                    # no pass of an update reads the per-layer output sequences (rnn_base.py)
-            return self._train_one_batch()
+            if self.device.type == 'cuda':
+                ops.amax_maintenance()                           # update boundary: the magnitude epochs may start over here (hip/ops.py)
+            log = self._train_one_batch()
+            if ops.AMAX_VERIFY and self.device.type == 'cuda':   # RESEL_AMAX_VERIFY=1: every mode-2 product of this update had its handles checked
+                ops.amax_verify_raise(self.device)
+            return log
 
     def _train_one_batch(self) -> Dict:
+        """One update: sample -> hidden states -> target -> critic step -> soft update -> actor step (if due) -> log.  Entered by the eager
+        `train_one_batch` and, while a GraphedUpdate records or launches the update from its static inputs, by its `_body`."""
         par = self.parameter
-        if self._graph is None and self.device.type == 'cuda':
-            ops.amax_maintenance()                               # update boundary: the magnitude epochs may start over here (hip/ops.py)
         self.policy.to(self.device)
         self.optimizer_policy.to(self.device)
-        policy_update_cnt = 0
+        actor_steps = 0
         scal: Dict[str, torch.Tensor] = {}
         host: Dict[str, float] = {}
         for utd_idx in range(par.utd):
-            self.timer.register_point(tag='sample_trajs', level=2)
-            real_rows = None
-            if self._graph is not None:
-                # captured update (algorithm/graphed_update.py): the host half of the sampling ran before the replay, the plan sits in
-                # static buffers; here only the device half is enqueued (a memcpy node + the gather kernel)
-                dev, batch_size, table = self._graph.gather()
-                self.timer.register_end(level=2)
-                b = self._batch_views(dev, table)
-            elif getattr(self, 'device_replay', False) and self.device.type == 'cuda' \
-                    and self.replay_buffer.device_supported(randomize_mask=par.randomize_mask):
-                # device-resident ring: the host decides WHICH trajectories go where, the batch array is built on the GPU
-                if self.shape_buckets and self._needs_seq_table and not self.seq_buckets:
-                    raise RuntimeError('shape_buckets: ' + NO_SEQ_BUCKETS)
-                dev, batch_size, table = self.replay_buffer.sample_trajs_device(
-                    self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack,
-                    buckets=self.shape_buckets, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized)
-                real_rows = self.replay_buffer._last_real_rows
-                self.timer.register_end(level=2)
-                b = self._batch_views(dev, table)
-            else:
-                if self.shape_buckets:
-                    raise RuntimeError('shape_buckets: only batches assembled from the device replay ring are bucketed')
-                batch, batch_size, valid, table = self.replay_buffer.sample_trajs(
-                    par.sac_batch_size, None, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized,
-                    equalize_data_of_each_traj=True, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack)
-                self.timer.register_end(level=2)
-                b = self._upload_batch(batch, valid, table)
-            rows = b['state'].shape[0]
-            real_rows = real_rows or rows                        # rows drawn: fewer than `rows` only for a bucketed batch
-            value, target_value = self.values[0], self.target_values[0]
-            # hidden states + side channels: the target pass uses the one-slot-earlier flags (reference :368-378)
-            target_policy_hidden = self._make_hidden(self.policy, rows, b['total_start'], b['total_valid'], b['target_attention_mask'])
-            target_hiddens = [self._make_hidden(target_value, rows, b['total_start'], b['total_valid'], b['target_attention_mask'])]
-            value_hiddens = [self._make_hidden(value, rows, b['start'], b['valid'], b['attention_mask'])]
-            policy_hidden = self._make_hidden(self.policy, rows, b['start'], b['valid'], b['attention_mask'])
+            b, batch_size, real_rows = self._sample()
+            hidden = self._hidden_states(b)
             alpha_detach = self.log_sac_alpha.exp().detach()
-            mask = b['mask']
-
-            # 1. target (no grad); guard clamp/update + max|target| + sum(mask) happen inside the fused kernel
-            actor_due = self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > policy_update_cnt
-            self._share_this_update = self.share_policy_pass and actor_due
-            self.policy.eval()
-            if self.gru_batch:
-                # latency-bound layers, one stream: the three embedding passes of this phase - (target) policy and target critic on the
-                # shifted inputs without a graph, the critic with one - run in lockstep, their recurrences in ONE launch; the target
-                # computation and the critic forward below pick their embeddings up
-                value.train()
-                shifted = (b['next_state'], b['state'], b['action'], b['reward'])
-                ContextualModel.prefetch_embeddings([
-                    (self.policy if self.target_from_live_policy else self.target_policy, shifted, target_policy_hidden, False),
-                    (target_value, shifted, target_hiddens[0], False),
-                    (value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), value_hiddens[0], True)])
-            target_Q = self.get_target_Q(b, target_policy_hidden, target_hiddens, self._stats)
+            actor_due = self._actor_due(utd_idx, actor_steps)
+            target_Q, shared_out = self._target(b, hidden, share_policy_pass=self.share_policy_pass and actor_due)
             valid_num = self._stats[1]
-
-            # 2. critic step
-            value.train()
-            q = value.forward(b['state'], b['last_state'], b['last_action'], b['action'], value_hiddens[0], b['reward_input'])[0]
-            if self.discrete_env:                                   # Q of the action taken (reference :158)
-                q = q.gather(-1, b['action'].long().unsqueeze(0).expand(q.shape[0], -1, -1, -1))
-            if FUSED_Q and q.is_cuda and q.dtype == torch.float32:
-                q_loss_sum = ops.masked_q_loss(q, target_Q, mask)         # one forward + one backward kernel (reference :105-114, :80-81)
-            else:
-                q_loss_sum = ((q - target_Q.unsqueeze(0)).pow(2).sum(dim=0) * mask).sum()
-            self.optimizer_value.zero_grad()
-            q_loss_sum.backward()
-            scale = self._finish_step(self.optimizer_value, value.store, valid_num, guard=True,
-                                      overlap=lambda: scal.update(critic_loss=q_loss_sum.detach() / valid_num))
-            q_grad_norm = self._clip(value.store, value, par.value_max_gradnorm, par.value_embedding_max_gradnorm, scale)
-            self.optimizer_value.step(grad_scale=scale)
-            host['value_grad_norm'] = q_grad_norm
-
-            # 3. soft target update: one kernel over the flat buffers
-            self._value_update(tau=par.sac_tau)
-            value.eval()
+            self._critic_step(b, hidden, target_Q, valid_num, scal, host)
+            self._value_update(tau=par.sac_tau)                  # soft target update: one kernel over the flat buffers
+            self.values[0].eval()
             self.policy.train()
-
-            # 4. actor (+ alpha) step
-            if self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > policy_update_cnt:
-                if self.gru_batch:                                 # the actor's pass (with a graph) and the critic's embedding (without) together
-                    now = (b['state'], b['last_state'], b['last_action'], b['reward_input'])
-                    ContextualModel.prefetch_embeddings([(self.policy, now, policy_hidden, True), (value, now, value_hiddens[0], False)])
-                if self._shared_policy_out is not None:            # the target pass's head outputs, one slot later
-                    out2 = torch.nn.functional.pad(self._shared_policy_out[:, :-1], (0, 0, 1, 0))
-                    self._shared_policy_out = None
-                    action_mean, act_sample, log_prob = self.policy.process_model_out(out2)
-                else:
-                    action_mean, _, act_sample, log_prob, _, _ = self.policy.forward(b['state'], b['last_state'], b['last_action'],
-                                                                                    policy_hidden, b['reward_input'])
-                act_in = act_sample if self.base_algorithm == 'sac' else action_mean
-                # the actor objective differentiates Q only w.r.t. the action: the critic's parameters are frozen while its graph
-                # is recorded, so that the backward does not form the critic weight gradients the reference computes and drops
-                with _frozen_parameters(value):
-                    q_pi = value.forward(b['state'], b['last_state'], b['last_action'], act_in, value_hiddens[0], b['reward_input'],
-                                         detach_embedding=True)[0]
-                if self.discrete_env:                               # expectation over the action distribution (reference redq :85-86)
-                    objective = (self._actor_objective(alpha_detach, log_prob, self._q_for_policy(q_pi)) * log_prob.exp()).sum(dim=-1, keepdim=True)
-                    log_prob = (log_prob * log_prob.exp()).sum(dim=-1, keepdim=True)          # logged as -entropy (:425)
-                    actor_sum = (objective * mask).sum()
-                    lp_sum = None
-                elif FUSED_A and q_pi.is_cuda and q_pi.dtype == torch.float32 and self.base_algorithm == 'sac' and self.actor_q_reduce in ('min', 'mean'):
-                    # sum mask (alpha logp - red_e Q) and sum mask logp from one pass, gradients from one more (reference redq :37-49)
-                    actor_sum, lp_sum = ops.masked_actor_loss(log_prob, q_pi, mask, self.log_sac_alpha, True, self.actor_q_reduce == 'min')
-                else:
-                    objective = self._actor_objective(alpha_detach, log_prob, self._q_for_policy(q_pi))
-                    actor_sum = (objective * mask).sum()
-                    lp_sum = None
-                if lp_sum is None:
-                    lp_sum = (log_prob.detach() * mask).sum()
-                self.optimizer_policy.zero_grad()
-                actor_sum.backward(inputs=self.policy.parameters())
-                pstore = self.policy.store
-                tune_alpha = not par.no_alpha_auto_tune
-                if tune_alpha:     # d/d log_alpha of -sum(mask * log_alpha * (logp + H)) rides in the second spare slot
-                    pstore.grad[pstore.numel + 1] = -(lp_sum + self.target_entropy * valid_num)
-                scale = self._finish_step(self.optimizer_policy, pstore, valid_num, overlap=lambda: scal.update(
-                    log_prob=lp_sum / valid_num, actor_loss=actor_sum.detach() / valid_num))
-                pi_grad_norm = self._clip(pstore, self.policy, par.policy_max_gradnorm, par.policy_embedding_max_gradnorm, scale)
-                self.optimizer_policy.step(grad_scale=scale)
-                if tune_alpha:
-                    g_alpha = pstore.grad[pstore.numel + 1:pstore.numel + 2] / pstore.grad[pstore.numel:pstore.numel + 1]
-                    scal['alpha_loss'] = (self.log_sac_alpha.detach() * g_alpha)[0]
-                    self.log_sac_alpha.grad = g_alpha.clone()
-                    self.optimizer_alpha.step()
-                    with torch.no_grad():
-                        self.log_sac_alpha.clamp_max_(1)
-                scal['policy_l2_norm_square'] = self.policy.l2_norm_square()
-                host['policy_grad_norm'] = pi_grad_norm
-                policy_update_cnt += 1
+            if actor_due:
+                self._actor_step(b, hidden, shared_out, alpha_detach, valid_num, scal, host)
+                actor_steps += 1
         self.policy.to(self.sample_device)
+        return self._log(scal, host, batch_size, real_rows)
+
+    def _actor_due(self, utd_idx, done_so_far) -> bool:
+        """Does the actor (+ alpha) step follow critic step `utd_idx` of this update, `done_so_far` actor steps into it (reference :450-452)?"""
+        par = self.parameter
+        return self.grad_num % par.policy_update_per == 0 and (utd_idx + 1) / par.utd * par.policy_utd > done_so_far
+
+    def _sample(self):
+        """One packed batch -> (its field views on the device, transitions drawn, rows drawn: fewer than the batch has only if bucketed)."""
+        par = self.parameter
+        self.timer.register_point(tag='sample_trajs', level=2)
+        if self._graph is not None:
+            # captured update (algorithm/graphed_update.py): the host half of the sampling ran before the replay, the plan sits in
+            # static buffers; here only the device half is enqueued (a memcpy node + the gather kernel).  Sequence tables: built by
+            # GraphedUpdate._prepare into pinned buffers; copy nodes + static device views
+            dev, batch_size, real_rows = self._graph.gather()
+            seqs = self._graph.packed_seqs()
+        elif self.device_replay and self.device.type == 'cuda' and self.replay_buffer.device_supported(randomize_mask=par.randomize_mask):
+            # device-resident ring: the host decides WHICH trajectories go where, the batch array is built on the GPU
+            if self.shape_buckets and self._needs_seq_table and not self.seq_buckets:
+                raise RuntimeError('shape_buckets: ' + NO_SEQ_BUCKETS)
+            dev, batch_size, table = self.replay_buffer.sample_trajs_device(
+                self.device, par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack,
+                buckets=self.shape_buckets, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized)
+            real_rows = self.replay_buffer._last_real_rows
+            seqs = self._packed_seqs(table, *dev.shape[:2])
+        else:
+            if self.shape_buckets:
+                raise RuntimeError('shape_buckets: only batches assembled from the device replay ring are bucketed')
+            batch, batch_size, valid, table = self.replay_buffer.sample_trajs(
+                par.sac_batch_size, None, randomize_mask=par.randomize_mask, valid_number_post_randomized=par.valid_number_post_randomized,
+                equalize_data_of_each_traj=True, random_trunc_traj=par.random_trunc_traj, nest_stack_trajs=self.allow_nest_stack)
+            self.timer.register_end(level=2)
+            b = self._upload_batch(batch, valid, table)
+            return b, batch_size, b['state'].shape[0]
+        self.timer.register_end(level=2)
+        return self._batch_views(dev, seqs), batch_size, real_rows or dev.shape[0]
+
+    def _hidden_states(self, b):
+        """Hidden states + side channels of the four passes; the target passes use the one-slot-earlier flags (reference :368-378)."""
+        rows = b['state'].shape[0]
+        value, target_value = self.values[0], self.target_values[0]
+        return dict(target_policy=self._make_hidden(self.policy, rows, b['total_start'], b['total_valid'], b['target_attention_mask']),
+                    target_value=self._make_hidden(target_value, rows, b['total_start'], b['total_valid'], b['target_attention_mask']),
+                    value=self._make_hidden(value, rows, b['start'], b['valid'], b['attention_mask']),
+                    policy=self._make_hidden(self.policy, rows, b['start'], b['valid'], b['attention_mask']))
+
+    def _target(self, b, hidden, share_policy_pass):
+        """Target (no grad); guard clamp/update + max|target| + sum(mask) happen inside the fused kernel -> `get_target_Q`'s pair."""
+        value, target_value = self.values[0], self.target_values[0]
+        self.policy.eval()
+        if self.gru_batch:
+            # latency-bound layers, one stream: the three embedding passes of this phase - (target) policy and target critic on the
+            # shifted inputs without a graph, the critic with one - run in lockstep, their recurrences in ONE launch; the target
+            # computation and the critic forward below pick their embeddings up
+            value.train()
+            shifted = (b['next_state'], b['state'], b['action'], b['reward'])
+            ContextualModel.prefetch_embeddings([
+                (self.policy if self.target_from_live_policy else self.target_policy, shifted, hidden['target_policy'], False),
+                (target_value, shifted, hidden['target_value'], False),
+                (value, (b['state'], b['last_state'], b['last_action'], b['reward_input']), hidden['value'], True)])
+        return self.get_target_Q(b, hidden['target_policy'], [hidden['target_value']], self._stats, share_policy_pass)
+
+    def _critic_step(self, b, hidden, target_Q, valid_num, scal, host):
+        par, value, mask = self.parameter, self.values[0], b['mask']
+        value.train()
+        q = value.forward(b['state'], b['last_state'], b['last_action'], b['action'], hidden['value'], b['reward_input'])[0]
+        if self.discrete_env:                                   # Q of the action taken (reference :158)
+            q = q.gather(-1, b['action'].long().unsqueeze(0).expand(q.shape[0], -1, -1, -1))
+        if q.is_cuda and q.dtype == torch.float32:
+            q_loss_sum = ops.masked_q_loss(q, target_Q, mask)         # one forward + one backward kernel (csrc/losses.hip; reference :105-114, :80-81)
+        else:                                                   # CPU tensors keep the torch spelling
+            q_loss_sum = ((q - target_Q.unsqueeze(0)).pow(2).sum(dim=0) * mask).sum()
+        self.optimizer_value.zero_grad()
+        q_loss_sum.backward()
+        scale = self._finish_step(self.optimizer_value, value.store, valid_num, guard=True,
+                                  overlap=lambda: scal.update(critic_loss=q_loss_sum.detach() / valid_num))
+        q_grad_norm = self._clip(value.store, value, par.value_max_gradnorm, par.value_embedding_max_gradnorm, scale)
+        self.optimizer_value.step(grad_scale=scale)
+        host['value_grad_norm'] = q_grad_norm
+
+    def _actor_step(self, b, hidden, shared_out, alpha_detach, valid_num, scal, host):
+        """Actor (+ alpha) step on the live critics; `shared_out`: the target pass's head outputs (`get_target_Q`) or None."""
+        par, value, mask = self.parameter, self.values[0], b['mask']
+        if self.gru_batch:                                 # the actor's pass (with a graph) and the critic's embedding (without) together
+            now = (b['state'], b['last_state'], b['last_action'], b['reward_input'])
+            ContextualModel.prefetch_embeddings([(self.policy, now, hidden['policy'], True), (value, now, hidden['value'], False)])
+        if shared_out is not None:                         # the target pass's head outputs, one slot later
+            out2 = torch.nn.functional.pad(shared_out[:, :-1], (0, 0, 1, 0))
+            action_mean, act_sample, log_prob = self.policy.process_model_out(out2)
+        else:
+            action_mean, _, act_sample, log_prob, _, _ = self.policy.forward(b['state'], b['last_state'], b['last_action'],
+                                                                            hidden['policy'], b['reward_input'])
+        act_in = act_sample if self.base_algorithm == 'sac' else action_mean
+        # the actor objective differentiates Q only w.r.t. the action: the critic's parameters are frozen while its graph
+        # is recorded, so that the backward does not form the critic weight gradients the reference computes and drops
+        with _frozen_parameters(value):
+            q_pi = value.forward(b['state'], b['last_state'], b['last_action'], act_in, hidden['value'], b['reward_input'],
+                                 detach_embedding=True)[0]
+        lp_sum = None
+        if self.discrete_env:                               # expectation over the action distribution (reference redq :85-86)
+            objective = (self._actor_objective(alpha_detach, log_prob, self._q_for_policy(q_pi)) * log_prob.exp()).sum(dim=-1, keepdim=True)
+            log_prob = (log_prob * log_prob.exp()).sum(dim=-1, keepdim=True)          # logged as -entropy (:425)
+            actor_sum = (objective * mask).sum()
+        elif q_pi.is_cuda and q_pi.dtype == torch.float32 and self.base_algorithm == 'sac' and self.actor_q_reduce in ('min', 'mean'):
+            # sum mask (alpha logp - red_e Q) and sum mask logp from one pass, gradients from one more (reference redq :37-49)
+            actor_sum, lp_sum = ops.masked_actor_loss(log_prob, q_pi, mask, self.log_sac_alpha, True, self.actor_q_reduce == 'min')
+        else:                                               # CPU tensors, TD3: the torch spelling
+            objective = self._actor_objective(alpha_detach, log_prob, self._q_for_policy(q_pi))
+            actor_sum = (objective * mask).sum()
+        if lp_sum is None:
+            lp_sum = (log_prob.detach() * mask).sum()
+        self.optimizer_policy.zero_grad()
+        actor_sum.backward(inputs=self.policy.parameters())
+        pstore = self.policy.store
+        tune_alpha = not par.no_alpha_auto_tune
+        if tune_alpha:     # d/d log_alpha of -sum(mask * log_alpha * (logp + H)) rides in the second spare slot
+            pstore.grad[pstore.numel + 1] = -(lp_sum + self.target_entropy * valid_num)
+        scale = self._finish_step(self.optimizer_policy, pstore, valid_num, overlap=lambda: scal.update(
+            log_prob=lp_sum / valid_num, actor_loss=actor_sum.detach() / valid_num))
+        pi_grad_norm = self._clip(pstore, self.policy, par.policy_max_gradnorm, par.policy_embedding_max_gradnorm, scale)
+        self.optimizer_policy.step(grad_scale=scale)
+        if tune_alpha:
+            g_alpha = pstore.grad[pstore.numel + 1:pstore.numel + 2] / pstore.grad[pstore.numel:pstore.numel + 1]
+            scal['alpha_loss'] = (self.log_sac_alpha.detach() * g_alpha)[0]
+            self.log_sac_alpha.grad = g_alpha.clone()
+            self.optimizer_alpha.step()
+            with torch.no_grad():
+                self.log_sac_alpha.clamp_max_(1)
+        scal['policy_l2_norm_square'] = self.policy.l2_norm_square()
+        host['policy_grad_norm'] = pi_grad_norm
+
+    def _host_log(self, batch_size, real_rows):
+        """The log entries that never were on the device (reference :455-467; no loss scaling here: fp32 / bf16 paths need none)."""
+        return dict(real_batch_size=batch_size, real_batch_traj_num=real_rows,
+                    average_traj_len=self.replay_buffer.size / len(self.replay_buffer), amp_scalar_pi=0, amp_scalar_q=0)
+
+    def _log(self, scal, host, batch_size, real_rows):
         scal.update(log_alpha=self.log_sac_alpha.detach()[0], target_q_max=self._stats[0], clip_min=self.Q_guard.state[0],
                     clip_max=self.Q_guard.state[1], q1_l2_norm_square=self.values[0].l2_norm_square())
         for k in [k for k, v in host.items() if torch.is_tensor(v)]:      # clipped runs: the norm is a device scalar
             scal[k] = host.pop(k).detach()
         keys = list(scal)
         packed = torch.stack([scal[k].reshape(()).float() for k in keys])
-        if self._graph is not None:                              # captured update: a D2H node into the graph's static pinned buffer
-            return self._graph.log_node(keys, packed, host, dict(real_batch_size=batch_size, real_batch_traj_num=real_rows,
-                                                                  average_traj_len=self.replay_buffer.size / len(self.replay_buffer),
-                                                                  amp_scalar_pi=0, amp_scalar_q=0))
-        if ops.AMAX_VERIFY and self.device.type == 'cuda':       # RESEL_AMAX_VERIFY=1: every mode-2 product of this update had its handles checked
-            ops.amax_verify_raise(self.device)
-        log = DeferredLog(keys, packed, pinned=self.device.type == 'cuda')     # ONE device->host copy of all scalars
-        log.set_host({k: float(v) for k, v in host.items()})
-        log.set_host(dict(real_batch_size=batch_size, real_batch_traj_num=real_rows,
-                          average_traj_len=self.replay_buffer.size / len(self.replay_buffer), amp_scalar_pi=0, amp_scalar_q=0))
-        if not getattr(self, 'defer_log', False):
+        items = dict({k: float(v) for k, v in host.items()}, **self._host_log(batch_size, real_rows))
+        if self._graph is not None:                              # captured update: a copy node into the graph's static buffer, read back behind the replay
+            return self._graph.log_node(keys, packed, items)
+        log = DeferredLog.from_packed(keys, packed, self.device.type == 'cuda', items)     # ONE device->host copy of all scalars
+        if not self.defer_log:
             log.resolve()                                        # reference behaviour: floats in hand when the call returns
         return log

@@ -11,6 +11,3 @@ class TD3FullLengthRNNREDQ(TD3FullLengthRNNEnsembleQ):
         return self._subset_stream().permutation(num_ensemble)[:self.parameter.redq_m]
 
     actor_q_reduce = 'mean'
-
-    def _q_for_policy(self, qs):
-        return qs.mean(dim=0)

@@ -21,6 +21,9 @@ MIN_TOKENS = 256                                      # token tables shorter tha
 MIN_SEQS = 16
 ATTN_BLOCK = 128                                      # tokens per attention workgroup: the longest-sequence bound is a multiple of it
 
+NO_SEQ_BUCKETS = 'shape buckets do not cover layers that need sequence tables (cgpt): the token and cu_seqlens tables vary with the batch ' \
+                 'and are bucketed only with seq_buckets (RESEL_GRAPH_SEQ_BUCKETS=1)'
+
 
 def ladder(x):
     """Smallest member of {2^k, 3 * 2^(k-1)} that is >= x: 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, ... (at most 1.5x growth)."""
