@@ -633,6 +633,45 @@ int resel_step_state_reset(const int32_t* flags, int B, resel_reset_segs_t segs,
 int resel_categorical_step(const float* logits, int64_t ld_logits, const float* u, float floor, float* logp, int64_t ld_logp,
                            float* mode, float* sample, int64_t ld_idx, int M, int A, resel_stream_t stream);
 
+/* ---- discrete-action update: differentiable categorical head, all-action value, the two discrete losses --------------------
+ * (reference contextual_sac_discrete_policy.py:106-121 on whole rows; sac_full_length_rnn_redq.py:52-72 target, :85-86 actor,
+ * sac_full_length_rnn_ensembleQ.py:158 critic on the action taken).  Raw fp32 device pointers; logits / logp / probs [M, A];
+ * q / dq [E, M, A] contiguous, A fastest; mask / y / v / action [M]; g and log_alpha device scalars.  Every entry returns
+ * RESEL_EINVAL before the device is touched for a NULL required pointer, A < 1, A > RESEL_CATEGORICAL_MAX_ACTIONS, E < 1 or M < 0;
+ * M == 0 launches nothing and returns 0.  No host read, no device assert, no atomics (sums are two-stage in a fixed order: bitwise
+ * reproducible), capturable.
+ *
+ * head, forward: the four steps of resel_categorical_step (one shared device function) on every row: logp = log p, probs = p,
+ *   mode [M] = the lowest argmax of p as fp32; no sampling.  A row holding a NaN gets NaN in all of its logp and probs and mode 0;
+ *   other rows are unaffected.  A row takes the next power of two at or above A lanes (at most 64), a wave 64 / that rows; A > 64
+ *   runs the chunked loop of the step kernel.
+ * head, backward: dlogp or dprobs may be NULL (both NULL: RESEL_EINVAL).  With s = softmax(x), S2 = sum(s + floor), p the final
+ *   probabilities:  g_i = dprobs_i + dlogp_i / p_i;  dp_i = g_i - sum_j g_j p_j;  ds_i = dp_i / S2;  dx_i = s_i (ds_i - sum_j ds_j s_j).
+ *   s and p are recomputed from the logits, so the call takes the same `floor` as the forward.  A = 1: dlogits is exactly 0. */
+int resel_categorical_fwd(const float* logits, float floor, float* logp, float* probs, float* mode, int M, int A, resel_stream_t stream);
+int resel_categorical_bwd(const float* logits, float floor, const float* dlogp, const float* dprobs, float* dlogits, int M, int A,
+                          resel_stream_t stream);
+/* all-action value (no gradient):  v[r] = sum_a exp(logp[r, a]) (min_{e in S} q[e, r, a] - exp(log_alpha) logp[r, a]);  S = the m
+ * entries of subset (int32, device; clamped into [0, E)) or, subset == NULL, all E members (m is ignored).  A NaN member gives NaN. */
+int resel_discrete_value(const float* q, const int32_t* subset, int m, const float* logp, const float* log_alpha, float* v,
+                         int E, int M, int A, resel_stream_t stream);
+/* critic loss on the action taken: action [M] is the fp32 index as the batch stores it, clamped into [0, A) before the read (NaN: 0).
+ *   out2[0] = sum_m mask sum_e (q[e, m, a_m] - y[m])^2                                  (mask NULL = ones)
+ *   dq[e, m, a] = 2 g[0] mask (q[e, m, a_m] - y[m]) at a = a_m, 0 elsewhere; EVERY element of dq is written; rows with mask == 0 get 0.
+ * workspace: resel_masked_loss_workspace_bytes(). */
+int resel_q_taken_loss_fwd(const float* q, const float* action, const float* y, const float* mask, float* out2, void* workspace,
+                           int E, int M, int A, resel_stream_t stream);
+int resel_q_taken_loss_bwd(const float* q, const float* action, const float* y, const float* mask, const float* g, float* dq,
+                           int E, int M, int A, resel_stream_t stream);
+/* actor loss as an expectation over all actions: p = exp(logp), alpha = exp(log_alpha), Q_a = min_e (reduce_min 1) or mean_e (0) q[e, ., a]
+ *   out2[0] = sum_m mask sum_a p_a (alpha logp_a - Q_a),   out2[1] = sum_m mask sum_a p_a logp_a   (a statistic: no gradient)
+ *   dlogp[m, a] = g[0] mask p_a (alpha (logp_a + 1) - Q_a)
+ *   dq (may be NULL: not formed) = -g[0] mask p_a / E (mean)  or  -g[0] mask p_a at the FIRST minimal member, 0 elsewhere (min). */
+int resel_discrete_actor_loss_fwd(const float* logp, const float* q, const float* mask, const float* log_alpha, float* out2,
+                                  void* workspace, int E, int M, int A, int reduce_min, resel_stream_t stream);
+int resel_discrete_actor_loss_bwd(const float* logp, const float* q, const float* mask, const float* log_alpha, const float* g,
+                                  float* dlogp, float* dq, int E, int M, int A, int reduce_min, resel_stream_t stream);
+
 /* ---- C = W^T N over a very long reduction dimension (weight gradients of the narrow Mamba projections) ----------------
  * Replaces autograd's `grad.t() @ input` of the x_proj / dt_proj F.linear calls (reference
  * models/smamba/mamba_ssm/ops/selective_scan_interface_new.py:261-335; models/smamba/mamba.py:231-233).

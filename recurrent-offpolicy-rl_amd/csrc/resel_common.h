@@ -58,6 +58,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// sum over aligned groups of W lanes (W a power of two <= 64), result in every lane of the group; W = 64 is wave_sum, step for step
+template <int W>
+__device__ __forceinline__ float seg_sum(float v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// lanes a row of A entries gets when rows are packed into a wave: the next power of two at or above A, at most 64
+inline int row_lanes(int A) {
+    int w = 1;
+    while (w < A && w < 64) w <<= 1;
+    return w;
+}
+
 // Column sums of row-major partial slabs in a fixed order (bitwise reproducible): out[o(c)] = sum_{k<K} part[k * ld + c],
 // c < C.  With taps == 0 the output index is c; otherwise the columns are [ch][padded taps KT] and only the last `taps`
 // of every KT go out, as out[ch * taps + tap].  256 threads = 16 columns x 16 row groups; grid = ceil(C / 16) blocks.

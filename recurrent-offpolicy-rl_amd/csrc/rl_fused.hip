@@ -101,6 +101,46 @@ __global__ __launch_bounds__(256) void target_v_kernel(const float* __restrict__
     }
     block_reduce4(mn, mx, 0.f, 0.f, part + 4 * blockIdx.x);
 }
+// Discrete actions (reference sac_full_length_rnn_redq.py:52-72): v[r] = sum_a exp(logp[r, a]) (min_{e in S} q[e, r, a] - alpha logp[r, a]).
+// A row gets W = row_lanes(A) lanes, a wave 64 / W rows (the packing of csrc/categorical.hip): lane l owns the actions l, l + W, ...,
+// consecutive lanes read consecutive addresses of q and logp, and the row sum is an xor-shuffle tree inside the lane group - a fixed
+// order.  A NaN member makes its action's minimum NaN, as q.min(dim=0) does.  subset entries are clamped into [0, E).
+template <int W>
+__global__ __launch_bounds__(256) void discrete_value_kernel(const float* __restrict__ q, const int32_t* __restrict__ subset, int n_sub,
+                                                             const float* __restrict__ logp, const float* __restrict__ log_alpha,
+                                                             float* __restrict__ v, int E, int M, int A) {
+    const int lane = threadIdx.x & (W - 1);
+    const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / W) + ((threadIdx.x & 63) / W);
+    const int64_t MA = (int64_t)M * A;
+    const bool live = row < M;                        // lane groups past the last row only take part in the shuffles
+    const float alpha = expf(log_alpha[0]);
+    float acc = 0.f;
+    if (live) {
+        for (int a = lane; a < A; a += W) {
+            const int64_t i = row * A + a;
+            float val = INFINITY;
+            bool bad = false;
+            for (int k = 0; k < n_sub; ++k) {
+                const int e = subset ? min(max(subset[k], 0), E - 1) : k;
+                const float x = q[e * MA + i];
+                bad |= x != x;
+                val = fminf(val, x);
+            }
+            if (bad) val = NAN;
+            const float lp = logp[i];
+            acc += expf(lp) * (val - alpha * lp);
+        }
+    }
+    acc = seg_sum<W>(acc);
+    if (live && lane == 0) v[row] = acc;
+}
+template <int W>
+void launch_discrete_value(const float* q, const int32_t* subset, int n_sub, const float* logp, const float* log_alpha, float* v, int E, int M,
+                           int A, hipStream_t s) {
+    const int64_t rows_per_block = 4 * (64 / W);
+    hipLaunchKernelGGL(discrete_value_kernel<W>, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, s, q, subset, n_sub,
+                       logp, log_alpha, v, E, M, A);
+}
 __global__ __launch_bounds__(256) void guard_init_kernel(const float* __restrict__ part, int nblk, float* guard) {
     float mn = INFINITY, mx = -INFINITY;
     for (int i = threadIdx.x; i < nblk; i += 256) { mn = fminf(mn, part[4 * i]); mx = fmaxf(mx, part[4 * i + 1]); }
@@ -280,6 +320,25 @@ extern "C" int resel_sac_target(const float* q, const int32_t* subset, int m, co
     hipLaunchKernelGGL(guard_init_kernel, dim3(1), dim3(256), 0, s, part1, nblk, guard);
     hipLaunchKernelGGL(target_y_kernel, dim3(nblk), dim3(256), 0, s, v, reward, done, mask, gamma, guard, target, part2, M);
     hipLaunchKernelGGL(guard_update_kernel, dim3(1), dim3(256), 0, s, part2, nblk, guard, stats);
+    return launch_status();
+}
+
+extern "C" int resel_discrete_value(const float* q, const int32_t* subset, int m, const float* logp, const float* log_alpha, float* v,
+                                    int E, int M, int A, resel_stream_t stream) {
+    if (!q || !logp || !log_alpha || !v || (subset && m < 1)) return RESEL_EINVAL;
+    if (E < 1 || M < 0 || A < 1 || A > RESEL_CATEGORICAL_MAX_ACTIONS) return RESEL_EINVAL;
+    if (M == 0) return RESEL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int n_sub = subset ? m : E;
+    switch (row_lanes(A)) {
+        case 1: launch_discrete_value<1>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        case 2: launch_discrete_value<2>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        case 4: launch_discrete_value<4>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        case 8: launch_discrete_value<8>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        case 16: launch_discrete_value<16>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        case 32: launch_discrete_value<32>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+        default: launch_discrete_value<64>(q, subset, n_sub, logp, log_alpha, v, E, M, A, s); break;
+    }
     return launch_status();
 }
 

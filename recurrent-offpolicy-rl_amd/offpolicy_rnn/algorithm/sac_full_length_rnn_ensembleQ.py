@@ -318,10 +318,13 @@ class SACFullLengthRNNEnsembleQ(SAC):
             onehot = self.policy.action2onehot(b['action'])
             _, _, sample, logp, _, _ = self.policy.forward(b['next_state'], b['state'], onehot, policy_hidden, b['reward'])
             q, index = self._target_critics(b, onehot, sample, target_hiddens[0])
-            if index is not None:
-                q = q[index(as_long=True)]
-            alpha = self.log_sac_alpha.detach().exp()
-            v = ((q.min(dim=0).values - alpha * logp) * logp.exp()).sum(dim=-1, keepdim=True)
+            if ops.discrete_fused(q):                   # minimum over the drawn members, entropy term and expectation in one kernel
+                v = ops.discrete_value(q, None if index is None else index(), logp, self.log_sac_alpha.detach())
+            else:
+                if index is not None:
+                    q = q[index(as_long=True)]
+                alpha = self.log_sac_alpha.detach().exp()
+                v = ((q.min(dim=0).values - alpha * logp) * logp.exp()).sum(dim=-1, keepdim=True)
             return ops.sac_target(v.unsqueeze(0).contiguous(), self._subset_on_device(np.arange(1), 1), None, self.log_sac_alpha.detach(),
                                   b['reward'], b['done'], b['mask'], self.parameter.gamma, self.Q_guard.state, stats, **self._guard_exchange())
 
@@ -510,9 +513,12 @@ class SACFullLengthRNNEnsembleQ(SAC):
         par, value, mask = self.parameter, self.values[0], b['mask']
         value.train()
         q = value.forward(b['state'], b['last_state'], b['last_action'], b['action'], hidden['value'], b['reward_input'])[0]
-        if self.discrete_env:                                   # Q of the action taken (reference :158)
+        taken_in_loss = self.discrete_env and ops.discrete_fused(q)
+        if self.discrete_env and not taken_in_loss:             # Q of the action taken (reference :158)
             q = q.gather(-1, b['action'].long().unsqueeze(0).expand(q.shape[0], -1, -1, -1))
-        if q.is_cuda and q.dtype == torch.float32:
+        if taken_in_loss:                                       # ... picked inside the loss kernels; dq comes back dense, no scatter
+            q_loss_sum = ops.masked_q_taken_loss(q, b['action'], target_Q, mask)
+        elif q.is_cuda and q.dtype == torch.float32:
             q_loss_sum = ops.masked_q_loss(q, target_Q, mask)         # one forward + one backward kernel (csrc/losses.hip; reference :105-114, :80-81)
         else:                                                   # CPU tensors keep the torch spelling
             q_loss_sum = ((q - target_Q.unsqueeze(0)).pow(2).sum(dim=0) * mask).sum()
@@ -543,7 +549,10 @@ class SACFullLengthRNNEnsembleQ(SAC):
             q_pi = value.forward(b['state'], b['last_state'], b['last_action'], act_in, hidden['value'], b['reward_input'],
                                  detach_embedding=True)[0]
         lp_sum = None
-        if self.discrete_env:                               # expectation over the action distribution (reference redq :85-86)
+        if self.discrete_env and ops.discrete_fused(q_pi) and self.actor_q_reduce in ('min', 'mean'):
+            # expectation over the action distribution (reference redq :85-86): both sums from one pass, d/dlogp from one more
+            actor_sum, lp_sum = ops.masked_discrete_actor_loss(log_prob, q_pi, mask, self.log_sac_alpha, self.actor_q_reduce == 'min')
+        elif self.discrete_env:
             objective = (self._actor_objective(alpha_detach, log_prob, self._q_for_policy(q_pi)) * log_prob.exp()).sum(dim=-1, keepdim=True)
             log_prob = (log_prob * log_prob.exp()).sum(dim=-1, keepdim=True)          # logged as -entropy (:425)
             actor_sum = (objective * mask).sum()

@@ -125,6 +125,13 @@ SIGNATURES = {
     'resel_attn_decode_rows': (c_int, [P, L, P, P, P, P, F, I, I, I, I, S]),
     'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),
     'resel_categorical_step': (c_int, [P, L, P, F, P, L, P, P, L, I, I, S]),
+    'resel_categorical_fwd': (c_int, [P, F, P, P, P, I, I, S]),
+    'resel_categorical_bwd': (c_int, [P, F, P, P, P, I, I, S]),
+    'resel_discrete_value': (c_int, [P, P, I, P, P, P, I, I, I, S]),
+    'resel_q_taken_loss_fwd': (c_int, [P, P, P, P, P, P, I, I, I, S]),
+    'resel_q_taken_loss_bwd': (c_int, [P, P, P, P, P, P, I, I, I, S]),
+    'resel_discrete_actor_loss_fwd': (c_int, [P, P, P, P, P, P, I, I, I, I, S]),
+    'resel_discrete_actor_loss_bwd': (c_int, [P, P, P, P, P, P, P, I, I, I, I, S]),
 }
 
 

@@ -1093,6 +1093,158 @@ def masked_actor_loss(logp, q, mask, log_alpha, use_logp=True, reduce_min=False)
     return out[0], out[1].detach()
 
 
+# ---------------------------------------------------------------------------------------------- discrete-action update
+def discrete_fused(t) -> bool:
+    """RESEL_DISCRETE_FUSED (default on; 0: the torch spelling): the discrete-action update runs its head, target value and losses
+    through the kernels below.  Only fp32 device tensors take the fused form."""
+    return os.environ.get('RESEL_DISCRETE_FUSED', '1') != '0' and t.is_cuda and t.dtype == torch.float32
+
+
+class CategoricalHeadFn(torch.autograd.Function):
+    """logits [..., A] -> (mode [...] fp32, no grad; logp [..., A]; probs [..., A]) as ONE node (include/resel_hip.h
+    `resel_categorical_fwd` / `_bwd`); the backward recomputes the softmax from the saved logits."""
+
+    @staticmethod
+    def forward(ctx, logits, floor):
+        _need_cuda('categorical_head', logits)
+        shape = logits.shape
+        A = shape[-1]
+        x = logits.float().reshape(-1, A).contiguous()
+        M = x.shape[0]
+        logp, probs = torch.empty_like(x), torch.empty_like(x)
+        mode = torch.empty(M, dtype=torch.float32, device=x.device)
+        if M > 0:
+            check(lib().resel_categorical_fwd(_p(x), float(floor), _p(logp), _p(probs), _p(mode), M, A, _stream()), 'categorical_fwd')
+        ctx.save_for_backward(x)
+        ctx.cfg = (shape, float(floor))
+        ctx.set_materialize_grads(False)
+        mode = mode.reshape(shape[:-1])
+        ctx.mark_non_differentiable(mode)
+        return mode, logp.reshape(shape), probs.reshape(shape)
+
+    @staticmethod
+    def backward(ctx, _dmode, dlogp, dprobs):
+        x, = ctx.saved_tensors
+        shape, floor = ctx.cfg
+        if dlogp is None and dprobs is None:
+            return None, None
+        M, A = x.shape
+        f = lambda t: None if t is None else t.float().reshape(M, A).contiguous()
+        dl, dp = f(dlogp), f(dprobs)
+        dx = torch.empty_like(x)
+        if M > 0:
+            check(lib().resel_categorical_bwd(_p(x), floor, _p(dl), _p(dp), _p(dx), M, A, _stream()), 'categorical_bwd')
+        return dx.reshape(shape), None
+
+
+def categorical_head(logits, floor=0.01):
+    """Whole-row categorical head (reference contextual_sac_discrete_policy.py:106-121): p = renormalised twice (softmax + floor)
+    -> (mode = lowest argmax of p as fp32 [...], log p [..., A], p [..., A]); differentiable in logp and probs, one autograd node."""
+    return CategoricalHeadFn.apply(logits, floor)
+
+
+@torch.no_grad()
+def discrete_value(q, subset, logp, log_alpha):
+    """q [E, ..., A], logp [..., A], subset int32 [m] on the device or None (all E members), log_alpha a device scalar
+    -> v [..., 1] = sum_a exp(logp) (min_{e in subset} q[e] - exp(log_alpha) logp)   (include/resel_hip.h `resel_discrete_value`)."""
+    _need_cuda('discrete_value', q, logp, log_alpha, subset)
+    E, A = q.shape[0], logp.shape[-1]
+    lp = logp.float().reshape(-1, A).contiguous()
+    M = lp.shape[0]
+    q3 = q.float().reshape(E, M, A).contiguous()
+    la = log_alpha.float().reshape(-1).contiguous()
+    v = torch.empty(M, dtype=torch.float32, device=q.device)
+    if subset is not None:
+        assert subset.dtype == torch.int32
+        subset = subset.reshape(-1).contiguous()
+    if M > 0:
+        check(lib().resel_discrete_value(_p(q3), _p(subset), 0 if subset is None else int(subset.numel()), _p(lp), _p(la), _p(v), E, M, A,
+                                         _stream()), 'discrete_value')
+    return v.reshape(logp.shape[:-1] + (1,))
+
+
+class MaskedQTakenLossFn(torch.autograd.Function):
+    """sum_m mask[m] sum_e (q[e, m, a_m] - y[m])^2 over q [E, ..., A] as ONE node (include/resel_hip.h `resel_q_taken_loss_*`): no gather
+    in front, no zero-fill + scatter behind - the backward writes the dense dq the GEMM backward consumes."""
+
+    @staticmethod
+    def forward(ctx, q, action, y, mask):
+        _need_cuda('q_taken_loss', q, action, y)
+        E, A = q.shape[0], q.shape[-1]
+        f = lambda t: None if t is None else t.float().reshape(-1).contiguous()
+        a1, y1, m1 = f(action), f(y), f(mask)
+        M = y1.numel()
+        q3 = q.float().reshape(E, M, A).contiguous()
+        assert a1.numel() == M and (m1 is None or m1.numel() == M)
+        out = (torch.empty if M > 0 else torch.zeros)(2, dtype=torch.float32, device=q.device)
+        ws = _ws(lib().resel_masked_loss_workspace_bytes(), q.device)
+        if M > 0:
+            check(lib().resel_q_taken_loss_fwd(_p(q3), _p(a1), _p(y1), _p(m1), _p(out), _p(ws), E, M, A, _stream()), 'q_taken_loss_fwd')
+        ctx.save_for_backward(q3, a1, y1, m1)
+        ctx.shape = q.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        q3, a1, y1, m1 = ctx.saved_tensors
+        E, M, A = q3.shape
+        dq = torch.empty_like(q3)
+        if M > 0:
+            check(lib().resel_q_taken_loss_bwd(_p(q3), _p(a1), _p(y1), _p(m1), _p(g.float().reshape(1).contiguous()), _p(dq), E, M, A, _stream()),
+                  'q_taken_loss_bwd')
+        return dq.view(ctx.shape), None, None, None
+
+
+def masked_q_taken_loss(q, action, y, mask):
+    """q [E, ..., A]; action [..., 1]: the fp32 action index as the batch stores it; y, mask [..., 1]."""
+    return MaskedQTakenLossFn.apply(q, action, y, mask)
+
+
+class MaskedDiscreteActorLossFn(torch.autograd.Function):
+    """(sum_m mask sum_a p (alpha logp - red_e q[e]), sum_m mask sum_a p logp) with p = exp(logp) as ONE node (include/resel_hip.h
+    `resel_discrete_actor_loss_*`); the second output is a statistic and carries no gradient.  dq is formed only when q asks for one."""
+
+    @staticmethod
+    def forward(ctx, logp, q, mask, log_alpha, reduce_min):
+        _need_cuda('discrete_actor_loss', logp, q)
+        E, A = q.shape[0], logp.shape[-1]
+        lp = logp.float().reshape(-1, A).contiguous()
+        M = lp.shape[0]
+        q3 = q.float().reshape(E, M, A).contiguous()
+        m1 = None if mask is None else mask.float().reshape(-1).contiguous()
+        assert m1 is None or m1.numel() == M
+        la = log_alpha.detach().float().reshape(-1).contiguous()
+        out = (torch.empty if M > 0 else torch.zeros)(2, dtype=torch.float32, device=q.device)
+        ws = _ws(lib().resel_masked_loss_workspace_bytes(), q.device)
+        if M > 0:
+            check(lib().resel_discrete_actor_loss_fwd(_p(lp), _p(q3), _p(m1), _p(la), _p(out), _p(ws), E, M, A, int(bool(reduce_min)), _stream()),
+                  'discrete_actor_loss_fwd')
+        ctx.save_for_backward(lp, q3, m1, la)
+        ctx.cfg = (bool(reduce_min), logp.shape, q.shape)
+        total, stat = out[0], out[1]                  # two outputs, so that no select-backward (zero-fill + copy) sits behind the node
+        ctx.mark_non_differentiable(stat)
+        return total, stat
+
+    @staticmethod
+    def backward(ctx, g, _dstat):
+        lp, q3, m1, la = ctx.saved_tensors
+        reduce_min, lshape, qshape = ctx.cfg
+        E, M, A = q3.shape
+        g = g.float().reshape(1).contiguous()
+        dlp = torch.empty_like(lp)
+        dq = torch.empty_like(q3) if ctx.needs_input_grad[1] else None
+        if M > 0:
+            check(lib().resel_discrete_actor_loss_bwd(_p(lp), _p(q3), _p(m1), _p(la), _p(g), _p(dlp), _p(dq), E, M, A, int(reduce_min), _stream()),
+                  'discrete_actor_loss_bwd')
+        return dlp.view(lshape), (None if dq is None else dq.view(qshape)), None, None, None
+
+
+def masked_discrete_actor_loss(logp, q, mask, log_alpha, reduce_min=False):
+    """logp [..., A], q [E, ..., A], mask [..., 1] -> (objective sum, sum mask sum_a p logp (detached))."""
+    total, stat = MaskedDiscreteActorLossFn.apply(logp, q, mask, log_alpha, reduce_min)
+    return total, stat.detach()
+
+
 @torch.no_grad()
 def guard_apply_slots(slots, world, guard):
     """slots fp32 [world * 4] (every rank's extrema, delivered by the gradient all-reduce) -> first-call initialisation + running

@@ -1,7 +1,8 @@
 """Categorical actor for discrete action spaces (reference
 offpolicy_rnn/policy_value_models/contextual_sac_discrete_policy.py:13-138): logits -> softmax, mixed with a 0.01 floor
 and renormalised; returns (argmax, sample, log-probabilities of ALL actions).  A one-token call on the device without autograd - a
-rollout or evaluation step, eager or captured - runs the head as one HIP kernel (`ops.categorical_step`)."""
+rollout or evaluation step, eager or captured - runs the head as one HIP kernel (`ops.categorical_step`); whole-row passes on the device
+(the update) run it as one differentiable node (`ops.categorical_head`, switch `RESEL_DISCRETE_FUSED`) and keep their multinomial draw."""
 from typing import Optional, Tuple
 
 import torch
@@ -64,6 +65,12 @@ class ContextualSACDiscretePolicy(ContextualModel):
             lead = model_output.shape[:-1] + (1,)
             logp = logp.reshape(model_output.shape)
             return mode.long().reshape(lead), sample.long().reshape(lead), logp, logp.exp()
+        from ..hip import ops
+        if ops.discrete_fused(model_output):                         # whole rows (the update): one node forward, one backward
+            mode, logp, probs = ops.categorical_head(model_output, self.PROB_FLOOR)
+            # the update never uses this sample; the draw stays because it advances the device generator as the torch spelling does
+            action_sample = torch.multinomial(probs.reshape(-1, probs.shape[-1]), 1, True).reshape(probs.shape[:-1] + (1,))
+            return mode.long().unsqueeze(-1), action_sample, logp, probs
         probs = torch.softmax(model_output, dim=-1)                  # reference :112-113 (max-shifted exp / sum)
         probs = probs + self.PROB_FLOOR
         probs = probs / probs.sum(dim=-1, keepdim=True)
