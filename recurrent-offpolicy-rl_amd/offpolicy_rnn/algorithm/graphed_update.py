@@ -32,8 +32,20 @@ profiles/r09_cgpt_buckets.md) the two tables are padded into one more bucket (`s
 ladder, sequences to a power of two - empty sequences, the real token count stays in cu_seqlens' last element ON THE DEVICE), the
 decoder packs / unpacks with kernels that read that count (`ops.pack_tokens` / `unpack_tokens`) and the attention core defines the
 token tail (`ops.attn_varlen(padded=True)`); the bucketed key is (rows, row length, plan entries, tokens, cu entries, attention
-blocks per row, actor flag) and has in practice as many values as the batch bucket alone.  `train()` takes the mode from RESEL_GRAPH_BUCKETS (`buckets_from_env`: 1, auto; unset = 'off').  Every `step()` is exactly ONE update (same update-to-data ratio and random streams as the eager loop): the first `warmup`
-calls run eagerly (allocator and lazily initialised kernels warm up), a shape is recorded the SECOND time it occurs (a shape that
+blocks per row, actor flag) and has in practice as many values as the batch bucket alone.  `train()` takes the mode from RESEL_GRAPH_BUCKETS (`buckets_from_env`: 1, auto; unset = 'off').  Every `step()` is exactly ONE `train_one_batch()`: `utd` PASSES (a pass is one iteration of the update's `utd` loop - one sampled batch,
+one target, one critic step, one soft target update and, where `_actor_due` says so, an actor (+ alpha) step), each prepared on the host
+and launched from the graph of its own launch sequence - the captured unit is the pass, not the step, and where this text says "update"
+for what is recorded, replayed, counted or staged, it means a pass (utd = 1: the same thing).  A step with utd = 4, policy_utd = 2 is four
+replays alternating between two recordings; the passes of one step may differ in shape (ragged batches) and mix replays, eager launches
+and a recording.  Host random streams: the eager loop draws, per pass, the sampling plan and then the REDQ subset from numpy -
+`_prepare` runs pass by pass and keeps that order; the constructor consumes no draw.  The update boundary (`ops.amax_maintenance()`, the
+generation check) is once per `step()`, in front of the first pass; `amax_arena_zero`, the dropout base's advance and the restart of the
+host's offset count are per recorded body, i.e. per pass - two passes of one step draw different masks.  The log: every key has a fixed slot
+in the static buffer, a pass's log node writes its own keys only (a later pass overwrites an earlier one's, actor keys survive from the
+last pass that ran the actor step - the eager loop's shared dict), ONE read-back behind the step's last pass into a pinned ring turned
+per step; the returned log names the union of the keys the step's passes wrote, so nothing of an earlier step shows.  `eager_fallbacks`,
+`_steps`, `_seen`, `warmup` and the capture window count passes.  The first `warmup`
+passes run eagerly (allocator and lazily initialised kernels warm up), a shape is recorded the SECOND time it occurs (a shape that
 never recurs is not worth two device synchronisations and an activation pool), at most `max_graphs` graphs live at a time in ONE
 shared memory pool (they never replay concurrently), the least recently used one is dropped for a newcomer - but an evicted shape must
 recur RECAPTURE_HITS times before it is recorded again and at most `max_graphs` recordings happen per CAPTURE_WINDOW updates, so a
@@ -51,7 +63,8 @@ Data-parallel groups: the recording is CUT at each gradient exchange (`cut`) - a
 the two all-reduces issued eagerly between them on the same stream (works with every backend; nothing waits on the host).
 Randomised loss masks change the values of one column and no shape or launch; random truncation changes batch shapes like any ragged
 workload (exact keys: most of its updates fall to `step()`'s eager launch; buckets absorb it).
-Refused at construction (use the eager `train_one_batch`): utd != 1, the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce)."""
+Refused at construction (use the eager `train_one_batch`): the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce).  utd < 1 is an
+error of the flag set (ValueError), not a refusal."""
 import os
 from collections import OrderedDict
 
@@ -77,10 +90,11 @@ def _exact_table_key(built):
 
 class GraphedUpdate:
     PLAN_CAPACITY = 16384                             # plan segments the static buffers hold (64 KB of pinned memory per slot)
-    RING = 3                                          # pinned staging slots: the host may be this many updates ahead of the device
+    RING = 3                                          # pinned staging slots: the host may be this many passes (and logs: this many steps) ahead of the device
     SEEN_CAP = 1024                                   # shape keys remembered (variable-length episodes produce many that never recur)
     RECAPTURE_HITS = 8                                # occurrences an EVICTED shape needs before it is recorded again
-    CAPTURE_WINDOW = 256                              # at most `max_graphs` recordings per this many updates: more recurring shapes than graphs run eagerly
+    CAPTURE_WINDOW = 256                              # at most `max_graphs` recordings per this many passes: more recurring shapes than graphs run eagerly
+    LOG_SLOTS = 64                                    # device scalars a run may log, one fixed slot each
 
     BUCKET_SHAPES = 8                                 # bucketed shapes held per launch sequence when the caller sets no `max_graphs`
     NO_SEQ_BUCKETS = NO_SEQ_BUCKETS + "; use buckets='off' or 'auto'"
@@ -110,6 +124,8 @@ class GraphedUpdate:
         why = self.refusal(alg)
         if why:
             raise RuntimeError('GraphedUpdate: ' + why)
+        if alg.parameter.utd < 1:                     # an error of the flag set, not a reason to launch eagerly: the eager loop would run no pass either
+            raise ValueError(f'GraphedUpdate: utd={alg.parameter.utd} (an update is at least one pass)')
         if buckets not in ('off', 'on', 'auto'):
             raise ValueError(f'GraphedUpdate: buckets={buckets!r} (off, on, auto)')
         # read HERE, not by the caller: `train()` builds `GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())`
@@ -118,20 +134,23 @@ class GraphedUpdate:
             raise RuntimeError('GraphedUpdate: ' + self.NO_SEQ_BUCKETS)
         self.alg, self.device = alg, alg.device
         self.graphs = OrderedDict()                   # batch shape key -> CUDAGraph, least recently used first
-        self._sequences = 2 if alg.parameter.policy_update_per > 1 else 1   # launch sequences per shape: with / without the actor step
+        self._sequences = self.launch_sequences(alg)  # launch sequences per shape: with / without the actor step
         self._own_max_graphs = max_graphs is None
         if max_graphs is None:                        # four exact (eight bucketed) batch shapes per launch sequence
             max_graphs = (self.BUCKET_SHAPES if buckets == 'on' else 4) * self._sequences
         self.buckets = buckets                        # 'auto' becomes 'on' at most once (_count_shape)
         self._shapes = set()                          # 'auto': distinct exact shapes seen so far
         self.warmup, self.max_graphs = warmup, max_graphs
-        self._eager_left = warmup                     # updates still to run eagerly before anything is recorded
+        # every counter below counts PASSES (one iteration of the `utd` loop; utd = 1: a pass is an update)
+        self._eager_left = warmup                     # passes still to run eagerly before anything is recorded
         self._seen = OrderedDict()                    # batch shape key -> occurrences so far (least recently seen first; pruned to SEEN_CAP)
-        self._captures = []                           # step indices of the most recent recordings (capture-rate limit)
-        self._steps = 0
+        self._captures = []                           # pass indices of the most recent recordings (capture-rate limit)
+        self._steps = 0                               # passes launched so far
+        self._updates = 0                             # `step()` calls so far (the log ring's turn)
+        self._pass = (0, 0)                           # (utd_idx, actor steps so far) of the pass being prepared / launched (step, pass_position)
         self._amax_generation = ops.AMAX_GENERATION[0]
         self._pool = torch.cuda.graph_pool_handle()   # memory pool shared by every recorded graph (and by the segments of one update)
-        self.eager_fallbacks = 0
+        self.eager_fallbacks = 0                      # passes launched eagerly through `step()`
         # data-parallel groups: the process group's watchdog thread polls events while this thread records - harmless, but a capture in the
         # default `global` mode treats such a call from ANOTHER thread as an error and invalidates the recording
         self._capture_mode = 'thread_local' if alg.grad_sync.active else 'global'
@@ -161,16 +180,20 @@ class GraphedUpdate:
             if torch.is_tensor(st.get('step')):
                 st['step'] = st['step'].to(self.device)
         self._plan_dev = torch.empty((self.PLAN_CAPACITY, 4), dtype=torch.int32, device=self.device)
-        self._log_dev = torch.zeros(64, dtype=torch.float32, device=self.device)    # static target of the graph's log node
+        self._log_dev = torch.zeros(self.LOG_SLOTS, dtype=torch.float32, device=self.device)    # static target of the graphs' log nodes
+        self._log_slots = {}                          # log key -> its fixed slot in `_log_dev` (handed out on a key's first appearance, log_node)
         # randomised loss masks: one word offset per plan entry + the bitmap words of every entry at the ring's row capacity
         self._sel_capacity = self.PLAN_CAPACITY * (1 + (alg.replay_buffer.max_traj_step + 31) // 32) if alg.parameter.randomize_mask else 0
         self._sel_dev = torch.zeros(self._sel_capacity, dtype=torch.int32, device=self.device) if self._sel_capacity else None
         self._ring = [dict(plan=torch.empty((self.PLAN_CAPACITY, 4), dtype=torch.int32, pin_memory=True),
                            sub=torch.empty(self.subset_np.size, dtype=torch.int32, pin_memory=True),
                            bc=torch.empty(4, dtype=torch.float32, pin_memory=True),
-                           log=torch.empty(64, dtype=torch.float32, pin_memory=True),
                            sel=torch.empty(self._sel_capacity, dtype=torch.int32, pin_memory=True) if self._sel_capacity else None,
-                           evt=torch.cuda.Event(), used=False, handed=None) for _ in range(self.RING)]
+                           evt=torch.cuda.Event(), used=False) for _ in range(self.RING)]
+        # the log's read-back has a ring of its own, turned once per `step()`: with utd > RING a staging slot comes round again inside
+        # one step, and the log handed out by the step before is still unread then
+        self._log_ring = [dict(log=torch.empty(self.LOG_SLOTS, dtype=torch.float32, pin_memory=True), evt=torch.cuda.Event(), handed=None)
+                          for _ in range(self.RING)]
         self._turn = 0
         self._slot = self._ring[0]
         self._plan = None                             # the sampling plan of the update being prepared / launched (_prepare)
@@ -249,13 +272,37 @@ class GraphedUpdate:
             return 'not a full-trajectory trainer'
         if alg.grad_sync.active and os.environ.get('RESEL_DP_GUARD', 'bucket') == 'allreduce':
             return 'the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce) issues collectives inside the target computation'
-        if par.utd != 1:
-            return 'utd != 1'
         if not (alg.device_replay and alg.replay_buffer.device_supported(randomize_mask=par.randomize_mask)):
             return 'needs the device-resident replay ring'
         return None
 
+    @staticmethod
+    def pass_schedule(alg):
+        """The actor flags of the passes of the coming `train_one_batch()` (one per iteration of its `utd` loop), obtained only by walking
+        the trainer's `_actor_due` the way that loop does.  Host only: works on a CPU trainer, touches nothing."""
+        flags = []
+        for utd_idx in range(alg.parameter.utd):
+            flags.append(bool(alg._actor_due(utd_idx, sum(flags))))
+        return flags
+
+    @staticmethod
+    def launch_sequences(alg):
+        """Launch sequences per batch shape: 2 if two passes of a run can differ in their actor flag - within one step (policy_utd < utd
+        spreads the actor steps over the passes) or from step to step (policy_update_per > 1) -, 1 otherwise.  Walks `pass_schedule` over
+        one period of `grad_num` (the schedule depends on it only through grad_num % policy_update_per); `grad_num` is put back."""
+        kept, flags = alg.grad_num, set()
+        try:
+            for alg.grad_num in range(max(1, alg.parameter.policy_update_per)):
+                flags.update(GraphedUpdate.pass_schedule(alg))
+        finally:
+            alg.grad_num = kept
+        return max(1, len(flags))
+
     # ---- called by the trainer while `alg._graph is self` -------------------------------------------------------------------
+    def pass_position(self):
+        """The trainer's `_train_one_batch` while this object drives the update: (utd_idx, actor steps so far) of the ONE pass it is to run."""
+        return self._pass
+
     def gather(self):
         pl = self._plan
         n = pl['seg'].shape[0]
@@ -306,12 +353,27 @@ class GraphedUpdate:
         return dict(segs=rec['segs'], log_keys=self._log_keys, log_items=self._log_items)
 
     def log_node(self, keys, packed, host_items):
+        """The trainer's `_log` of ONE pass.  Every key has a fixed slot in the static buffer and a pass writes only its own keys (copy
+        nodes of the graph, one per run of neighbouring slots): the passes of a step merge on the device, a later pass overwriting an
+        earlier one's keys - what the eager loop's shared `scal` does.  The read-back follows the step's last pass (`_finish`)."""
         self._log_keys, self._log_items = keys, host_items
-        self._log_dev[:packed.numel()].copy_(packed)                         # a node of the graph; the read-back follows the replay (_finish)
+        slots = [self._log_slots.setdefault(k, len(self._log_slots)) for k in keys]
+        if len(self._log_slots) > self.LOG_SLOTS:
+            raise RuntimeError(f'GraphedUpdate: more than {self.LOG_SLOTS} logged device scalars')
+        i = 0
+        while i < len(slots):
+            j = i + 1
+            while j < len(slots) and slots[j] == slots[j - 1] + 1:
+                j += 1
+            self._log_dev[slots[i]:slots[i] + j - i].copy_(packed[i:j])
+            i = j
         return None
 
-    # ---- host side of one update ----------------------------------------------------------------------------------------------
+    # ---- host side of one pass ------------------------------------------------------------------------------------------------
     def _prepare(self):
+        """Host half of the pass at `self._pass`: sampling plan, then the REDQ subset - the order in which the eager loop draws them from
+        numpy, pass by pass -, the AdamW factors (the critic's every pass, the policy's only where the actor step is due) into one
+        staging slot.  -> the graph key: the batch shape key + the actor flag of this pass."""
         alg, par = self.alg, self.alg.parameter
         pl = alg.replay_buffer.plan_trajs_device(par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj,
                                                  nest_stack_trajs=alg.allow_nest_stack, buckets=self.buckets == 'on',
@@ -334,11 +396,8 @@ class GraphedUpdate:
         key = (pl['nrow'], pl['longest'], n) if self.buckets == 'on' else _exact_batch_key(pl)
         if self._drop_base is not None and built is None:
             built = self._build_seqs(pl)
-        # staging slot of this update: its copies of three updates ago have long run; the log handed out then is read out before its block is reused
+        # staging slot of this pass: its copies of three passes ago have long run
         slot = self._slot = self._ring[self._turn % self.RING]
-        if slot['handed'] is not None:
-            slot['handed'].resolve()
-            slot['handed'] = None
         if slot['used']:
             slot['evt'].synchronize()
         if built is not None and self.buckets == 'on':                      # reachable with `seq_buckets` only
@@ -356,8 +415,8 @@ class GraphedUpdate:
         slot['sub'].numpy()[...] = sub
         self.subset_i32.copy_(slot['sub'], non_blocking=True)
         self.subset_i64.copy_(self.subset_i32)
-        # is the actor step due in this update (utd = 1: its one critic step, no actor step yet)?  Part of the key: the two launch sequences are two graphs
-        actor_due = alg._actor_due(0, 0)
+        # is the actor step due in this pass?  Part of the key: the two launch sequences are two graphs
+        actor_due = alg._actor_due(*self._pass)
         for i, opt in enumerate((alg.optimizer_value, alg.optimizer_policy)):
             if i == 0 or actor_due:
                 opt.prepare_step(slot['bc'][2 * i:2 * i + 2])
@@ -378,7 +437,7 @@ class GraphedUpdate:
         self.graphs.clear()
         self._seen.clear()
         self._captures = []
-        self.alg.logger(f'update graphs: {len(self._shapes)} batch shapes in {self._steps + 1} updates - batch shapes are bucketed from here on '
+        self.alg.logger(f'update graphs: {len(self._shapes)} batch shapes in {self._steps + 1} {"updates" if self.alg.parameter.utd == 1 else "passes"} - batch shapes are bucketed from here on '
                         f'(RESEL_GRAPH_BUCKETS=0 keeps exact shapes)')
         self._shapes.clear()
         return True
@@ -402,22 +461,40 @@ class GraphedUpdate:
             for opt in (alg.optimizer_value, alg.optimizer_policy):
                 opt.device_factors_active = False
 
-    def _finish(self):
-        n = len(self._log_keys)
-        slot = self._slot
-        slot['log'][:n].copy_(self._log_dev[:n], non_blocking=True)          # behind the update on the stream
-        slot['evt'].record()
-        slot['used'] = True
-        pl = self._plan                               # the host entries of THIS update (the captured dict holds the recorded update's)
-        items = dict(self._log_items, **self.alg._host_log(pl['total_size'], pl.get('nrow_real', pl['nrow'])))
-        slot['handed'] = DeferredLog(list(self._log_keys), slot['log'][:n], slot['evt'], items)
-        return slot['handed']
+    def _finish(self, keys, items):
+        """The step's ONE read-back, behind its last pass on the stream: the whole slot buffer into this step's pinned block; the log
+        names `keys` - the union of the keys its passes wrote, so a step without an actor step shows no actor key of an earlier one."""
+        ring = self._log_ring[self._updates % self.RING]
+        if ring['handed'] is not None:                # the log handed out RING steps ago is read out before its block is reused
+            ring['handed'].resolve()
+        n = len(self._log_slots)
+        ring['log'][:n].copy_(self._log_dev[:n], non_blocking=True)
+        ring['evt'].record()
+        pl = self._plan                               # the host entries of the LAST pass, as the eager `_log` takes them
+        items = dict(items, **self.alg._host_log(pl['total_size'], pl.get('nrow_real', pl['nrow'])))
+        ring['handed'] = DeferredLog(keys, ring['log'][:n], ring['evt'], items, index=[self._log_slots[k] for k in keys])
+        self._updates += 1
+        return ring['handed']
 
     def step(self):
-        """Exactly one update: eager while warming up or while the batch shape has no graph, a replay otherwise."""
+        """Exactly one `train_one_batch()`: `utd` passes, each prepared on the host (`_prepare`: plan, then subset - the eager loop's
+        order of numpy draws) and launched from its own launch sequence (`_launch_pass`: a replay, an eager launch or a recording, mixed
+        freely within one step); the update-boundary work once, in front of the first pass; one log, read back once behind the last."""
         if ops.amax_maintenance() or self._amax_generation != ops.AMAX_GENERATION[0]:
             self.graphs.clear()                       # the magnitude epochs started over: recorded kernel nodes carry epochs of the old generation
             self._amax_generation = ops.AMAX_GENERATION[0]
+        alg = self.alg
+        keys, items, actor_steps = {}, {}, 0
+        for utd_idx in range(alg.parameter.utd):
+            self._pass = (utd_idx, actor_steps)       # read by `_prepare` (the key, the AdamW factors) and by the trainer (`pass_position`)
+            actor_steps += self._launch_pass()
+            keys.update(dict.fromkeys(self._log_keys))                       # device scalars: merged in `_log_dev`, named here
+            items.update(self._log_items)             # host entries: a later pass wins, an earlier one's survive (the eager loop's `host`)
+        self._pass = (0, 0)
+        return self._finish(list(keys), items)
+
+    def _launch_pass(self):
+        """One pass: eager while warming up or while its batch shape has no graph, a replay otherwise.  -> did it run the actor step."""
         key = self._prepare()
         g = self.graphs.get(key)
         self._steps += 1
@@ -427,16 +504,16 @@ class GraphedUpdate:
             while len(self._seen) > self.SEEN_CAP:
                 self._seen.popitem(last=False)
             # a recording costs two device synchronisations and a whole capture pass: with more recurring shapes than `max_graphs` an
-            # evict-and-record-again policy would turn every update into capture + replay.  Hence: an evicted shape has to recur
-            # RECAPTURE_HITS times before it is recorded again, and no more than `max_graphs` recordings per CAPTURE_WINDOW updates -
-            # whatever has no graph runs eagerly (the same update from the same static inputs).
+            # evict-and-record-again policy would turn every pass into capture + replay.  Hence: an evicted shape has to recur
+            # RECAPTURE_HITS times before it is recorded again, and no more than `max_graphs` recordings per CAPTURE_WINDOW passes -
+            # whatever has no graph runs eagerly (the same pass from the same static inputs).
             self._captures = [t for t in self._captures if self._steps - t < self.CAPTURE_WINDOW]
             throttled = len(self.graphs) >= self.max_graphs and len(self._captures) >= self.max_graphs
-            if self._eager_left > 0 or seen < 2 or throttled:      # warm-up updates / a shape on its first visit: the same update, launched eagerly
+            if self._eager_left > 0 or seen < 2 or throttled:      # warm-up passes / a shape on its first visit: the same pass, launched eagerly
                 self._eager_left = max(0, self._eager_left - 1)
                 self.eager_fallbacks += 1
                 self._body()
-                return self._finish()
+                return self._launched(key)
             if len(self.graphs) >= self.max_graphs:
                 old_key, _ = self.graphs.popitem(last=False)       # least recently used; its activations return to the shared pool
                 self._seen[old_key] = 2 - self.RECAPTURE_HITS
@@ -448,9 +525,15 @@ class GraphedUpdate:
             seg.replay()
             if exchange is not None:
                 exchange()                            # the gradient all-reduce, eagerly between two replays on the same stream
-        if ops.AMAX_VERIFY:                           # the recorded update contains the check kernels: read their verdict behind the replay
+        if ops.AMAX_VERIFY:                           # the recorded pass contains the check kernels: read their verdict behind the replay
             ops.amax_verify_raise(self.device)
-        return self._finish()
+        return self._launched(key)
+
+    def _launched(self, key):
+        """Behind a pass on the stream: its staging slot is free once this event has passed.  -> the pass's actor flag."""
+        self._slot['evt'].record()
+        self._slot['used'] = True
+        return key[-1]
 
     @property
     def graph(self):                                  # the most recently recorded graph (tests): its first segment

@@ -423,30 +423,41 @@ class SACFullLengthRNNEnsembleQ(SAC):
             return log
 
     def _train_one_batch(self) -> Dict:
-        """One update: sample -> hidden states -> target -> critic step -> soft update -> actor step (if due) -> log.  Entered by the eager
-        `train_one_batch` and, while a GraphedUpdate records or launches the update from its static inputs, by its `_body`."""
+        """One update: `utd` passes (`_one_pass`) -> log.  Entered by the eager `train_one_batch` and, while a GraphedUpdate records or
+        launches a pass from its static inputs, by its `_body`: the captured unit is ONE pass - the driver walks the `utd` loop itself and
+        hands over where in it this pass stands (`pass_position`); the pass's log goes into the graph's static buffer (`log_node`)."""
         par = self.parameter
         self.policy.to(self.device)
         self.optimizer_policy.to(self.device)
-        actor_steps = 0
         scal: Dict[str, torch.Tensor] = {}
         host: Dict[str, float] = {}
-        for utd_idx in range(par.utd):
-            b, batch_size, real_rows = self._sample()
-            hidden = self._hidden_states(b)
-            alpha_detach = self.log_sac_alpha.exp().detach()
-            actor_due = self._actor_due(utd_idx, actor_steps)
-            target_Q, shared_out = self._target(b, hidden, share_policy_pass=self.share_policy_pass and actor_due)
-            valid_num = self._stats[1]
-            self._critic_step(b, hidden, target_Q, valid_num, scal, host)
-            self._value_update(tau=par.sac_tau)                  # soft target update: one kernel over the flat buffers
-            self.values[0].eval()
-            self.policy.train()
-            if actor_due:
-                self._actor_step(b, hidden, shared_out, alpha_detach, valid_num, scal, host)
-                actor_steps += 1
+        if self._graph is not None:
+            _, batch_size, real_rows = self._one_pass(*self._graph.pass_position(), scal, host)
+        else:
+            actor_steps = 0
+            for utd_idx in range(par.utd):
+                stepped, batch_size, real_rows = self._one_pass(utd_idx, actor_steps, scal, host)
+                actor_steps += stepped
         self.policy.to(self.sample_device)
         return self._log(scal, host, batch_size, real_rows)
+
+    def _one_pass(self, utd_idx, actor_steps, scal, host):
+        """Pass `utd_idx` of an update, `actor_steps` actor steps into it: sample -> hidden states -> target -> critic step -> soft update ->
+        actor step (if due).  Fills `scal` / `host`; -> (did the actor step run, transitions drawn, rows drawn)."""
+        par = self.parameter
+        b, batch_size, real_rows = self._sample()
+        hidden = self._hidden_states(b)
+        alpha_detach = self.log_sac_alpha.exp().detach()
+        actor_due = self._actor_due(utd_idx, actor_steps)
+        target_Q, shared_out = self._target(b, hidden, share_policy_pass=self.share_policy_pass and actor_due)
+        valid_num = self._stats[1]
+        self._critic_step(b, hidden, target_Q, valid_num, scal, host)
+        self._value_update(tau=par.sac_tau)                      # soft target update: one kernel over the flat buffers
+        self.values[0].eval()
+        self.policy.train()
+        if actor_due:
+            self._actor_step(b, hidden, shared_out, alpha_detach, valid_num, scal, host)
+        return bool(actor_due), batch_size, real_rows
 
     def _actor_due(self, utd_idx, done_so_far) -> bool:
         """Does the actor (+ alpha) step follow critic step `utd_idx` of this update, `done_so_far` actor steps into it (reference :450-452)?"""

@@ -6,10 +6,11 @@ class DeferredLog(dict):
     pinned memory and become floats on first access (`resolve()`), so a caller that does not read them - a training loop
     logging every n-th update, bench.py - never stalls the launch queue on the update it has just enqueued."""
 
-    def __init__(self, keys, buf, event, host_items=()):
-        """`buf`: host tensor the scalars named by `keys` arrive in, readable once `event` (None: at once) has passed."""
+    def __init__(self, keys, buf, event, host_items=(), index=None):
+        """`buf`: host tensor the scalars named by `keys` arrive in, readable once `event` (None: at once) has passed; `index`: where in
+        `buf` each key's scalar sits (None: in the order of `keys`) - a buffer with a fixed slot per key, of which this log names some."""
         super().__init__()
-        self._keys, self._buf, self._event = keys, buf, event
+        self._keys, self._buf, self._event, self._index = keys, buf, event, index
         self.set_host(host_items)
 
     @classmethod
@@ -30,7 +31,8 @@ class DeferredLog(dict):
         if self._keys is not None:
             if self._event is not None:
                 self._event.synchronize()
-            vals = dict(zip(self._keys, self._buf.tolist()))
+            got = self._buf.tolist()
+            vals = dict(zip(self._keys, got if self._index is None else [got[i] for i in self._index]))
             if 'actor_loss' in vals:
                 vals['actor_loss'] = (vals['actor_loss'],)      # a 1-tuple upstream (reference :430); kept
             self._keys = None
