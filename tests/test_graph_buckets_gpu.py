@@ -36,6 +36,17 @@ def _value(v):
     return v[0] if isinstance(v, tuple) else v
 
 
+def _key_len(g, bucketed):
+    """Entries of a graph key of the driver `g`, from the key function on the plan of its last pass."""
+    from offpolicy_rnn.algorithm.graph_policy import exact_table_key, graph_key
+    from offpolicy_rnn.buffers.transition_buffer.shape_buckets import pad_seq_tables
+    pl, table = g._plan, ()
+    if g.alg._needs_seq_table:
+        built = g._build_seqs(pl)
+        table = pad_seq_tables(built, pl['nrow'], pl['longest'])[1] if bucketed else exact_table_key(built)
+    return len(graph_key(pl, table, bucketed, False))
+
+
 def _compare(what, alg_a, alg_b, logs_a, logs_b, rtol, atol):
     """Parameters, target parameters, log alpha and every logged scalar; every figure is printed before anything is asserted."""
     worst = []
@@ -112,7 +123,7 @@ def test_bucketed_replays_equal_the_eager_updates_on_the_same_shapes(rnn, algo, 
         graphed.grad_num += 1
     torch.cuda.synchronize()
     print(f'MEASURED {rnn} {algo} per {per}: graphs {len(g.graphs)} {sorted(g.graphs)}, eager updates {g.eager_fallbacks} of {n_upd}')
-    assert len(g.graphs) >= 1 and all(len(k) == 4 for k in g.graphs)
+    assert len(g.graphs) >= 1 and all(len(k) == _key_len(g, True) for k in g.graphs)
     assert g.eager_fallbacks <= (6 if per == 1 else 10)
     _compare(f'{rnn} {algo} per {per} replay vs eager', graphed, eager, logs_g, logs_e, rtol=2e-5, atol=1e-6)
 
@@ -162,7 +173,7 @@ def test_auto_mode_switches_on_ragged_data(no_noise):
     assert switched_at is not None and switched_at <= 8
     assert g.max_graphs == 2, 'a caller\'s max_graphs is kept'
     assert sum(replayed[11:24]) >= 10
-    assert all(len(k) == 4 for k in g.graphs) and 1 <= len(g.graphs) <= 2
+    assert all(len(k) == _key_len(g, True) for k in g.graphs) and 1 <= len(g.graphs) <= 2
 
 
 @pytest.mark.gpu
@@ -182,7 +193,7 @@ def test_auto_mode_never_switches_on_fixed_length_data(no_noise):
         g.step()
         alg.grad_num += 1
     torch.cuda.synchronize()
-    assert g.buckets == 'auto' and len(g.graphs) == 1 and all(len(k) == 5 for k in g.graphs)      # an exact key
+    assert g.buckets == 'auto' and len(g.graphs) == 1 and all(len(k) == _key_len(g, False) for k in g.graphs)      # an exact key
     assert g.eager_fallbacks <= 2                               # the warm-up update (and a first visit, had the shape changed)
 
 
@@ -231,6 +242,6 @@ def test_auto_mode_stays_exact_with_sequence_tables():
         torch.cuda.synchronize()
         print(f'MEASURED cgpt auto: {len(g._seen)} keys seen, buckets {g.buckets}')
         assert g.buckets == 'auto' and len(g._seen) >= 2, 'the shapes did not vary: nothing would have switched'
-        assert all(len(k) == 11 for k in g._seen)                               # exact key + the sizes of the two sequence tables + actor flag
+        assert all(len(k) == _key_len(g, False) for k in g._seen)                # exact key + the sizes of the two sequence tables + actor flag
     finally:
         g.close()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_graph_buckets_gpu import _state, _trainer, _value, no_noise  # noqa: F401  (no_noise: fixture)
+from test_graph_buckets_gpu import _key_len, _state, _trainer, _value, no_noise  # noqa: F401  (no_noise: fixture)
 from test_host_logic import _push, _synth, make_parameter
 
 CGPT = 'cgpt_h1_l2_p0.0_ml64_rms'
@@ -243,7 +243,7 @@ def test_ragged_cgpt_updates_replay(no_noise, monkeypatch):
                     assert np.isfinite(_value(v)), (k, v)
         torch.cuda.synchronize()
         print(f'MEASURED cgpt td3: graphs {len(g.graphs)} {sorted(g.graphs)}, eager updates {g.eager_fallbacks} of 24')
-        assert len(g.graphs) >= 1 and all(len(k) == 7 for k in g.graphs)
+        assert len(g.graphs) >= 1 and all(len(k) == _key_len(g, True) for k in g.graphs)
         assert g.eager_fallbacks <= 6
     finally:
         g.close()
@@ -276,6 +276,6 @@ def test_auto_mode_switches_with_sequence_buckets(no_noise):
         torch.cuda.synchronize()
         print(f'MEASURED cgpt auto with seq_buckets: switched at update {switched_at}, keys {sorted(g._seen)}')
         assert switched_at is not None and switched_at <= 4
-        assert g.max_graphs == 1 and all(len(k) == 7 for k in g._seen)
+        assert g.max_graphs == 1 and all(len(k) == _key_len(g, True) for k in g._seen)
     finally:
         g.close()

@@ -102,6 +102,7 @@ def test_ragged_batches_have_few_bucketed_shapes(rnn, oracle_ops):
     """24 updates' worth of plans from the real planner (the REDQ subset draw of an update follows each plan on the same numpy
     stream): the exact graph keys hardly recur (20-22 distinct for the packed families, 10 for gru, whose rows are not packed), the
     bucketed ones are 1-4 shapes."""
+    from offpolicy_rnn.algorithm.graph_policy import graph_key
     alg = ragged_trainer(rnn)
     par, buf = alg.parameter, alg.replay_buffer
     keys = {}
@@ -111,8 +112,7 @@ def test_ragged_batches_have_few_bucketed_shapes(rnn, oracle_ops):
         for _ in range(24):
             pl = buf.plan_trajs_device(par.sac_batch_size, None, random_trunc_traj=par.random_trunc_traj,
                                        nest_stack_trajs=alg.allow_nest_stack, buckets=buckets)
-            n = pl['seg'].shape[0]
-            keys[buckets].add((pl['nrow'], pl['longest'], n) if buckets else (pl['nrow'], pl['longest'], pl['max_len'], n))
+            keys[buckets].add(graph_key(pl, (), buckets, False))
             alg._select_target_ensemble(8)
     print(f'{rnn}: {len(keys[False])} exact keys, {len(keys[True])} bucketed keys in 24 plans: {sorted(keys[True])}')
     assert len(keys[True]) <= 5 and len(keys[False]) >= 10

@@ -81,7 +81,7 @@ for i in range(n):
     if i >= warm and gu is not None:
         pl = gu._plan
         tokens = int(pl['table'].sum())                              # packed tokens of the batch (its one-slot shift has a few less)
-        tb = gu._seq_now[0][0]                                       # length of the token table the kernels ran on
+        tb = gu.staging.seq_now[0][0]                                       # length of the token table the kernels ran on
         real, padded, slots = real + tokens, padded + tb, slots + pl['nrow'] * pl['longest']
         worst = max(worst, tb / tokens)
     if len(pending) > 2:
