@@ -633,6 +633,36 @@ int resel_step_state_reset(const int32_t* flags, int B, resel_reset_segs_t segs,
 int resel_categorical_step(const float* logits, int64_t ld_logits, const float* u, float floor, float* logp, int64_t ld_logp,
                            float* mode, float* sample, int64_t ld_idx, int M, int A, resel_stream_t stream);
 
+/* Environment step as the last node of a graphed policy step: the T-Maze memory task (reference envs/memory_envs/tmaze.py, TMazeBase
+ * with ambiguous positions; ids and constants of envs/memory_envs/configs/tmaze_{passive,active}.py) for the B rows of a batched
+ * evaluation - the per-row body of utility/policy_eval.py `run_episodes` and its `begin()`, as ONE launch on `stream`: one thread per
+ * row, no LDS, no atomics, no allocation, nothing read from the host: capturable.
+ *   cfg: cells (x, 0) for 0 <= x <= oracle_length + corridor_length and (oracle_length + corridor_length, +-1); an episode lasts
+ *     episode_length steps; the three rewards are doubles and the reward of a step is formed in double exactly as the host
+ *     environment forms it (env_utils/tmaze.py), signed zeros included.
+ *   action: the fp32 action index of row b at action[b * ld_action] (column 0 of the categorical head's output block), clamped into
+ *     [0, 4) (NaN: 0); 0..3 move by (1,0), (0,1), (-1,0), (0,-1), a move off the map leaves the position unchanged.
+ *   goals [B, J] int32 (row stride ld_goals >= J): goal side -1 / +1 of the j-th episode of row b; n_episodes [B] int32: the episodes
+ *     row b runs, clamped into [0, J].
+ *   env_state [B, RESEL_TMAZE_STATE_WORDS] int32: x, y, goal_y, oracle_visited, t, ep_len, episodes_started, running;  ret_acc [B]
+ *     double: the return of the running episode;  ep_ret double / ep_len int32 [B, J] (row stride ld_ep >= J): results per episode.
+ *   in_block: the step's input rows (row stride ld_in >= 2 * 2 + A + 1): state[2] | lst_state[2] | lst_action[A] | reward[1];
+ *     flags [B] int32: the step's reset flags.  Columns beyond the row's 2 * 2 + A + 1 are not touched.
+ * init != 0: `begin()` for every row and no step: all state words written, lst_state = lst_action = reward = 0, flag = 1, ret_acc = 0;
+ *   a row with n_episodes > 0 resets its environment with goals[b, 0] and gets the reset observation in `state`, any other row is
+ *   idle with state = 0.  Every evaluation starts with this call; nothing is assumed about the buffers before it.
+ * init == 0, idle row: zeros in the whole input row and flag = 1, nothing else.  Running row: the environment steps; lst_state <-
+ *   state, state <- the new observation, lst_action <- one-hot(index), reward <- (float)r, ret_acc += r (double, in step order),
+ *   ep_len += 1, flag = 0; when the episode is over ret_acc and ep_len go to [b, j], and the row begins episode j + 1 as above or
+ *   goes idle once it has run n_episodes[b].
+ * RESEL_EINVAL before the device is touched: a NULL pointer, A != 4, B < 0, J < 1, ld_in < 2 * 2 + A + 1, ld_action < 1, ld_goals < J,
+ * ld_ep < J, corridor_length < 1, oracle_length < 0, episode_length < 1, penalty > 0.  B == 0 launches nothing and returns 0. */
+#define RESEL_TMAZE_STATE_WORDS 8
+typedef struct { int32_t corridor_length, oracle_length, episode_length; double goal_reward, penalty, distract_reward; } resel_tmaze_cfg_t;
+int resel_tmaze_step(resel_tmaze_cfg_t cfg, int init, const float* action, int64_t ld_action, const int32_t* goals, int64_t ld_goals,
+                     const int32_t* n_episodes, int J, int32_t* env_state, double* ret_acc, double* ep_ret, int32_t* ep_len,
+                     int64_t ld_ep, float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream);
+
 /* ---- discrete-action update: differentiable categorical head, all-action value, the two discrete losses --------------------
  * (reference contextual_sac_discrete_policy.py:106-121 on whole rows; sac_full_length_rnn_redq.py:52-72 target, :85-86 actor,
  * sac_full_length_rnn_ensembleQ.py:158 critic on the action taken).  Raw fp32 device pointers; logits / logp / probs [M, A];

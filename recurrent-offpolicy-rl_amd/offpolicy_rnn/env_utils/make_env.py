@@ -1,7 +1,8 @@
 """Environment factory (reference offpolicy_rnn/env_utils/make_env.py:41-72).
 
 The simulator zoo of the reference (`envs/`) is out of scope.  Names of the form
-`synthetic-o<obs>-a<act>-T<len>` (or `-d<n>-` for n discrete actions) build the Gaussian environment used by the benchmark / tests; anything else is
+`synthetic-o<obs>-a<act>-T<len>` (or `-d<n>-` for n discrete actions) build the Gaussian environment used by the benchmark / tests;
+`Mem-T-{passive,active}-<L>[-cont-act]-v0` build the T-Maze memory task (env_utils/tmaze.py); anything else is
 handed to `gym.make` when gym is installed and fails loudly otherwise."""
 import re
 
@@ -67,6 +68,13 @@ def make_env(env_name: str, seed: int) -> dict:
         return dict(train_env=SyntheticEnv(obs, act, T, seed, disc), eval_env=SyntheticEnv(obs, act, T, seed + 1, disc), train_tasks=[],
                     eval_tasks=[None], max_rollouts_per_task=1, max_trajectory_len=T, obs_dim=obs, act_dim=act,
                     act_continuous=not disc, seed=seed, multiagent=False)
+    from .tmaze import TMaze, parse_name
+    kw = parse_name(env_name)
+    if kw is not None:                                   # Mem-T-{passive,active}-<L>[-cont-act]-v0: the reference's T-Maze ids
+        env, eval_env = TMaze(seed=seed, **kw), TMaze(seed=seed + 1, **kw)
+        return dict(train_env=env, eval_env=eval_env, train_tasks=[], eval_tasks=[None], max_rollouts_per_task=1,
+                    max_trajectory_len=env.episode_length, obs_dim=2, act_dim=4, act_continuous=env.continuous_act_space, seed=seed,
+                    multiagent=False)
     try:
         import gym
     except ImportError as e:

@@ -31,6 +31,13 @@ class ResetCounters(ctypes.Structure):
     _fields_ = [('pos', c_void_p * RESET_MAX_COUNTERS)]
 
 
+class TMazeCfg(ctypes.Structure):                       # resel_tmaze_cfg_t, by value
+    _fields_ = [('corridor_length', ctypes.c_int32), ('oracle_length', ctypes.c_int32), ('episode_length', ctypes.c_int32),
+                ('goal_reward', ctypes.c_double), ('penalty', ctypes.c_double), ('distract_reward', ctypes.c_double)]
+
+
+TMAZE_STATE_WORDS = 8
+
 # name -> (restype, argtypes); order and types mirror include/resel_hip.h
 SIGNATURES = {
     'resel_abi_version': (c_int, []),
@@ -125,6 +132,7 @@ SIGNATURES = {
     'resel_attn_decode_rows': (c_int, [P, L, P, P, P, P, F, I, I, I, I, S]),
     'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),
     'resel_categorical_step': (c_int, [P, L, P, F, P, L, P, P, L, I, I, S]),
+    'resel_tmaze_step': (c_int, [TMazeCfg, I, P, L, P, L, P, I, P, P, P, P, L, P, L, I, P, I, S]),
     'resel_categorical_fwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_categorical_bwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_discrete_value': (c_int, [P, P, I, P, P, P, I, I, I, S]),

@@ -20,9 +20,14 @@ position of the flagged rows, and every cgpt KV cache takes one position per row
 `resel_attn_decode_rows`).  The object issues the resets, so it mirrors the per-row positions on the host and refuses a step that
 would overrun a row's cache.
 
+`after_step=hook` appends work to the captured step: `hook(self)` runs as the last thing of the forward - in the warm-up and in the
+capture - and sees `_in_dev`, `_flags_dev` and `_out_dev`.  An environment that exists as a kernel (utility/policy_eval.py `DeviceEnvEval`,
+`ops.tmaze_step`) turns the output block into the next step's input block there; `capture()` then records the graph without a first host
+call and `replay_device()` replays it with no copy and no synchronise.  Without a hook the captured graph is what it was.
+
 Parameters are read through their storage, so in-place optimiser steps are seen by the next replay; call
 `invalidate()` after anything that re-allocates them (`load`, `.to`)."""
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 import torch
@@ -32,11 +37,13 @@ from . import ops
 
 
 class GraphedPolicyStep:
-    def __init__(self, policy, device, batch_size: int = 1, warmup: int = 2, row_reset: bool = False):
+    def __init__(self, policy, device, batch_size: int = 1, warmup: int = 2, row_reset: bool = False,
+                 after_step: Optional[Callable[['GraphedPolicyStep'], None]] = None):
         if torch.device(device).type != 'cuda':
             raise RuntimeError('GraphedPolicyStep replays a hipGraph: it needs a CUDA (ROCm) device')
         self.policy, self.device, self.B, self._warmup = policy, torch.device(device), batch_size, warmup
         self.row_reset = bool(row_reset)
+        self.after_step = after_step                              # last thing in the captured step (None: the graph ends at the state copies)
         self.categorical = bool(getattr(policy, 'categorical', False))
         self._row_pos = np.zeros(batch_size, dtype=np.int64)      # row_reset: host mirror of the per-row cgpt positions
         self._graph: Optional[torch.cuda.CUDAGraph] = None
@@ -94,6 +101,8 @@ class GraphedPolicyStep:
             elif isinstance(h, tuple):
                 for j, t in enumerate(h):
                     t.copy_(new_hidden[i][j].reshape(t.shape))
+        if self.after_step is not None:              # e.g. an environment step that turns `_out_dev` into the next `_in_dev` / `_flags_dev`
+            self.after_step(self)
 
     def _capture(self, obs_dim: int, act_dim: int):
         self._layout = dict(obs=obs_dim, act=act_dim)
@@ -137,6 +146,17 @@ class GraphedPolicyStep:
             else:
                 ip.device_offset.fill_(c)
         self._graph = graph
+
+    def capture(self, obs_dim: int, act_dim: int):
+        """Capture for rows of (obs_dim, act_dim) without a first host call (a no-op when that graph exists)."""
+        if self._graph is None or self._layout != dict(obs=obs_dim, act=act_dim):
+            with torch.no_grad():
+                self._capture(obs_dim, act_dim)
+
+    def replay_device(self):
+        """Replay only: no H2D, no D2H, no synchronise.  The inputs are what is in `_in_dev` / `_flags_dev` (an `after_step` hook
+        wrote them); the caller owns the host mirrors of the cgpt positions (`_row_pos`, `seqlen_offset`) and the full-cache check."""
+        self._graph.replay()
 
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()

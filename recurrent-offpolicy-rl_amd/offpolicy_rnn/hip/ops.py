@@ -2191,6 +2191,37 @@ def categorical_step(logits, u, floor=0.01, out=None):
 
 
 @torch.no_grad()
+def tmaze_step(cfg: dict, init: bool, action, goals, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags):
+    """One T-Maze environment step (or, init: the start of an evaluation) for the B rows of a graphed policy step, as one launch:
+    include/resel_hip.h `resel_tmaze_step`, host twin env_utils/tmaze.py.  cfg: `TMaze.device_config()`.
+    action: fp32 [B] view, any stride - the action indices (column 0 of the categorical step's output block);
+    goals int32 [B, J], n_episodes int32 [B] (each at most J), env_state int32 [B, 8], ret_acc fp64 [B], ep_ret fp64 / ep_len int32 [B, J];
+    in_block fp32 [B, >= 9] with unit column stride (state[2] | lst_state[2] | lst_action[4] | reward[1]), flags int32 [B].
+    Everything is updated in place; nothing else on the stream, no host read, no allocation: capturable."""
+    from ._lib import TMAZE_STATE_WORDS, TMazeCfg
+    _need_cuda('tmaze_step', action, goals, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags)
+    B, A = flags.numel(), 4
+    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
+    assert action.dtype == torch.float32 and action.dim() == 1 and action.numel() == B
+    assert goals.dtype == torch.int32 and goals.dim() == 2 and goals.shape[0] == B and (goals.stride(1) == 1 or goals.shape[1] == 1)
+    J = goals.shape[1]
+    assert n_episodes.dtype == torch.int32 and n_episodes.is_contiguous() and n_episodes.numel() == B
+    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, TMAZE_STATE_WORDS)
+    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
+    assert ep_ret.dtype == torch.float64 and ep_len.dtype == torch.int32 and ep_ret.shape == ep_len.shape == (B, J)
+    assert ep_ret.is_contiguous() and ep_len.is_contiguous()
+    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
+    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    c = TMazeCfg(int(cfg['corridor_length']), int(cfg['oracle_length']), int(cfg['episode_length']), float(cfg['goal_reward']),
+                 float(cfg['penalty']), float(cfg['distract_reward']))
+    check(lib().resel_tmaze_step(c, int(bool(init)), _p(action), max(action.stride(0), 1), _p(goals), max(goals.stride(0), J),
+                                 _p(n_episodes), J, _p(env_state), _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block),
+                                 max(in_block.stride(0), 2 * 2 + A + 1), A, _p(flags), B, _stream()), 'tmaze_step')
+
+
+@torch.no_grad()
 def soft_update_(target_flat, online_flat, tau):
     _need_cuda('soft_update', target_flat, online_flat)
     PARAM_EPOCH[0] += 1

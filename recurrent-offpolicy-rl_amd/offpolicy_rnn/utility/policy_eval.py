@@ -7,7 +7,13 @@ per environment step for all of them - and an episode that ends hands its row to
 position are reset inside the graph, hip/graph_step.py).
 
 `run_episodes` is the scheduler (host only, numpy in / numpy out); `BatchedPolicyEval` owns the graph, the environments and a private
-random stream, and leaves every global generator as it found it."""
+random stream, and leaves every global generator as it found it.
+
+An environment that exists as a kernel (the discrete T-Maze, env_utils/tmaze.py / `ops.tmaze_step`) is stepped INSIDE the graph:
+`DeviceEnvEval` appends the environment step to the policy step as its last node, so an evaluation is `waves x episode_length`
+back-to-back replays behind one init call, with one D2H at the end and no host round trip per step.  `RESEL_DEVICE_ENV=0` keeps
+such an environment on the host loop."""
+import os
 import random
 from typing import Callable, Dict, List, Optional
 
@@ -85,6 +91,97 @@ def run_episodes(step: Callable, envs: List, n_episodes: int, obs_dim: int, act_
     return out, ep_row
 
 
+DEVICE_ENV_DEFAULT = '1'                                   # RESEL_DEVICE_ENV when the variable is not set
+
+
+def device_env_enabled() -> bool:
+    return os.environ.get('RESEL_DEVICE_ENV', DEVICE_ENV_DEFAULT) != '0'
+
+
+class DeviceEnvEval:
+    """`run_episodes` for `rows` discrete T-Mazes with the environment step inside the graphed policy step.
+
+    All episodes have the same length T, so the host scheduler runs episode k on row k % rows as that row's (k // rows)-th episode and
+    takes ceil(n / rows) * T steps; this object does the same with one `ops.tmaze_step(init=True)` call, that many `replay_device()`
+    calls, one D2H of the per-episode results and one synchronise.  The goal sides come from the per-row host environments
+    (`TMaze.draw_goal`, the draw their `reset()` makes), in the order the host loop would draw them.
+    The hook runs in the warm-up and in the capture too, on whatever the buffers hold: every buffer is (re)initialised by the init
+    call of each evaluation, never at capture."""
+
+    def __init__(self, policy, envs: List, device):
+        from ..hip._lib import TMAZE_STATE_WORDS
+        from ..hip.graph_step import GraphedPolicyStep
+        self.envs, self.rows, self.device = envs, len(envs), torch.device(device)
+        self.cfg = envs[0].device_config()
+        assert all(e.device_config() == self.cfg for e in envs), 'one graph steps one kind of environment'
+        self.T, self.obs_dim, self.act_dim = int(self.cfg['episode_length']), 2, 4
+        self.step = GraphedPolicyStep(policy, self.device, batch_size=self.rows, row_reset=True, after_step=self._env_step)
+        self.J = 0
+        dev = self.device
+        self._env_state = torch.zeros((self.rows, TMAZE_STATE_WORDS), dtype=torch.int32, device=dev)
+        self._ret_acc = torch.zeros(self.rows, dtype=torch.float64, device=dev)
+
+    def _ensure(self, J: int):
+        """Tables for J episodes per row.  Their addresses are part of the captured graph: growing them captures again."""
+        if J <= self.J:
+            return
+        B, dev = self.rows, self.device
+        self._tab_host = torch.zeros(B * J + B, dtype=torch.int32).pin_memory()           # goals [B, J] | n_episodes [B]: one H2D
+        self._tab_dev = torch.zeros(B * J + B, dtype=torch.int32, device=dev)
+        self._goals, self._n_ep = self._tab_dev[:B * J].view(B, J), self._tab_dev[B * J:]
+        self._res_dev = torch.zeros(B * J * 12, dtype=torch.uint8, device=dev)            # ep_ret fp64 [B, J] | ep_len int32 [B, J]: one D2H
+        self._res_host = torch.zeros(B * J * 12, dtype=torch.uint8).pin_memory()
+        self._ep_ret, self._ep_len = self._res_dev[:B * J * 8].view(torch.float64).view(B, J), self._res_dev[B * J * 8:].view(torch.int32).view(B, J)
+        self.J = J
+        self.step.invalidate()
+
+    def _env_step(self, step):
+        from ..hip import ops
+        ops.tmaze_step(self.cfg, False, step._out_dev[:, 0], self._goals, self._n_ep, self._env_state, self._ret_acc, self._ep_ret,
+                       self._ep_len, step._in_dev, step._flags_dev)
+
+    def invalidate(self):
+        self.step.invalidate()
+
+    @torch.no_grad()
+    def run(self, n_episodes: int):
+        """-> what `run_episodes` returns for these environments: ({'EpRetTest': [...], 'EpLenTest': [...]}, [row of each episode])."""
+        from ..hip import ops
+        n, B, T, step = int(n_episodes), self.rows, self.T, self.step
+        if n <= 0:
+            return {'EpRetTest': [], 'EpLenTest': []}, []
+        waves = -(-n // B)
+        self._ensure(waves)
+        J = self.J
+        step.capture(self.obs_dim, self.act_dim)
+        for ip in step._counters():                                          # what `__call__` raises at the step that would overrun
+            if T > ip.max_seqlen:
+                raise RuntimeError(f'cgpt rollout: KV cache is full (row 0: {ip.max_seqlen} tokens, max_seqlen {ip.max_seqlen})')
+        per_row = [len(range(r, n, B)) for r in range(B)]                    # ceil((n - r) / rows)
+        tab = self._tab_host.numpy()
+        tab[:] = 0
+        for r, env in enumerate(self.envs):                                  # each row's own stream, in draw order
+            for j in range(per_row[r]):
+                tab[r * J + j] = env.draw_goal()
+        tab[B * J:] = per_row
+        self._tab_dev.copy_(self._tab_host, non_blocking=True)
+        ops.tmaze_step(self.cfg, True, step._out_dev[:, 0], self._goals, self._n_ep, self._env_state, self._ret_acc, self._ep_ret,
+                       self._ep_len, step._in_dev, step._flags_dev)
+        for _ in range(waves * T):
+            step.replay_device()
+        self._res_host.copy_(self._res_dev, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        # the host mirrors of the cgpt positions, as the same schedule through `__call__` leaves them: a row of the last wave is
+        # T tokens into its episode, a row that went idle earlier was fed one flagged step after another (position 0, then 1)
+        step._row_pos = np.array([T if per_row[r] == waves else 1 for r in range(B)], dtype=np.int64)
+        for ip in step._counters():
+            ip.seqlen_offset = int(step._row_pos.max())
+        res = self._res_host.numpy()
+        ep_ret, ep_len = res[:B * J * 8].view(np.float64).reshape(B, J), res[B * J * 8:].view(np.int32).reshape(B, J)
+        out = {'EpRetTest': [float(ep_ret[k % B, k // B]) for k in range(n)], 'EpLenTest': [int(ep_len[k % B, k // B]) for k in range(n)]}
+        return out, [k % B for k in range(n)]
+
+
 def _is_training(policy) -> bool:
     mods = getattr(policy, 'contextual_modules', None)
     if mods:
@@ -109,12 +206,16 @@ class BatchedPolicyEval:
         self.eval_tasks, self.discrete = eval_tasks, bool(discrete)
         self.rs = np.random.RandomState(seed)
         self.step, self.envs, self.env_seeds = step, None, []
+        self._host_only = step is not None                 # a replacement step is a host callable: never the in-graph environment
+        self.device_env: Optional[DeviceEnvEval] = None
         self.last_rows: List[int] = []                     # row that ran each episode of the last evaluation
 
     def invalidate(self):
         """After anything that re-allocates the policy's parameters (`load`, `.to`): capture again at the next evaluation."""
         if hasattr(self.step, 'invalidate'):
             self.step.invalidate()
+        if self.device_env is not None:
+            self.device_env.invalidate()
 
     def _reset_env(self, env):
         if hasattr(env, 'meta_env_flag') and getattr(env, 'n_tasks', None) is not None:
@@ -131,9 +232,19 @@ class BatchedPolicyEval:
                 env.observation_space.seed(seed + 7)
                 self.envs.append(env)
                 self.env_seeds.append(seed)
+        if self._on_device():
+            if self.device_env is None:
+                self.device_env = DeviceEnvEval(self.policy, self.envs, self.device)
+            return
         if self.step is None:
             from ..hip.graph_step import GraphedPolicyStep
             self.step = GraphedPolicyStep(self.policy, self.device, batch_size=self.rows, row_reset=True)
+
+    def _on_device(self) -> bool:
+        """The in-graph environment step: discrete T-Mazes behind a categorical policy on a CUDA device, unless RESEL_DEVICE_ENV=0."""
+        from ..env_utils.tmaze import device_steppable
+        return (not self._host_only and self.discrete and self.device.type == 'cuda' and device_env_enabled()
+                and bool(getattr(self.policy, 'categorical', False)) and all(device_steppable(e) for e in self.envs))
 
     def evaluate(self, n_episodes: int) -> Dict[str, list]:
         """n_episodes deterministic episodes (action = the policy's mean) of the current parameters, which the graph reads through
@@ -147,6 +258,9 @@ class BatchedPolicyEval:
             if self.policy is not None:
                 self.policy.eval()
             self._make()
+            if self._on_device():
+                out, self.last_rows = self.device_env.run(int(n_episodes))
+                return out
             obs_dim = self.envs[0].observation_space.shape[0]
 
             def step(state, lst_state, lst_action, reward, reset):

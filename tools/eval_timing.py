@@ -3,8 +3,9 @@
 (b) the 10 episodes one after another through the B = 1 graphed step with `load_hidden(None)` between them - the only form there
     was before `row_reset`.
 Both run the same host loop (`run_episodes`), the same environments and the policy in eval mode.  `--env synthetic-o17-d6-T1000` (any
-synthetic name, make_env.py) replaces the benchmark's environment; a `-d<n>-` name is a discrete-action run: categorical policy, the
-evaluator's discrete form.
+name make_env.py builds without gym) replaces the benchmark's environment; a name with discrete actions (`-d<n>-`, `Mem-T-...-v0`) is a
+discrete-action run: categorical policy, the evaluator's discrete form.  A discrete T-Maze (`Mem-T-passive-1000-v0`) is stepped inside
+the graph of leg (a) unless RESEL_DEVICE_ENV=0 (utility/policy_eval.py `DeviceEnvEval`); `device_env` in the output says which it was.
 
     python tools/eval_timing.py [--rnn smamba_s32_c16_b2_nln cgpt_h8_l6_p0.1_ml1024_rms] [--episodes 10] [--steps 1000] [--n 3]
                                 [--env synthetic-o17-d6-T1000]
@@ -26,7 +27,9 @@ ap.add_argument('--rnn', nargs='+', default=['smamba_s32_c16_b2_nln', 'cgpt_h8_l
 ap.add_argument('--episodes', type=int, default=10)
 ap.add_argument('--steps', type=int, default=1000)
 ap.add_argument('--n', type=int, default=3)
-ap.add_argument('--env', default=None, help='synthetic-o<obs>-[ad]<act>-T<len>: replaces the benchmark environment and --steps')
+ap.add_argument('--env', default=None, help='synthetic-o<obs>-[ad]<act>-T<len> or Mem-T-{passive,active}-<L>-v0: replaces the benchmark '
+                                            'environment and --steps')
+ap.add_argument('--skip-one-by-one', action='store_true', help='time leg (a) only')
 args = ap.parse_args()
 
 import numpy as np
@@ -53,7 +56,7 @@ def timed(fn):
 for rnn in args.rnn:
     torch.manual_seed(1234)
     np.random.seed(1234)
-    discrete = args.env is not None and '-d' in args.env
+    discrete = args.env is not None and not make_env(args.env, 0)['act_continuous']
     par = bench.make_parameter(rnn, 2, args.steps, algo='td3' if rnn.startswith('cgpt') and not discrete else 'sac')
     if args.env is not None:
         par.env_name = args.env
@@ -78,10 +81,11 @@ for rnn in args.rnn:
             return run_episodes(step, [env], args.episodes, alg.obs_dim, alg.act_dim, lambda e: e.reset(), discrete=discrete)[0]
         finally:
             alg.policy.train()
-    t_one = timed(one_by_one)
+    t_one = [float('nan')] * args.n if args.skip_one_by_one else timed(one_by_one)
     med = statistics.median
     print(json.dumps(dict(
-        rnn=rnn, env=par.env_name, episodes=args.episodes, steps=args.steps, n=args.n,
+        rnn=rnn, env=par.env_name, episodes=args.episodes, steps=args.steps, n=args.n, device_env=batched.device_env is not None,
+        rows_graph_all_s=[round(t, 4) for t in t_rows],
         rows_graph_s=dict(median=round(med(t_rows), 4), min=round(min(t_rows), 4), max=round(max(t_rows), 4)),
         one_by_one_s=dict(median=round(med(t_one), 4), min=round(min(t_one), 4), max=round(max(t_one), 4)),
         us_per_replay=dict(rows_graph=round(1e6 * med(t_rows) / args.steps, 1), one_by_one=round(1e6 * med(t_one) / (args.steps * args.episodes), 1)),
