@@ -663,6 +663,36 @@ int resel_tmaze_step(resel_tmaze_cfg_t cfg, int init, const float* action, int64
                      const int32_t* n_episodes, int J, int32_t* env_state, double* ret_acc, double* ep_ret, int32_t* ep_len,
                      int64_t ld_ep, float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream);
 
+/* ---- T-Maze training rollout inside the graphed policy step: one iteration of the collection loop per replay ----------------
+ * (reference algorithm/sac.py:319-353: sample, env.step, mem_push of the transition, the next step's inputs; host twin: `SAC._train_loop`
+ * with `SAC._push` / `SAC.env_step`, buffers/transition_buffer/replay_memory.py `transition_to_array`).  The LAST node of the policy step's
+ * graph, as the entry above, with the same environment arithmetic (shared device functions) and the same env_state words; what differs is
+ * that the action is the SAMPLED index (column 1 of the categorical step's block), that every step also writes the transition the ring
+ * stores, and that a row never begins an episode by itself: the host starts each one with an init call outside the graph.
+ *   action [B] fp32, stride ld_action: the sampled indices, clamped into [0, 4) (NaN: 0).   goal [B] int32: the goal side of the episode
+ *     an init call begins (-1 / +1; read by init only).   env_state int32 [B, 8], ret_acc double [B]: word 5 is the number of steps taken,
+ *     word 7 whether the episode runs; ret_acc the return so far, summed in double in step order.
+ *   traj fp32 [B, T_cap, ld_row]: the episode block; step `len` (0-based) of row b writes transition row [b, len, :].
+ *   lay: the first column of each ring field in a transition row (`MemoryArray.name2range`), -1 = the ring does not store it.  Widths:
+ *     state, last_state, next_state 2; last_action A; action, reward, mask, start, done, reward_input, timeout 1.  The rollout has no
+ *     log-probability: lay.logp must be -1.  Fields may stand in any order; columns no field covers are not touched.
+ *   in_block fp32 [B, ld_in]: state[2] | lst_state[2] | lst_action[A] | reward[1], the policy step's input rows.
+ * init != 0: `env_reset()` for every row and no step: state words zeroed, the environment reset with goal[b], ret_acc = 0, the reset
+ *   observation in `state`, zeros in lst_state / lst_action / reward; the row runs.  traj is not touched.
+ * init == 0, running row, step len: with `old` the input row as the policy step just read it and a the clamped index, the environment
+ *   steps; traj[b, len] <- state, last_state, last_action, reward_input = old;  action = (float)a;  next_state = the new observation;
+ *   reward = (float)r;  mask = 1;  start = (len == 0);  done;  timeout = (len + 1 >= max_episode_steps);  then the input row becomes
+ *   lst_state <- old state, state <- the new observation, lst_action <- one-hot(a), reward <- (float)r;  ret_acc += r;  len += 1;  at
+ *   done the row stops.  A step with len >= T_cap writes no transition row (everything else proceeds).
+ * init == 0, stopped row: nothing is read or written.
+ * RESEL_EINVAL before the device is touched: a NULL pointer, A != 4, B < 0, T_cap < 1, max_episode_steps < 1, ld_in < 2 * 2 + A + 1,
+ * ld_action < 1, lay.logp >= 0, ld_row smaller than the furthest end of a present field, or a cfg the entry above refuses.  B == 0
+ * launches nothing and returns 0.  One thread per row; no LDS, atomics, host read or allocation: capturable. */
+typedef struct { int32_t state, last_state, last_action, action, next_state, reward, logp, mask, start, done, reward_input, timeout; } resel_collect_layout_t;
+int resel_tmaze_collect_step(resel_tmaze_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                             const int32_t* goal, int32_t* env_state, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream);
+
 /* ---- discrete-action update: differentiable categorical head, all-action value, the two discrete losses --------------------
  * (reference contextual_sac_discrete_policy.py:106-121 on whole rows; sac_full_length_rnn_redq.py:52-72 target, :85-86 actor,
  * sac_full_length_rnn_ensembleQ.py:158 critic on the action taken).  Raw fp32 device pointers; logits / logp / probs [M, A];

@@ -5,6 +5,8 @@
 // step's input row and reset flag into the step's device block, so an evaluation is back-to-back graph replays with no host
 // round trip.  One thread per row, 64-thread blocks, a few dozen scalar operations: latency of one launch, nothing to tune.
 // No LDS, no atomics, nothing read from the host, no allocation: capturable.
+// The training rollout has a kernel of the same shape (`tmaze_collect_kernel`, the per-row body of one iteration of `SAC._train_loop`):
+// the same move / reward / observation functions on the SAMPLED index, plus the transition row the replay ring stores.
 #include "resel_common.h"
 
 namespace {
@@ -26,6 +28,42 @@ __device__ __forceinline__ void observe(const resel_tmaze_cfg_t& cfg, int32_t* s
         obs[0] = 1.f;
         obs[1] = (float)st[SY];
     }
+}
+
+// The action index as the head kernel wrote it (fp32), clamped into [0, 4); NaN fails both tests: 0.
+__device__ __forceinline__ int clamp_action(float af) { return af >= 3.f ? 3 : (af >= 0.f ? (int)af : 0); }
+
+// One move of `TMaze.step`: the clock advances, the agent moves unless the target cell is off the map.  -> done
+__device__ __forceinline__ bool move(const resel_tmaze_cfg_t& cfg, int32_t* st, int a) {
+    const int t = st[ST] + 1;
+    int x = st[SX], y = st[SY];
+    const int nx = x + (a == 0) - (a == 2), ny = y + (a == 1) - (a == 3);
+    const int end = cfg.oracle_length + cfg.corridor_length;
+    if ((ny == 0 && nx >= 0 && nx <= end) || (nx == end && (ny == 1 || ny == -1))) {
+        x = nx;
+        y = ny;
+    }
+    st[ST] = t;
+    st[SX] = x;
+    st[SY] = y;
+    return t >= cfg.episode_length;
+}
+
+// Reward of the step `move` just made: the host twin's expressions, one rounding each (no contraction): -0.0 survives.
+__device__ __forceinline__ double reward(const resel_tmaze_cfg_t& cfg, const int32_t* st, bool done) {
+    if (done) return __dmul_rn(st[SY] == st[SGOAL] ? 1.0 : 0.0, cfg.goal_reward);
+    double r = __dmul_rn(st[SX] < st[ST] - cfg.oracle_length ? 1.0 : 0.0, cfg.penalty);
+    if (st[SX] == 0) r = __dadd_rn(r, cfg.distract_reward);
+    return r;
+}
+
+// The input row of the next policy step: lst_state <- state, state <- the new observation, lst_action <- one-hot(a), reward <- (float)r.
+__device__ __forceinline__ void feed_back(const resel_tmaze_cfg_t& cfg, int32_t* st, float* in, int a, int A, double r) {
+    in[2] = in[0];
+    in[3] = in[1];
+    observe(cfg, st, in);
+    for (int c = 0; c < A; ++c) in[4 + c] = c == a ? 1.f : 0.f;
+    in[4 + A] = (float)r;
 }
 
 // `begin()` of the scheduler for one row: zero last state / last action / reward, flag set, and either the reset observation of
@@ -74,32 +112,10 @@ __global__ __launch_bounds__(64) void tmaze_step_kernel(resel_tmaze_cfg_t cfg, i
         flags[b] = 1;
         return;
     }
-    const float af = action[(int64_t)b * ld_action];
-    const int a = af >= 3.f ? 3 : (af >= 0.f ? (int)af : 0);             // clamp into [0, 4); NaN fails both tests: 0
-    const int t = st[ST] + 1;
-    int x = st[SX], y = st[SY];
-    const int nx = x + (a == 0) - (a == 2), ny = y + (a == 1) - (a == 3);
-    const int end = cfg.oracle_length + cfg.corridor_length;
-    if ((ny == 0 && nx >= 0 && nx <= end) || (nx == end && (ny == 1 || ny == -1))) {
-        x = nx;
-        y = ny;
-    }
-    st[ST] = t;
-    st[SX] = x;
-    st[SY] = y;
-    const bool done = t >= cfg.episode_length;
-    double r;                                             // the host twin's expressions, one rounding each (no contraction): -0.0 survives
-    if (done) {
-        r = __dmul_rn(y == st[SGOAL] ? 1.0 : 0.0, cfg.goal_reward);
-    } else {
-        r = __dmul_rn(x < t - cfg.oracle_length ? 1.0 : 0.0, cfg.penalty);
-        if (x == 0) r = __dadd_rn(r, cfg.distract_reward);
-    }
-    in[2] = in[0];
-    in[3] = in[1];
-    observe(cfg, st, in);
-    for (int c = 0; c < A; ++c) in[4 + c] = c == a ? 1.f : 0.f;
-    in[4 + A] = (float)r;
+    const int a = clamp_action(action[(int64_t)b * ld_action]);
+    const bool done = move(cfg, st, a);
+    const double r = reward(cfg, st, done);
+    feed_back(cfg, st, in, a, A, r);
     const double ret = __dadd_rn(ret_acc[b], r);
     ret_acc[b] = ret;
     const int len = st[SLEN] + 1;
@@ -115,9 +131,91 @@ __global__ __launch_bounds__(64) void tmaze_step_kernel(resel_tmaze_cfg_t cfg, i
     }
 }
 
+// ---- training rollout: one iteration of `SAC._train_loop` per replay ---------------------------------------------------------
+// Columns the transition row needs: the furthest end of a present field (widths: observations 2, last action A, scalars 1).
+__device__ __host__ inline int layout_need(const resel_collect_layout_t& lay, int A) {
+    const int off[11] = {lay.state, lay.last_state, lay.last_action, lay.action, lay.next_state, lay.reward,
+                         lay.mask,  lay.start,      lay.done,        lay.reward_input, lay.timeout};
+    const int wid[11] = {2, 2, A, 1, 2, 1, 1, 1, 1, 1, 1};
+    int need = 0;
+    for (int f = 0; f < 11; ++f)
+        if (off[f] >= 0 && off[f] + wid[f] > need) need = off[f] + wid[f];
+    return need;
+}
+
+__device__ __forceinline__ void put(float* row, int off, const float* v, int w) {
+    if (off < 0) return;                                  // a field the ring does not store
+    for (int c = 0; c < w; ++c) row[off + c] = v[c];
+}
+
+__device__ __forceinline__ void put1(float* row, int off, float v) {
+    if (off >= 0) row[off] = v;
+}
+
+__global__ __launch_bounds__(64) void tmaze_collect_kernel(resel_tmaze_cfg_t cfg, resel_collect_layout_t lay, int init,
+                                                           const float* __restrict__ action, int64_t ld_action,
+                                                           const int32_t* __restrict__ goal, int32_t* __restrict__ env_state,
+                                                           double* __restrict__ ret_acc, float* __restrict__ traj, int T_cap, int64_t ld_row,
+                                                           int max_episode_steps, float* __restrict__ in_block, int64_t ld_in, int B) {
+    constexpr int A = 4;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int32_t* st = env_state + (int64_t)b * RESEL_TMAZE_STATE_WORDS;
+    float* in = in_block + (int64_t)b * ld_in;
+    if (init) {                                           // `env_reset()`: the reset observation, zero last state / last action / reward
+        for (int w = 0; w < RESEL_TMAZE_STATE_WORDS; ++w) st[w] = 0;
+        for (int c = 2; c < 4 + A + 1; ++c) in[c] = 0.f;
+        ret_acc[b] = 0.0;
+        st[SX] = cfg.oracle_length;
+        st[SGOAL] = goal[b];
+        st[SSTARTED] = 1;
+        st[SRUNNING] = 1;
+        observe(cfg, st, in);
+        return;
+    }
+    if (!st[SRUNNING]) return;                            // the episode is over: the row waits for the host's next init, untouched
+    const int a = clamp_action(action[(int64_t)b * ld_action]);
+    const int len = st[SLEN];
+    float before[4 + A + 1];                              // state | last_state | last_action | reward_input as the policy just saw them
+    for (int c = 0; c < 4 + A + 1; ++c) before[c] = in[c];
+    const bool done = move(cfg, st, a);
+    const double r = reward(cfg, st, done);
+    feed_back(cfg, st, in, a, A, r);
+    if (len >= 0 && len < T_cap && layout_need(lay, A) <= ld_row) {       // what `SAC._push` stores, at row `len` of the episode block
+        float* row = traj + ((int64_t)b * T_cap + len) * ld_row;
+        put(row, lay.state, before, 2);
+        put(row, lay.last_state, before + 2, 2);
+        put(row, lay.last_action, before + 4, A);
+        put1(row, lay.action, (float)a);
+        put(row, lay.next_state, in, 2);
+        put1(row, lay.reward, (float)r);
+        put1(row, lay.mask, 1.f);
+        put1(row, lay.start, len == 0 ? 1.f : 0.f);
+        put1(row, lay.done, done ? 1.f : 0.f);
+        put1(row, lay.reward_input, before[4 + A]);
+        put1(row, lay.timeout, len + 1 >= max_episode_steps ? 1.f : 0.f);
+    }
+    ret_acc[b] = __dadd_rn(ret_acc[b], r);
+    st[SLEN] = len + 1;
+    if (done) st[SRUNNING] = 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int resel_tmaze_collect_step(resel_tmaze_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                             const int32_t* goal, int32_t* env_state, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream) {
+    if (!action || !goal || !env_state || !ret_acc || !traj || !in_block) return RESEL_EINVAL;
+    if (A != 4 || B < 0 || ld_in < 2 * 2 + A + 1 || ld_action < 1 || T_cap < 1 || max_episode_steps < 1) return RESEL_EINVAL;
+    if (cfg.corridor_length < 1 || cfg.oracle_length < 0 || cfg.episode_length < 1 || !(cfg.penalty <= 0.0)) return RESEL_EINVAL;
+    if (lay.logp >= 0 || ld_row < 1 || layout_need(lay, A) > ld_row) return RESEL_EINVAL;
+    if (B == 0) return RESEL_OK;
+    hipLaunchKernelGGL(tmaze_collect_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cfg, lay, init, action, ld_action,
+                       goal, env_state, ret_acc, traj, T_cap, ld_row, max_episode_steps, in_block, ld_in, B);
+    return launch_status();
+}
 
 int resel_tmaze_step(resel_tmaze_cfg_t cfg, int init, const float* action, int64_t ld_action, const int32_t* goals, int64_t ld_goals,
                      const int32_t* n_episodes, int J, int32_t* env_state, double* ret_acc, double* ep_ret, int32_t* ep_len, int64_t ld_ep,

@@ -91,6 +91,8 @@ class SAC:
             self.graph_step = GraphedPolicyStep(self.policy, self.sample_device, batch_size=1)
         self.evaluator = None                   # BatchedPolicyEval, built by the first evaluate()
         self._eval_refusal_logged = False
+        self.collector = None                   # DeviceCollector of the running / last train(), when it collected on the device
+        self._collect_refusal_logged = False
         self.sample_num = 0
         self.grad_num = 0
         self.start_time = time.time()
@@ -232,9 +234,19 @@ class SAC:
                 # turns out ragged (fixed-length ones never switch), 0 / unset = exact shapes only
                 graphed = GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())
                 update = graphed.step
+        # a discrete T-Maze is collected on the device (utility/device_collect.py): environment step, transition row and next inputs are the
+        # last node of the policy step's graph; RESEL_DEVICE_COLLECT (read here) switches it, every other run keeps the host loop below
+        from ..utility.device_collect import DeviceCollector
+        why = DeviceCollector.refusal(self)
+        self.collector = None if why else DeviceCollector(self)
+        if why and not self._collect_refusal_logged:
+            self.logger(f'training episodes are collected through the host loop ({why})')
+            self._collect_refusal_logged = True
         try:
             self._train_loop(update)
         finally:
+            if self.collector is not None:      # rollout mirrors, environment fields and the B = 1 step's state as the host loop leaves them
+                self.collector.sync_host()
             if graphed is not None:             # detach the process-wide dropout base: later eager trainers of this process draw from torch's generator again
                 graphed.close()
 
@@ -273,16 +285,19 @@ class SAC:
             self.policy.train()
             self.policy.to(self.sample_device)
             for _ in range(self.parameter.step_per_iteration):
-                act_sample = self.sample_action()
-                act_env = unorm_act(act_sample[0], self.env.action_space)
-                next_state, reward, done, _ = self.env.step(int(np.asarray(act_env).reshape(-1)[0]) if self.discrete_env else act_env)
-                ep_ret += reward
-                ep_len += 1
-                self._push(act_sample, next_state, reward, done, ep_len)
-                self.env_step(next_state, act_sample, reward, done)
-                if done:
-                    self.logger.add_tabular_data(tb_prefix='Train', EpRet=ep_ret, EpLength=ep_len)
-                    ep_ret, ep_len = 0.0, 0
+                if self.collector is not None:                    # the same iteration inside the step's graph; an episode's last step pushes and logs it
+                    self.collector.collect_step()
+                else:
+                    act_sample = self.sample_action()
+                    act_env = unorm_act(act_sample[0], self.env.action_space)
+                    next_state, reward, done, _ = self.env.step(int(np.asarray(act_env).reshape(-1)[0]) if self.discrete_env else act_env)
+                    ep_ret += reward
+                    ep_len += 1
+                    self._push(act_sample, next_state, reward, done, ep_len)
+                    self.env_step(next_state, act_sample, reward, done)
+                    if done:
+                        self.logger.add_tabular_data(tb_prefix='Train', EpRet=ep_ret, EpLength=ep_len)
+                        ep_ret, ep_len = 0.0, 0
                 if self.sample_num % self.parameter.update_interval == 0 and self.sample_num >= self.parameter.start_train_num:
                     self.logger.add_tabular_data(tb_prefix='train', **update())
                     self.grad_num += 1

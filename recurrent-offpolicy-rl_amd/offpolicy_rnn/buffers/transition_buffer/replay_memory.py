@@ -145,6 +145,37 @@ class MemoryArray:
         if self.ptr >= self.max_transition_num:
             self.ptr = 0
 
+    def push_rows(self, rows: np.ndarray):
+        """Bulk insert of one finished trajectory given as its stored rows, fp32 [n, width] in this ring's column layout (what
+        `transition_to_array` makes of each transition) - the same ring, tables, `ptr`, counters, dirty ranges and eviction as n
+        `mem_push` calls ending in `done`, without a Python object per transition.  The layout must exist (a first `mem_push`-ed
+        trajectory, or `push_trajectory`, fixes it), and no partial trajectory may be pending in `self.memory`: its transitions would
+        end up behind rows that were collected after them."""
+        if self.memory:
+            raise RuntimeError(f'push_rows: {len(self.memory)} transitions of an unfinished trajectory are pending in `memory`')
+        if self.memory_buffer is None:
+            raise RuntimeError('push_rows: the ring has no column layout yet (it is fixed by the first trajectory pushed as transitions)')
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.width or rows.dtype != self.STORE_DTYPE or len(rows) == 0:
+            raise ValueError(f'push_rows: expected {np.dtype(self.STORE_DTYPE).name} rows [n >= 1, {self.width}], got {rows.dtype} {rows.shape}')
+        n = len(rows)
+        drop, count = 0, self.transition_count
+        while count + n > self.max_transition_num:            # evict the oldest trajectories
+            count -= self.trajectory_length[drop]
+            drop += 1
+        if drop:
+            self.transition_count = count
+            del self.trajectory_start[:drop]
+            del self.trajectory_length[:drop]
+        self.memory_buffer[self.ptr:self.ptr + n] = rows
+        self.trajectory_start.append(self.ptr)
+        self._dirty.append((self.ptr, n))
+        self.trajectory_length.append(n)
+        self.transition_count += n
+        self.ptr += n
+        if self.ptr >= self.max_transition_num:
+            self.ptr = 0
+
     # ------------------------------------------------------------------ sampling
     @property
     def available_traj_num(self):

@@ -75,13 +75,17 @@ class TMaze:
         if self._on_map(self.x + mx, self.y + my):
             self.x, self.y = self.x + mx, self.y + my
         done = self.time_step >= self.episode_length
-        if done:
-            rew = float(self.y == self.goal_y) * self.goal_reward
-        else:                                            # behind the schedule x = t - o: -0.0 when it is not, kept as the reference forms it
-            rew = float(self.x < self.time_step - self.oracle_length) * self.penalty
-            if self.x == 0:
-                rew = rew + self.distract_reward
-        return self._obs(), rew, done, {}
+        return self._obs(), self.last_reward(), done, {}
+
+    def last_reward(self) -> float:
+        """The reward of the step that led to the current (x, y, time_step) - a function of these alone."""
+        if self.time_step >= self.episode_length:
+            return float(self.y == self.goal_y) * self.goal_reward
+        # behind the schedule x = t - o: -0.0 when it is not, kept as the reference forms it
+        rew = float(self.x < self.time_step - self.oracle_length) * self.penalty
+        if self.x == 0:
+            rew = rew + self.distract_reward
+        return rew
 
 
 def parse_name(env_name: str):

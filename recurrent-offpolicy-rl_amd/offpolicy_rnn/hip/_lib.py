@@ -37,6 +37,13 @@ class TMazeCfg(ctypes.Structure):                       # resel_tmaze_cfg_t, by 
 
 
 TMAZE_STATE_WORDS = 8
+COLLECT_FIELDS = ('state', 'last_state', 'last_action', 'action', 'next_state', 'reward', 'logp', 'mask', 'start', 'done', 'reward_input',
+                  'timeout')                            # the ring's `tuplenames`, in its order
+
+
+class CollectLayout(ctypes.Structure):                  # resel_collect_layout_t, by value: first column of each field, -1 = absent
+    _fields_ = [(name, ctypes.c_int32) for name in COLLECT_FIELDS]
+
 
 # name -> (restype, argtypes); order and types mirror include/resel_hip.h
 SIGNATURES = {
@@ -133,6 +140,7 @@ SIGNATURES = {
     'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),
     'resel_categorical_step': (c_int, [P, L, P, F, P, L, P, P, L, I, I, S]),
     'resel_tmaze_step': (c_int, [TMazeCfg, I, P, L, P, L, P, I, P, P, P, P, L, P, L, I, P, I, S]),
+    'resel_tmaze_collect_step': (c_int, [TMazeCfg, CollectLayout, I, P, L, P, P, P, P, I, L, I, P, L, I, I, S]),
     'resel_categorical_fwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_categorical_bwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_discrete_value': (c_int, [P, P, I, P, P, P, I, I, I, S]),

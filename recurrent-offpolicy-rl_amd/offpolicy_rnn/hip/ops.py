@@ -2222,6 +2222,44 @@ def tmaze_step(cfg: dict, init: bool, action, goals, n_episodes, env_state, ret_
 
 
 @torch.no_grad()
+def tmaze_collect_step(cfg: dict, name2range: dict, init: bool, action, goal, env_state, ret_acc, traj, max_episode_steps: int, in_block):
+    """One iteration of the training rollout on a discrete T-Maze (or, init: `env_reset()` with the goal sides in `goal`) for the B rows of a
+    graphed policy step, as one launch: include/resel_hip.h `resel_tmaze_collect_step`, host twin `SAC._train_loop` / `_push` / `env_step`.
+    cfg: `TMaze.device_config()`.  name2range: `MemoryArray.name2range`, field -> (first column, end); an empty range is a field the ring does
+    not store, and a stored field must have the width the rollout produces (observations 2, last action 4, scalars 1; no log-probability).
+    action: fp32 [B] view, any stride - the SAMPLED indices (column 1 of the categorical step's output block); goal int32 [B];
+    env_state int32 [B, 8], ret_acc fp64 [B]; traj fp32 [B, T_cap, >= the layout's width] with unit column stride: the episode block;
+    in_block fp32 [B, >= 9] with unit column stride.  Everything is updated in place; no host read, no allocation: capturable."""
+    from ._lib import COLLECT_FIELDS, TMAZE_STATE_WORDS, CollectLayout, TMazeCfg
+    _need_cuda('tmaze_collect_step', action, goal, env_state, ret_acc, traj, in_block)
+    B, A = goal.numel(), 4
+    assert goal.dtype == torch.int32 and goal.dim() == 1 and goal.is_contiguous()
+    assert action.dtype == torch.float32 and action.dim() == 1 and action.numel() == B
+    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, TMAZE_STATE_WORDS)
+    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
+    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
+    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
+    assert traj.dtype == torch.float32 and traj.dim() == 3 and traj.shape[0] == B and traj.shape[1] >= 1 and traj.shape[2] >= 1
+    T_cap, ld_row = traj.shape[1], traj.stride(1) if traj.shape[1] > 1 else max(traj.stride(1), traj.shape[2])
+    assert traj.stride(2) == 1 and ld_row >= traj.shape[2] and (B <= 1 or traj.stride(0) == T_cap * ld_row), 'rows of one episode block'
+    widths = dict(state=2, last_state=2, next_state=2, last_action=A, logp=0)
+    lay = CollectLayout()
+    for name in COLLECT_FIELDS:
+        a, b = name2range[name]
+        if b > a:
+            assert b - a == widths.get(name, 1) and a >= 0, f'tmaze_collect_step: field {name} is {b - a} wide in the ring'
+            assert b <= traj.shape[2], f'tmaze_collect_step: field {name} ends at column {b} of {traj.shape[2]}'
+        setattr(lay, name, a if b > a else -1)
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    c = TMazeCfg(int(cfg['corridor_length']), int(cfg['oracle_length']), int(cfg['episode_length']), float(cfg['goal_reward']),
+                 float(cfg['penalty']), float(cfg['distract_reward']))
+    check(lib().resel_tmaze_collect_step(c, lay, int(bool(init)), _p(action), max(action.stride(0), 1), _p(goal), _p(env_state), _p(ret_acc),
+                                         _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block), max(in_block.stride(0), 2 * 2 + A + 1),
+                                         A, B, _stream()), 'tmaze_collect_step')
+
+
+@torch.no_grad()
 def soft_update_(target_flat, online_flat, tau):
     _need_cuda('soft_update', target_flat, online_flat)
     PARAM_EPOCH[0] += 1

@@ -1,0 +1,159 @@
+"""Training rollouts of a discrete T-Maze on the device: one graph replay per environment step, one copy back per episode.
+
+`SAC._train_loop` pays one H2D, one replay, one D2H, one synchronise, a Python `TMaze.step`, a `Transition` / `mem_push` and the numpy
+bookkeeping of `env_step` for every environment step.  A T-Maze episode has a fixed length, the ring only admits whole trajectories and the
+categorical head samples from the device generator, so none of that has to reach the host before the episode ends: `DeviceCollector` appends
+`ops.tmaze_collect_step` (csrc/env_step.hip) to the policy step's graph as its last node.  The kernel reads the SAMPLED index, steps the
+environment, writes the transition row the ring stores into an episode block and turns the input block into the next step's input.
+
+Per step the host issues `replay_device()` and counts; at an episode's last step it copies the episode block, the return and the
+environment words back with ONE D2H and ONE synchronise, hands the rows to `MemoryArray.push_rows`, logs the episode, draws the next goal
+side from the environment's own stream, starts the episode with one init launch outside the graph and loads a fresh recurrent state - the
+host loop's order of side effects, which fixes every random stream.  Ring, logs, generators and parameters equal the host loop's bit for bit
+(tests/test_device_collect_gpu.py).  `RESEL_DEVICE_COLLECT` switches it (read at `train()`)."""
+import os
+
+import numpy as np
+import torch
+
+from ..env_utils.tmaze import device_steppable
+
+DEVICE_COLLECT_DEFAULT = '1'                               # RESEL_DEVICE_COLLECT when the variable is not set (measured: profiles/r20_device_collect.md)
+SX, SY, SGOAL, SVISITED, ST, SLEN, SSTARTED, SRUNNING = range(8)   # words of env_state (csrc/env_step.hip)
+
+
+def device_collect_enabled() -> bool:
+    return os.environ.get('RESEL_DEVICE_COLLECT', DEVICE_COLLECT_DEFAULT) != '0'
+
+
+class DeviceCollector:
+    """The environment loop of `alg.train()` for a discrete T-Maze, with the environment, the transition rows and the next inputs inside
+    the graphed policy step.  Built behind the warm-up and `env_reset()`: the first episode is the one `env_reset()` began (the
+    environment's current goal, no extra draw).  `collect_step()` is one iteration of the loop up to (not including) the update;
+    `sync_host()` writes the rollout state back into the trainer and the environment object."""
+
+    @staticmethod
+    def refusal(alg):
+        """Why `alg.train()` collects through the host loop (None: it collects on the device)."""
+        if not device_steppable(alg.env):
+            return 'the environment has no device step (a T-Maze with discrete actions has one)'
+        if alg.sample_device.type != 'cuda' or not bool(getattr(alg.policy, 'categorical', False)):
+            return 'the policy is not a categorical one sampling on a CUDA device'
+        if os.environ.get('RESEL_GRAPH_ROLLOUT', '1') == '0':
+            return 'RESEL_GRAPH_ROLLOUT=0'
+        if not device_collect_enabled():
+            return 'RESEL_DEVICE_COLLECT=0'
+        if alg.replay_buffer.memory_buffer is None:
+            return 'the ring has no column layout yet (no warm-up trajectory)'
+        return None
+
+    def __init__(self, alg):
+        from ..hip._lib import TMAZE_STATE_WORDS
+        from ..hip.graph_step import GraphedPolicyStep
+        self.alg, self.env, self.device = alg, alg.env, alg.sample_device
+        self.cfg = self.env.device_config()
+        self.T, self.obs_dim, self.act_dim = int(self.cfg['episode_length']), 2, 4
+        assert alg.obs_dim == self.obs_dim and alg.act_dim == self.act_dim
+        ring = alg.replay_buffer
+        self.name2range, self.width = dict(ring.name2range), int(ring.width)
+        self.step = GraphedPolicyStep(alg.policy, self.device, batch_size=1, after_step=self._env_step)
+        # one device block and one D2H per episode: return fp64 [1] | env_state int32 [1, 8] | episode rows fp32 [1, T, width]
+        head = 8 + 4 * TMAZE_STATE_WORDS
+        self._res_dev = torch.zeros(head + 4 * self.T * self.width, dtype=torch.uint8, device=self.device)
+        self._res_host = torch.zeros(self._res_dev.numel(), dtype=torch.uint8).pin_memory()
+        self._ret = self._res_dev[:8].view(torch.float64)
+        self._env_state = self._res_dev[8:head].view(torch.int32).view(1, TMAZE_STATE_WORDS)       # zeros: the row is stopped until the first init
+        self._traj = self._res_dev[head:].view(torch.float32).view(1, self.T, self.width)
+        res = self._res_host.numpy()
+        self._ret_np, self._state_np = res[:8].view(np.float64), res[8:head].view(np.int32)
+        self._rows_np = res[head:].view(np.float32).reshape(self.T, self.width)
+        self._goal_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._goal_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._counters = []
+        self.t = 0                                         # steps of the running episode that have been replayed
+        self.started = False
+        self.replays = self.episode_syncs = self.init_launches = 0
+
+    # ------------------------------------------------------------------------------------------ graph side
+    def _env_step(self, step):
+        from ..hip import ops
+        ops.tmaze_collect_step(self.cfg, self.name2range, False, step._out_dev[:, 1], self._goal_dev, self._env_state, self._ret, self._traj,
+                               self.alg.max_episode_steps, step._in_dev)
+
+    def _init_episode(self, goal: int):
+        from ..hip import ops
+        self._goal_host[0] = int(goal)
+        self._goal_dev.copy_(self._goal_host, non_blocking=True)
+        ops.tmaze_collect_step(self.cfg, self.name2range, True, self.step._out_dev[:, 1], self._goal_dev, self._env_state, self._ret,
+                               self._traj, self.alg.max_episode_steps, self.step._in_dev)
+        self.init_launches += 1
+        self.t = 0
+
+    def _begin(self):
+        """The first sample behind the warm-up, where the host loop captures its step: capture (the warm-up passes run the hook on a
+        stopped row, so they see the zero input block the host loop's capture sees), then the episode `env_reset()` began."""
+        env = self.env
+        assert env.time_step == 0 and env.x == env.oracle_length and env.y == 0, 'the collector starts behind env_reset()'
+        self.step.load_hidden(self.alg.sample_hidden)
+        self.step.capture(self.obs_dim, self.act_dim)
+        self._counters = self.step._counters()
+        self._init_episode(env.goal_y)
+        self.started = True
+
+    # ------------------------------------------------------------------------------------------ the loop body
+    @torch.no_grad()
+    def collect_step(self):
+        if not self.started:
+            self._begin()
+        for ip in self._counters:                          # what `GraphedPolicyStep.__call__` raises at the step that would overrun
+            if ip.seqlen_offset >= ip.max_seqlen:
+                raise RuntimeError(f'cgpt rollout: KV cache is full ({ip.seqlen_offset} tokens, max_seqlen {ip.max_seqlen})')
+        self.step.replay_device()
+        self.replays += 1
+        for ip in self._counters:
+            ip.seqlen_offset += 1
+        self.t += 1
+        if self.t >= self.T:
+            self._finish_episode()
+
+    def _finish_episode(self):
+        alg = self.alg
+        self._res_host.copy_(self._res_dev, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.episode_syncs += 1
+        length = int(self._state_np[SLEN])
+        assert length == self.T and not self._state_np[SRUNNING], (length, self.T, self._state_np.tolist())
+        alg.replay_buffer.push_rows(self._rows_np[:length])
+        alg.logger.add_tabular_data(tb_prefix='Train', EpRet=float(self._ret_np[0]), EpLength=length)
+        self.env.goal_y = self.env.draw_goal()             # `env_reset()`: the draw of `env.reset()`, then the fresh recurrent state
+        self._init_episode(self.env.goal_y)
+        alg.sample_hidden = alg._init_sample_hidden()
+        self.step.load_hidden(alg.sample_hidden)
+
+    # ------------------------------------------------------------------------------------------ back to the host loop's state
+    @torch.no_grad()
+    def sync_host(self):
+        """On return from `train()`: the trainer's rollout mirrors, the environment object's fields, the B = 1 step's recurrent state
+        and the ring's pending transitions (the open episode) hold what the host loop would have left there."""
+        if not self.started:
+            return
+        alg, env, o, a = self.alg, self.env, self.obs_dim, self.act_dim
+        row = self.step._in_dev[0].cpu().numpy()            # (synchronises)
+        st = self._env_state[0].cpu().numpy()
+        env.x, env.y, env.goal_y, env.oracle_visited, env.time_step = int(st[SX]), int(st[SY]), int(st[SGOAL]), bool(st[SVISITED]), int(st[ST])
+        alg.state_np = row[:o].copy().reshape(1, -1)
+        if self.t == 0:                                    # behind `env_reset()`
+            alg.last_state_np, alg.last_action_np, alg.reward_np = np.zeros((1, o)), np.zeros((1, a)), np.zeros((1, 1))
+        else:
+            alg.last_state_np = row[o:2 * o].copy().reshape(1, -1)
+            alg.last_action_np = row[2 * o:2 * o + a].astype(np.float64).reshape(1, -1)
+            alg.reward_np = np.array([[env.last_reward()]])  # the double the float32 in the block was rounded from
+            ring = alg.replay_buffer                       # the open episode's transitions wait in the ring's `memory`, as `mem_push` leaves them
+            rows = self._traj[0, :self.t].cpu().numpy()
+            ring.memory = [ring.array_to_transition(rows[k:k + 1].copy()) for k in range(self.t)]
+        if alg.graph_step is not None:                     # the recurrent state mid-episode lives in the step object, as in the host loop
+            alg.graph_step.load_hidden(self.step._hidden)
+            for dst, src in zip(alg.graph_step._counters(), self.step._counters()):
+                dst.key_value_memory_dict = {k: v.clone() for k, v in src.key_value_memory_dict.items()}
+                dst.seqlen_offset = src.seqlen_offset
+                dst.device_offset.fill_(src.seqlen_offset)
