@@ -742,6 +742,24 @@ size_t resel_atb_workspace_bytes(int64_t K, int Wd, int Nd);
 int resel_atb(const float* wide, int64_t ldw, int Wd, const float* narrow, int64_t ldn, int Nd, float* out, int transposed,
               void* workspace, int64_t K, resel_stream_t stream);
 
+/* Products with one side at most 48 wide, bound by one pass over their wide side (csrc/skinny_gemm.hip; fp32 MFMA, no operand split).
+ *
+ * resel_narrow_k: C[M, N] (row stride ldc) = act(A[M, :K] W[N, K]^T + bias[N]).  K <= 48, K % 4 == 0, N % 4 == 0; A is a column block
+ * of a wider row-major matrix (row stride lda, 8-byte aligned, lda even); W has row stride ldw (8-byte aligned, even); C is 16-byte
+ * aligned with ldc % 4 == 0.  act: 0 none, 1 ELU, 3 softplus (the codes of resel_gemm_f32x).  bias may be NULL.  amax_out: magnitude
+ * handle that receives max |C| under amax_epoch, or NULL.  One launch, no workspace.
+ *
+ * resel_narrow_n_pair: one pass over G[M, Wd] (row stride ldg % 4 == 0, 16-byte aligned, Wd % 4 == 0, Wd <= 512) gives
+ *   dX[M, Nn] (row stride lddx) = G W[Wd, Nn] (row stride ldw)      and      dW[Wd, Nn] (dense) = G^T X[M, Nn] (row stride ldx),
+ * Nn <= 48.  Either output may be NULL (then its second operand is not read).  dX is summed over Wd inside the workgroup, dW over M
+ * as resel_atb does (partial slabs in `workspace`, resel_narrow_n_pair_workspace_bytes(M, Wd, Nn), added in a fixed order): both are
+ * bitwise reproducible.  Shapes outside these limits return RESEL_EINVAL; callers keep the GEMM route for them. */
+int resel_narrow_k(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int64_t M, int N,
+                   int K, int act, void* amax_out, unsigned amax_epoch, resel_stream_t stream);
+size_t resel_narrow_n_pair_workspace_bytes(int64_t M, int Wd, int Nn);
+int resel_narrow_n_pair(const float* G, int64_t ldg, int Wd, const float* W, int64_t ldw, const float* X, int64_t ldx, int Nn, float* dX,
+                        int64_t lddx, float* dW, void* workspace, int64_t M, resel_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

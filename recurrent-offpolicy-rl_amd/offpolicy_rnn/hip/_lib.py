@@ -135,6 +135,9 @@ SIGNATURES = {
     'resel_selective_state_update': (c_int, [P, L, P, L, P, P, L, P, P, P, P, P, L, P, I, I, I, I, S]),
     'resel_atb_workspace_bytes': (c_size_t, [L, I, I]),
     'resel_atb': (c_int, [P, L, I, P, L, I, P, I, P, L, S]),
+    'resel_narrow_k': (c_int, [P, L, P, L, P, P, L, L, I, I, I, P, E, S]),
+    'resel_narrow_n_pair_workspace_bytes': (c_size_t, [L, I, I]),
+    'resel_narrow_n_pair': (c_int, [P, L, I, P, L, P, L, I, P, L, P, P, L, S]),
     'resel_attn_decode': (c_int, [P, L, P, P, I, P, P, F, I, I, I, I, S]),
     'resel_attn_decode_rows': (c_int, [P, L, P, P, P, P, F, I, I, I, I, S]),
     'resel_step_state_reset': (c_int, [P, I, ResetSegs, I, ResetCounters, I, S]),

@@ -138,7 +138,9 @@ class SelectiveScanFn(torch.autograd.Function):
     `SelectiveScanFn` (mamba_ssm/ops/selective_scan_interface_new.py:19-84)."""
 
     @staticmethod
-    def forward(ctx, u, delta, A, Bm, Cm, D, z, delta_bias, start, delta_softplus, return_last_state):
+    def forward(ctx, u, delta, A, Bm, Cm, D, z, delta_bias, start, delta_softplus, return_last_state, grad_mode=True):
+        """grad_mode: torch.is_grad_enabled() of the CALLER (inside forward it is always off, and `needs_input_grad` still names every
+        parameter that requires grad under no_grad): without it no checkpoints are written."""
         _need_cuda('selective_scan', u, delta, A, Bm, Cm)
         u, delta, Bm, Cm = _tok_major(u), _tok_major(delta), _tok_major(Bm), _tok_major(Cm)
         z = None if z is None else _tok_major(z)
@@ -149,7 +151,7 @@ class SelectiveScanFn(torch.autograd.Function):
         N = A.shape[1]
         start = _flags(start, Bsz, L)
         out = torch.empty(Bsz, L, Di, dtype=torch.float32, device=u.device)
-        need_grad = any(ctx.needs_input_grad)
+        need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
         ck = None
         if need_grad:
             ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), u.device)
@@ -178,13 +180,13 @@ class SelectiveScanFn(torch.autograd.Function):
         dD = torch.empty(Di, dtype=torch.float32, device=dev) if D is not None else None
         dbias = torch.empty(Di, dtype=torch.float32, device=dev) if delta_bias is not None else None
         _sscan_bwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, dout, ck, du, ddelta, dz, dB, dC, dA, dD, dbias, int(ctx.softplus))
-        return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None, None
+        return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None, None, None
 
 
 def selective_scan_tm(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, start=None, delta_softplus=True,
                       return_last_state=False):
     """Token-major entry: u, delta, z [B, L, Di]; Bm, Cm [B, L, N]; start [B, L] or [B, L, 1]."""
-    return SelectiveScanFn.apply(u, delta, A, Bm, Cm, D, z, delta_bias, start, delta_softplus, return_last_state)
+    return SelectiveScanFn.apply(u, delta, A, Bm, Cm, D, z, delta_bias, start, delta_softplus, return_last_state, torch.is_grad_enabled())
 
 
 def selective_scan_fn(u, delta, A, B, C, start, D=None, z=None, delta_bias=None, delta_softplus=False,
@@ -211,7 +213,8 @@ class MambaInnerFn(torch.autograd.Function):
     add passes (8 x 273 MB per update at config 2) disappear.  GEMMs: `mm_nt` / `mm_nn` / `wgrad` (hand-written, every pass)."""
 
     @staticmethod
-    def forward(ctx, x, in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask, start):
+    def forward(ctx, x, in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask, start, grad_mode=True):
+        """grad_mode: the caller's torch.is_grad_enabled() (see `SelectiveScanFn.forward`): a no_grad pass writes no scan checkpoints."""
         _need_cuda('mamba_inner', x, in_w, conv_w, xproj_w, dt_w, A_log, out_w)
         Bsz, L, Dm = x.shape
         Di, N = A_log.shape
@@ -230,7 +233,11 @@ class MambaInnerFn(torch.autograd.Function):
         tag_amax(xc, h_xc)
         x_dbl = mm_nt(xc, xproj_w)                                         # [M, R + 2N] = (delta_r | B | C)
         # delta = softplus(dt_proj(.) + bias) leaves the GEMM epilogue: the scan kernels spend no vector issue on it
-        if R < 32 <= R + 2 * N and os.environ.get('RESEL_DT_PAD', '1') != '0' and gemm_split() == 2:
+        if narrow_on() and narrow_k_ok(x_dbl[:, :R], dt_w):
+            # K = dt_rank = 16 against 137 MB of output: the streaming kernel with the weight resident in registers (no padded weight, no
+            # operand magnitudes; nothing multiplies delta again, so none is published for it either)
+            dt = narrow_k(x_dbl[:, :R], dt_w.detach(), dt_b, GEMM_SOFTPLUS)
+        elif R < 32 <= R + 2 * N and os.environ.get('RESEL_DT_PAD', '1') != '0' and gemm_split() == 2:
             # dt_proj has K = dt_rank = 16: one PARTIAL K step, which only the fp32-MFMA first edition takes (58 us for a product whose floor
             # is its 137 MB of output: 28 us).  Read 32 columns of x_dbl instead - the 16 behind delta_r are B's, finite - against the weight
             # padded with 16 zero columns (one launch): a whole K step, so the producer / consumer edition with its full-line stores runs it.
@@ -240,7 +247,7 @@ class MambaInnerFn(torch.autograd.Function):
             dt = gemm_f32(x_dbl[:, :R], dt_w, True, True, dt_b, GEMM_SOFTPLUS)
         # delta_softplus code 6 = 4 (the kernels form A = -exp(A_log) themselves) + 2 (delta arrives finished: no delta_bias)
         A = A_log.float().contiguous()
-        need_grad = any(ctx.needs_input_grad)
+        need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
         ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), x.device) if need_grad else None
         y = torch.empty(M, Di, dtype=torch.float32, device=x.device)
         h_y, p_y, e_y = _slot_args(track, x.device)
@@ -278,9 +285,13 @@ class MambaInnerFn(torch.autograd.Function):
                    dxc, ddt, dxz[:, Di:], dx_dbl[:, R:R + N], dx_dbl[:, R + N:], dA, dD, ddt_b, 6, p_dxz, p_ddt, e_b)
         tag_amax(ddt, h_ddt)
         # [Di, R] with a 66 752-long reduction: hand-written MFMA kernel (the library reaches 7 TFLOP/s on this shape)
-        d_dt_w = atb(ddt, x_dbl[:, :R]) if R <= 32 and Di % 4 == 0 and ddt.stride(1) == 1 and ddt.stride(0) % 4 == 0 \
-            else gemm_f32(ddt, x_dbl[:, :R], False, False)
-        mm_nn(ddt, dt_w, out=dx_dbl[:, :R])                                  # straight into its column block of dx_dbl
+        if narrow_on() and narrow_n_pair_ok(ddt, dt_w, x_dbl[:, :R]):
+            # ONE pass over ddt (137 MB) for both products it feeds; dx_dbl[:, :R] is written in place
+            _, d_dt_w = narrow_n_pair(ddt, dt_w, x_dbl[:, :R], dx_out=dx_dbl[:, :R])
+        else:
+            d_dt_w = atb(ddt, x_dbl[:, :R]) if R <= 32 and Di % 4 == 0 and ddt.stride(1) == 1 and ddt.stride(0) % 4 == 0 \
+                else gemm_f32(ddt, x_dbl[:, :R], False, False)
+            mm_nn(ddt, dt_w, out=dx_dbl[:, :R])                              # straight into its column block of dx_dbl
         d_xproj_w = wgrad(dx_dbl, xc, amax_x=h_xc)
         # the conv output's gradient = the scan's du (in dxc) + the x_proj input gradient: handed to the conv backward as TWO tensors
         # (summed on load) - the accumulating GEMM epilogue cost 150-214 us per call against 67 for the plain product
@@ -291,12 +302,13 @@ class MambaInnerFn(torch.autograd.Function):
         tag_amax(dxz, h_dxz)
         d_in_w = wgrad(dxz, x2, amax_x=ax)
         dx = mm_nn(dxz, in_w).view(Bsz, L, Dm) if ctx.needs_input_grad[0] else None
-        return (dx, d_in_w, dcw.reshape(cw_shape), dcb, d_xproj_w, d_dt_w, ddt_b, dA, dD, d_out_w, None, None)      # dA: already dL/dA_log
+        return (dx, d_in_w, dcw.reshape(cw_shape), dcb, d_xproj_w, d_dt_w, ddt_b, dA, dD, d_out_w, None, None, None)      # dA: already dL/dA_log
 
 
 def mamba_inner_fn(x, in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask=None, start=None):
     """x [B, L, D] -> [B, L, D]: the whole Mamba mixer of the training path (no biases on in/out projections)."""
-    return MambaInnerFn.apply(x.float().contiguous(), in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask, start)
+    return MambaInnerFn.apply(x.float().contiguous(), in_w, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, mask, start,
+                              torch.is_grad_enabled())
 
 
 # ---------------------------------------------------------------------------------------------- causal conv1d
@@ -1577,6 +1589,74 @@ def atb(wide, narrow, transposed=False):
     check(lib().resel_atb(_p(wide), wide.stride(0), Wd, _p(narrow), narrow.stride(0), Nd, _p(out), int(bool(transposed)), _p(ws), K,
                           _stream()), 'atb')
     return out
+
+
+# ---- products with one side at most 48 wide on the streaming fp32-MFMA kernels of csrc/skinny_gemm.hip -------------------------------
+def narrow_on():
+    """RESEL_NARROW (default on; read per call so that one process can run both routes): 0 = the GEMM / atb launches of before."""
+    return os.environ.get('RESEL_NARROW', '1') != '0'
+
+
+def _narrow_block(t, mult, align):
+    """t [M, C]: unit column stride, row stride a multiple of `mult` floats, base aligned to `align` bytes."""
+    return t.dim() == 2 and t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % mult == 0 \
+        and t.stride(0) >= t.shape[1] and t.data_ptr() % align == 0
+
+
+def narrow_k_ok(a, w, out=None):
+    """Shapes and layouts `resel_narrow_k` takes (include/resel_hip.h); everything else stays on `gemm_f32`."""
+    K, N = a.shape[1], w.shape[0]
+    return 4 <= K <= 48 and K % 4 == 0 and N % 4 == 0 and a.shape[0] > 0 and w.shape[1] == K and _narrow_block(a, 2, 8) \
+        and _narrow_block(w, 2, 8) and (out is None or _narrow_block(out, 4, 16))
+
+
+@torch.no_grad()
+def narrow_k(a, w, bias=None, act=None, out=None, amax_out=None):
+    """act(a [M, K <= 48] w[N, K]^T + bias) -> [M, N]; a may be a column block of a wider matrix, out (optional) one too.  act: None, 'elu'
+    or GEMM_SOFTPLUS.  amax_out: (handle, pointer, epoch) as `_slot_args` returns it - the output is tagged with the handle."""
+    _need_cuda('narrow_k', a, w)
+    assert narrow_k_ok(a, w, out) and act != GEMM_ACCUMULATE
+    M, K = a.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    assert out.shape == (M, N)
+    if bias is not None:
+        bias = bias if (bias.dtype == torch.float32 and bias.is_contiguous()) else bias.float().contiguous()
+        assert bias.numel() == N
+    slot, slot_p, epoch = amax_out if amax_out is not None else (None, None, 0)
+    check(lib().resel_narrow_k(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, GEMM_EPILOGUES[act],
+                               slot_p, epoch, _stream()), 'narrow_k')
+    return tag_amax(out, slot)
+
+
+def narrow_n_pair_ok(g, w, x):
+    """Shapes and layouts `resel_narrow_n_pair` takes: g [M, Wd <= 512], w [Wd, Nn <= 48] or None, x [M, Nn] or None."""
+    M, Wd = g.shape
+    ok = M > 0 and Wd % 4 == 0 and Wd <= 512 and _narrow_block(g, 4, 16)
+    for t, rows in ((w, Wd), (x, M)):
+        ok = ok and (t is None or (_narrow_block(t, 1, 4) and t.shape[0] == rows and 0 < t.shape[1] <= 48))
+    return ok and (w is None or x is None or w.shape[1] == x.shape[1])
+
+
+@torch.no_grad()
+def narrow_n_pair(g, w=None, x=None, dx_out=None):
+    """One pass over g [M, Wd]: (g w [M, Nn] if w is given - written to dx_out, e.g. a column block of a wider buffer, when that is
+    given - , g^T x [Wd, Nn] if x is given); the output whose operand is missing is None."""
+    _need_cuda('narrow_n_pair', g, w, x)
+    assert (w is not None or x is not None) and narrow_n_pair_ok(g, w, x)
+    M, Wd = g.shape
+    Nn = (w if w is not None else x).shape[1]
+    dx = dw = ws = None
+    if w is not None:
+        dx = dx_out if dx_out is not None else torch.empty(M, Nn, dtype=torch.float32, device=g.device)
+        assert dx.shape == (M, Nn) and _narrow_block(dx, 1, 4)
+    if x is not None:
+        dw = torch.empty(Wd, Nn, dtype=torch.float32, device=g.device)
+        ws = _ws(lib().resel_narrow_n_pair_workspace_bytes(M, Wd, Nn), g.device)
+    check(lib().resel_narrow_n_pair(_p(g), g.stride(0), Wd, _p(w), 0 if w is None else w.stride(0), _p(x), 0 if x is None else x.stride(0), Nn,
+                                    _p(dx), 0 if dx is None else dx.stride(0), _p(dw), _p(ws), M, _stream()), 'narrow_n_pair')
+    return dx, dw
 
 
 # ---------------------------------------------------------------------------------------------- bf16 projections (cgpt)

@@ -1,5 +1,6 @@
 """Census of the hand-written GEMM calls of one update: shape, operand layouts, call site (file:line of the caller of ops.gemm_f32 and
-of its caller), launches and device time (one HIP event pair per call).  Tells which operands are worth a producer-side magnitude."""
+of its caller), launches and device time (one HIP event pair per call).  Tells which operands are worth a producer-side magnitude.
+The streaming products (`atb`, `narrow_k`, `narrow_n_pair`) are listed too; `RESEL_NARROW=0` shows the GEMM route of the same products."""
 import sys, os, traceback
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'recurrent-offpolicy-rl_amd')]
@@ -32,6 +33,29 @@ def hooked(A, B, a_kcontig=True, b_kcontig=True, bias=None, act=None, out=None, 
 
 
 ops.gemm_f32 = hooked
+
+
+def hook_streaming(name, dims):
+    """The streaming products of csrc/skinny_gemm.hip (`atb`, `narrow_k`, `narrow_n_pair`) in the same table: mode '-', their name in the
+    activation column; dims(*args) -> (M, N, K) of the product (for the pair: rows of G, narrow width, width of G)."""
+    inner = getattr(ops, name)
+
+    def timed(*a, **kw):
+        st = traceback.extract_stack(limit=4)
+        site = ' <- '.join(f'{os.path.basename(f.filename)}:{f.lineno}' for f in reversed(st[:-1]))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = inner(*a, **kw)
+        e1.record()
+        M, N, K = dims(*a)
+        rec.append(((1, M, N, K, 1, 1, name, '-', site), e0, e1))
+        return r
+    setattr(ops, name, timed)
+
+
+hook_streaming('atb', lambda wide, narrow, *_: (wide.shape[1], narrow.shape[1], wide.shape[0]))
+hook_streaming('narrow_k', lambda a, w, *_: (a.shape[0], w.shape[0], a.shape[1]))
+hook_streaming('narrow_n_pair', lambda g, w=None, x=None, *_: (g.shape[0], (w if w is not None else x).shape[1], g.shape[1]))
 real_amax = ops.amax
 pre = []
 
