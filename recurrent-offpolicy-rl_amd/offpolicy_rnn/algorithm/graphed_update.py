@@ -53,6 +53,7 @@ read-back.  Here: `GraphedUpdate`, the driver - the static device inputs, the ho
 
 Refused at construction (use the eager `train_one_batch`): the three-phase Q-guard exchange (RESEL_DP_GUARD=allreduce).  utd < 1 is an
 error of the flag set (ValueError), not a refusal."""
+import gc
 import os
 
 import numpy as np
@@ -257,12 +258,18 @@ class GraphedUpdate:
     def _record(self):
         """Record one pass as a list of (graph, exchange) segments; one segment unless the trainer cuts (data parallel)."""
         torch.cuda.synchronize(self.device)
+        # No cyclic garbage collection while the stream captures: a dead CUDAGraph that only the collector can free (a dropped trainer or
+        # GraphedUpdate sits in reference cycles) synchronises the device in its destructor on ROCm, which a capturing stream refuses - the
+        # exception leaves a destructor and the process aborts.  Collect such garbage now and keep the collector off until the capture ends.
+        gc.collect()
         torch.cuda.empty_cache()
         if self._capture_stream is None:
             self._capture_stream = torch.cuda.Stream(device=self.device)
         side = self._capture_stream
         side.wait_stream(torch.cuda.current_stream(self.device))
         rec = self._rec = dict(segs=[], g=torch.cuda.CUDAGraph())
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             with torch.cuda.stream(side):
                 rec['g'].capture_begin(pool=self._pool, capture_error_mode=self._capture_mode)
@@ -273,6 +280,8 @@ class GraphedUpdate:
                 rec['segs'].append((rec['g'], None))
         finally:
             self._rec = None
+            if gc_was_on:
+                gc.enable()
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         return dict(segs=rec['segs'], log_keys=self._log_keys, log_items=self._log_items)

@@ -111,11 +111,12 @@ class SAC:
 
     def allow_nest_stack_trajs(self):
         """Rows may pack several trajectories unless a layer cannot honour resets (gru ignores rnn_start)."""
-        for net in (self.values[0].uni_network, self.values[0].embedding_network, self.policy.uni_network, self.policy.embedding_network):
-            for lid in net.layer_type:
-                if 'transformer' in lid or 'gru' in lid:
-                    return False
-        return True
+        return all(kind.honours_start for kind, _ in self._sequence_layers())
+
+    def _sequence_layers(self, models=None):
+        """[(kind, module)] of the sequence layers (models/layer_kinds.py) of `models`' networks; default: the live critic and the policy."""
+        return [kl for model in models or (self.values[0], self.policy) for net in (model.uni_network, model.embedding_network)
+                for kl in net.sequence_layers()]
 
     def _seed(self, seed: int):
         np.random.seed(seed)

@@ -99,9 +99,7 @@ class SACFullLengthRNNEnsembleQ(SAC):
         self.seq_buckets = False
         self._subset_rng = None                        # REDQ subset stream: None = numpy's global stream (see _subset_stream)
         self._pinned = PinnedRing(torch.float32)       # staging blocks of the host-built batch (one event per block)
-        self._needs_seq_table = any(lid.startswith('cgpt') for net in (self.values[0].uni_network, self.values[0].embedding_network,
-                                                                       self.policy.uni_network, self.policy.embedding_network)
-                                    for lid in net.layer_type)
+        self._needs_seq_table = any(kind.packs_sequences for kind, _ in self._sequence_layers())
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._planar_idx = {}                          # (flag names, device) -> their column indices on the device (_batch_views)
         self._subset_tables, self._subset_cache = {}, {}     # device copies of critic-subset index vectors (_subset_on_device)
@@ -113,34 +111,23 @@ class SACFullLengthRNNEnsembleQ(SAC):
         # another.  Both forms are launch sequences on the current stream.  Not with a shared policy pass: that pass records an autograd
         # graph inside the target computation.
         self.gru_batch = (self.device.type == 'cuda' and os.environ.get('RESEL_GRU_BATCH', '1') != '0' and not self.discrete_env
-                          and any(lid == 'gru' for lid in self.values[0].embedding_network.layer_type) and not self.share_policy_pass)
+                          and any(kind.deferred for kind, _ in self.values[0].embedding_network.sequence_layers())
+                          and not self.share_policy_pass)
 
     step = property(lambda self: self.train_one_batch)          # north_star's "algorithm.step()" alias
     device_replay = True        # keep a device mirror of the replay ring and assemble sampled batches on the GPU (CUDA only)
     defer_log = False           # True: the log's device scalars stay in flight until first read (DeferredLog); False: floats on return, as the reference
 
     def _get_skip_len(self):
-        skip = 0
-        for net in (self.values[0].uni_network, self.values[0].embedding_network, self.policy.uni_network, self.policy.embedding_network):
-            for i, lid in enumerate(net.layer_type):
-                if 'smamba' in lid:
-                    skip = max(net.layer_list[i].d_conv, skip)
-                elif 'mamba' in lid:
-                    skip = max(net.layer_list[i].mixer.d_conv, skip)
-                elif 'conv1d' in lid:
-                    skip = max(net.layer_list[i].d_conv, skip)
-        return skip + 1
-
-    # state cleared / masked at the first token of a trajectory; cgpt attends inside per-trajectory segments whose table
-    # is shifted with the tokens (`target_attention_mask`, reference :358-366)
-    _SHIFT_INVARIANT_IDS = ('smamba', 'mamba', 'gilr', 'lru', 'conv1d', 'cgpt')
+        return max((kind.context_len(layer) for kind, layer in self._sequence_layers()), default=0) + 1
 
     def _policy_pass_shareable(self) -> bool:
         """The target pass evaluates the policy on (s', s, a): the SAME token sequence as the actor pass on (s, s_prev,
         a_prev), one slot earlier (that is what the pre-step slot and the `total_*` flags of the reference build,
         sac_full_length_rnn_ensembleQ.py:338-378), with the SAME parameters (the actor is updated after both).  When every
-        layer's output at a token depends only on the tokens of its own trajectory - pointwise layers and recurrent layers
-        that reset / mask at the trajectory start - the actor pass is the target pass shifted by one slot, so ONE policy
+        layer's output at a token depends only on the tokens of its own trajectory - pointwise layers and sequence layers
+        that reset / mask at the trajectory start (`honours_start`; cgpt attends inside per-trajectory segments whose table is
+        shifted with the tokens, `target_attention_mask`, reference :358-366) - the actor pass is the target pass shifted by one slot, so ONE policy
         forward (with a graph) serves both and the second is skipped.  Not for `gru` (no reset: the leading padding slots
         differ between the two passes), layers with active dropout (`cgpt_*_p0.1`), the TD3 trainer that smooths a frozen target policy, discrete heads,
         RESEL_SHARE_POLICY_PASS=0."""
@@ -152,10 +139,8 @@ class SACFullLengthRNNEnsembleQ(SAC):
             return False
         if self.base_algorithm not in ('sac', 'td3'):
             return False
-        for net in (self.policy.embedding_network, self.policy.uni_network):
-            for lid in net.layer_type:
-                if not (lid == 'fc' or lid.startswith('efc') or lid.startswith(self._SHIFT_INVARIANT_IDS)):
-                    return False
+        if not all(kind.honours_start for kind, _ in self._sequence_layers((self.policy,))):
+            return False
         return not any(isinstance(m, torch.nn.Dropout) and m.p > 0 for mod in self.policy.contextual_modules.values() for m in mod.modules())
 
     # ------------------------------------------------------------------------------------------ batch

@@ -8,12 +8,9 @@ from typing import List, Tuple, Union
 
 import torch
 
+from .layer_kinds import kind_of
+
 State = Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]
-
-
-def _is_rnn_type(t: str) -> bool:
-    base = ('gru', 'lru', 'gilr', 'cgru', 'gilr_lstm', 'mamba', 'conv1d', 'smamba', 'transformer')
-    return (t in base or (t.startswith('e') and t[1:].split('-')[0] in base) or t.startswith(('conv1d', 'econv1d', 'mamba', 'smamba', 'transformer')))
 
 
 class RNNHidden:
@@ -85,7 +82,7 @@ class RNNHidden:
     def init_hidden_by_type(self, rnn_type: str, batch_size: int, unit_num: int, device) -> State:
         if rnn_type == 'lstm':
             return (torch.zeros((1, batch_size, unit_num), device=device), torch.zeros((1, batch_size, unit_num), device=device))
-        if _is_rnn_type(rnn_type):
+        if kind_of(rnn_type) is not None:          # raises for a sequence-layer id outside this build
             return torch.zeros((1, batch_size, unit_num), device=device)
         raise NotImplementedError(f'rnn type: {rnn_type} has not been implemented!!')
 
@@ -93,7 +90,7 @@ class RNNHidden:
     def init_random_hidden_by_type(self, rnn_type: str, batch_size: int, unit_num: int, device) -> State:
         if rnn_type == 'lstm':
             return (torch.rand((1, batch_size, unit_num), device=device) * 2 - 1, torch.rand((1, batch_size, unit_num), device=device) * 2 - 1)
-        if _is_rnn_type(rnn_type):
+        if kind_of(rnn_type) is not None:          # raises for a sequence-layer id outside this build
             return torch.rand((1, batch_size, unit_num), device=device) * 2 - 1
         raise NotImplementedError(f'rnn type: {rnn_type} has not been implemented!!')
 

@@ -1,11 +1,10 @@
 """RNNBase: a stack of layers selected by layer-id strings, with a per-layer (norm, activation) tail
 (reference offpolicy_rnn/models/rnn_base.py:31-532).
 
-Layer-id grammar kept from the reference (:101-247): `fc`, `efc-<E>`, `gru`, `gilr`, `lru`, `gilr_lstm`,
-`smamba[_s<N>][_c<K>][_b<blocks>][_n<ln|...>][_ff]`, `mamba[_s<N>][_c<K>][_noff]`, `conv1d[_<K>]`,
-`cgpt[_h<H>][_l<L>][_p<drop>][_ml<M>][_rms]`.  Ids of reference layers that are outside this build (`lstm`, `e<rnn>-<E>`,
-`econv1d*`, `gpt*`, `transformer*`, `cgru`) are recognised and rejected with an explicit message.  Module / parameter naming (`layer_list.<i>.…`, `activation_list.<i>.0.…`) matches the
-reference so that its per-module checkpoints load."""
+Layer-id grammar kept from the reference (:101-247): the dense ids `fc` and `efc-<E>` are handled here; what a sequence-layer id means -
+how the layer is built, called and what the trainers may assume about it - is one record of `layer_kinds.py`, resolved per layer at
+construction (`layer_kind`).  Module / parameter naming (`layer_list.<i>.…`, `activation_list.<i>.0.…`) matches the reference so that
+its per-module checkpoints load."""
 import copy
 import os
 from typing import List, Optional, Tuple, Union
@@ -15,71 +14,18 @@ import torch
 from ..hip import ops
 from .RNNHidden import RNNHidden
 from .ensemble_linear_model import EnsembleLinear, critic_mlp, critic_mlp_fusable, ensemble_head, head_fusable
-from .flash_attention.TransformerFlashAttention import InferenceParams, TransformerDecoder
+from .flash_attention.TransformerFlashAttention import TransformerDecoder
 from .conv1d.conv1d import Conv1d
 from .gilr.gilr import GILRLayer
 from .gilr_lstm.gilr_lstm import GILRLSTMLayer
-from .gru import GRU
 from .s6.mamba import MambaResidualBlock
 from .lru.lru import LRULayer
 from .smamba.mamba import BlockList as MambaBlockList
+from .layer_kinds import is_rnn_layer, kind_of, parse_cgpt_id, parse_mamba_id, parse_smamba_id  # noqa: F401  (the parsers: part of this module's surface)
 from .linear import Linear
 
 ACTIVATIONS = {'tanh': torch.nn.Tanh, 'relu': torch.nn.ReLU, 'sigmoid': torch.nn.Sigmoid, 'leaky_relu': torch.nn.LeakyReLU,
                'linear': torch.nn.Identity, 'elu': torch.nn.ELU, 'gelu': torch.nn.GELU}
-_UNSUPPORTED_PREFIXES = ('lstm', 'econv1d', 'gpt', 'transformer', 'cgru', 'elru', 'egilr')
-
-
-def parse_smamba_id(layer_id: str) -> dict:
-    cfg = dict(d_conv=4, d_state=16, block_num=2, rms_norm=True, use_ff=False)
-    for tok in layer_id.split('_')[1:]:
-        if tok.startswith('s'):
-            cfg['d_state'] = int(tok[1:])
-        elif tok.startswith('c'):
-            cfg['d_conv'] = int(tok[1:])
-        elif tok.startswith('b'):
-            cfg['block_num'] = int(tok[1:])
-        elif tok.startswith('n'):
-            cfg['rms_norm'] = tok[1:] != 'ln'
-        elif tok.startswith('f'):
-            cfg['use_ff'] = cfg['use_ff'] or tok[1:] == 'f'
-        else:
-            raise ValueError(f'Pattern {tok} has not been implemented!')
-    return cfg
-
-
-def parse_mamba_id(layer_id: str) -> dict:
-    """`mamba[_s<N>][_c<K>][_noff]` (reference rnn_base.py:118-135)."""
-    cfg = dict(d_conv=4, d_state=16, use_ff=True)
-    for tok in layer_id.split('_')[1:]:
-        if tok.startswith('s'):
-            cfg['d_state'] = int(tok[1:])
-        elif tok.startswith('c'):
-            cfg['d_conv'] = int(tok[1:])
-        elif tok.startswith('no'):
-            if tok[2:] == 'ff':
-                cfg['use_ff'] = False
-        else:
-            raise ValueError(f'Pattern {tok} has not been implemented!')
-    return cfg
-
-
-def parse_cgpt_id(layer_id: str) -> dict:
-    cfg = dict(nhead=8, nlayer=4, pdrop=0.1, maxlength=1024, ln=True)
-    for tok in layer_id.split('_')[1:]:
-        if tok.startswith('h'):
-            cfg['nhead'] = int(tok[1:])
-        elif tok.startswith('l'):
-            cfg['nlayer'] = int(tok[1:])
-        elif tok.startswith('p'):
-            cfg['pdrop'] = float(tok[1:])
-        elif tok.startswith('ml'):
-            cfg['maxlength'] = int(tok[2:])
-        elif tok.startswith('rms'):
-            cfg['ln'] = False
-        else:
-            raise ValueError(f'Pattern {tok} has not been implemented!')
-    return cfg
 
 
 # Set by the trainers around an update (`training_pass()`): nobody reads the per-layer output sequences (`full_rnn_memory`) of a training
@@ -105,10 +51,6 @@ class training_pass:
         return False
 
 
-def is_rnn_layer(layer_id: str) -> bool:
-    return layer_id != 'fc' and not layer_id.startswith('efc')
-
-
 class RNNBase(torch.nn.Module):
     def __init__(self, input_size: int, output_size: int, hidden_size_list: List[int], activation: List[str],
                  layer_type: List[str]):
@@ -121,6 +63,7 @@ class RNNBase(torch.nn.Module):
         self.activation_type = copy.deepcopy(activation)
         self.layer_list = torch.nn.ModuleList()
         self.activation_list = torch.nn.ModuleList()
+        self.layer_kind = []                    # per layer: its layer_kinds record, None for a dense layer (unknown ids raise here)
         self.rnn_hidden_state_input_size, self.rnn_layer_type = [], []
         self.rnn_num = 0
         self.input_size = input_size
@@ -128,7 +71,8 @@ class RNNBase(torch.nn.Module):
         width_in = input_size
         for ind, width in enumerate(list(hidden_size_list) + [output_size]):
             lid = self.layer_type[ind]
-            layer, hidden_width = self._make_layer(lid, width_in, width)
+            self.layer_kind.append(kind_of(lid))
+            layer, hidden_width = self._make_layer(lid, self.layer_kind[ind], width_in, width)
             self.layer_list.append(layer)
             if hidden_width is not None:
                 self.rnn_num += 1
@@ -136,48 +80,17 @@ class RNNBase(torch.nn.Module):
                 self.rnn_layer_type.append(lid)
             self.activation_list.append(self._make_activation(activation[ind], width))
             width_in = width
+        self.rnn_layer_kind = [kind for kind in self.layer_kind if kind is not None]           # beside rnn_layer_type
         self.xavier_initialize_weights()
 
     @staticmethod
-    def _make_layer(lid: str, n_in: int, n_out: int):
+    def _make_layer(lid: str, kind, n_in: int, n_out: int):
+        """-> (module, state width; None for a dense layer)."""
+        if kind is not None:
+            return kind.build(lid, n_in, n_out)
         if lid == 'fc':
             return Linear(n_in, n_out), None
-        if lid.startswith('efc'):
-            return EnsembleLinear(n_in, n_out, int(lid.split('-')[-1])), None
-        if lid == 'gru':
-            return GRU(n_in, n_out, batch_first=True), n_out
-        if lid == 'gilr':
-            return GILRLayer(n_in, n_out, batch_first=True), n_out
-        if lid == 'lru':
-            return LRULayer(n_in, n_out, batch_first=True), n_out * 2
-        if lid == 'gilr_lstm':
-            return GILRLSTMLayer(n_in, n_out, batch_first=True), n_out * 2
-        if lid.startswith('mamba'):
-            cfg = parse_mamba_id(lid)
-            layer = MambaResidualBlock(n_in, n_out, d_conv=cfg['d_conv'], d_state=cfg['d_state'], use_ff=cfg['use_ff'])
-            return layer, layer.mixer.desired_hidden_dim
-        if lid.startswith('conv1d'):
-            layer = Conv1d(n_in, n_out, d_conv=int(lid.split('_')[-1]) if '_' in lid else 4)
-            return layer, layer.desired_hidden_dim
-        if lid.startswith('smamba'):
-            cfg = parse_smamba_id(lid)
-            assert n_in == n_out, f'mamba_simple require input_dim == output_dim, while got {n_in} and {n_out}'
-            layer = MambaBlockList(cfg['block_num'], n_in, d_conv=cfg['d_conv'], d_state=cfg['d_state'], rms_norm=cfg['rms_norm'],
-                                   use_ff=cfg['use_ff'])
-            return layer, layer.desired_hidden_dim
-        if lid.startswith('cgpt'):
-            cfg = parse_cgpt_id(lid)
-            return TransformerDecoder(n_in, cfg['nhead'], 4 * n_in, cfg['nlayer'], cfg['pdrop'], cfg['ln']), cfg['maxlength']
-        if lid == 'lstm':
-            # the reference lists `lstm` (rnn_base.py:58) but cannot run it on this path either: ContextualModel.meta_forward asks every
-            # embedding network for its full hidden sequence (contextual_model.py:92-94, 113-115) and RNNHidden refuses to hold one for an
-            # LSTM (RNNHidden.py:23-25: 'It is not supported to store full RNN output of LSTM!!!')
-            raise NotImplementedError("layer id 'lstm': the reference's full-trajectory path rejects it as well (RNNHidden.py:23-25 asserts "
-                                      "when ContextualModel.meta_forward requests the full hidden sequence, contextual_model.py:92-94)")
-        if lid.startswith(_UNSUPPORTED_PREFIXES):
-            raise NotImplementedError(f'layer id {lid!r} exists in the reference but is outside the MI355X hot path of this build '
-                                      f'(supported: fc, efc-<E>, gru, gilr, lru, gilr_lstm, smamba_*, mamba_*, conv1d_*, cgpt_*)')
-        raise NotImplementedError(f'unknown layer id {lid!r}')
+        return EnsembleLinear(n_in, n_out, int(lid.split('-')[-1])), None
 
     @staticmethod
     def _make_activation(spec: str, width: int):
@@ -228,22 +141,22 @@ class RNNBase(torch.nn.Module):
                     elif 'bias' in name:
                         torch.nn.init.constant_(param.data, 0)
 
+    def sequence_layers(self):
+        """[(kind, module)] of the sequence layers, in stack order: what the trainers ask about a network's layers, they ask here."""
+        return [(kind, layer) for kind, layer in zip(self.layer_kind, self.layer_list) if kind is not None]
+
     def rnn_parameters(self, recursive=True):
         out = []
-        for lid, layer in zip(self.layer_type, self.layer_list):
-            if is_rnn_layer(lid):
-                out += list(layer.rnn_parameters()) if hasattr(layer, 'rnn_parameters') else list(layer.parameters(recursive))
+        for _, layer in self.sequence_layers():
+            out += list(layer.rnn_parameters()) if hasattr(layer, 'rnn_parameters') else list(layer.parameters(recursive))
         return out
 
     # ------------------------------------------------------------------------------------------ hidden state
     def _make_state(self, batch_size, device, random: bool) -> RNNHidden:
         st = RNNHidden(self.rnn_num, self.rnn_layer_type, device)
-        for width, lid in zip(self.rnn_hidden_state_input_size, self.rnn_layer_type):
-            if lid.startswith('cgpt'):
-                st.append(InferenceParams(max_seqlen=width, max_batch_size=batch_size))
-                continue
-            make = st.init_random_hidden_by_type if random else st.init_hidden_by_type
-            st.append(make(lid, batch_size, width, device))
+        make = st.init_random_hidden_by_type if random else st.init_hidden_by_type
+        for width, lid, kind in zip(self.rnn_hidden_state_input_size, self.rnn_layer_type, self.rnn_layer_kind):
+            st.append(kind.make_state(width, batch_size) if kind.make_state else make(lid, batch_size, width, device))
         return st
 
     def make_init_state(self, batch_size: int, device: Union[str, torch.device] = torch.device('cpu')) -> RNNHidden:
@@ -254,8 +167,8 @@ class RNNBase(torch.nn.Module):
 
     # ------------------------------------------------------------------------------------------ forward
     def _fuse_out_act(self, ind, x) -> bool:
-        """The activation module behind sequence layer `ind` is a plain ELU and this is a training pass over whole fp32 GPU sequences: the
-        layer may apply it in its last kernel (`out_act='elu'`)."""
+        """The activation module behind sequence layer `ind` is a plain ELU and this is a training pass over whole fp32 GPU sequences: a
+        layer whose kind can (`LayerKind.fuses_out_act`) may apply it in its last kernel (`out_act='elu'`)."""
         act_mod = self.activation_list[ind]
         return (_in_training_pass() and isinstance(act_mod, torch.nn.ELU) and act_mod.alpha == 1.0 and x.is_cuda
                 and x.dtype == torch.float32 and x.dim() == 3 and x.shape[-2] > 1)
@@ -309,8 +222,9 @@ class RNNBase(torch.nn.Module):
 
     def _forward_steps(self, x: torch.Tensor, hidden_state: Optional[RNNHidden] = None, require_full_hidden: bool = False,
                        first_grad_part=None, out_dest=None):
-        """Generator form of the forward pass: yields the (gi, W_hh, b_hh, h0) of every `gru` layer, is sent that recurrence's output
-        sequence, and returns (out, out_state, full) - so that ONE walk serves `meta_forward` and `lockstep_forward`.
+        """Generator form of the forward pass: yields the (gi, W_hh, b_hh, h0) of every `gru` layer (a `deferred` kind), is sent that
+        recurrence's output sequence, and returns (out, out_state, full) - so that ONE walk serves `meta_forward` and `lockstep_forward`.
+        Per layer: a dense step or a sequence step (through the layer's kind), then the activation tail.
         first_grad_part = (x_part, col0): the first layer (a shared-input efc layer) differentiates x only through that
         column block (EnsembleLinear.forward); anything else keeps the ordinary path.
         out_dest: an `ops.ColDest` - if the LAST layer is an `fc` on the hand-written GEMM, its output is written straight into that column
@@ -325,92 +239,30 @@ class RNNBase(torch.nn.Module):
         out_state = RNNHidden(self.rnn_num, self.rnn_layer_type, device=x.device, batch_first=False)
         full = RNNHidden(self.rnn_num, self.rnn_layer_type, device=x.device, batch_first=True) if require_full_hidden else None
         k = 0
-        n_layers = len(self.layer_list)
         fused_next = 0
         for ind, layer in enumerate(self.layer_list):
-            if fused_next:                          # consumed by the ensemble head / critic MLP node below
+            if fused_next:                          # consumed by the ensemble head / critic MLP node of the dense step
                 fused_next -= 1
                 continue
-            lid = self.layer_type[ind]
-            if is_rnn_layer(lid):
-                if lid in ('gilr', 'lru') and self._fuse_out_act(ind, x) and layer.use_ff:
-                    # the plain ELU behind the layer rides in its closing add + LayerNorm kernel (training passes only, see _TRAINING_PASS)
-                    if lid == 'gilr':
-                        x, h = layer(x, hidden_state[k], hidden_state.rnn_start, out_act='elu')
-                    else:
-                        x, h = layer(x, hidden_state[k], hidden_state.rnn_start, hidden_state.grad_detach, out_act='elu')
-                    k += 1
-                    out_state.append(h)
-                    if require_full_hidden:
-                        full.append(None)
-                    continue
-                if lid in ('gilr', 'gilr_lstm'):
-                    x, h = layer(x, hidden_state[k], hidden_state.rnn_start)
-                elif lid == 'lru':
-                    x, h = layer(x, hidden_state[k], hidden_state.rnn_start, hidden_state.grad_detach)
-                elif lid.startswith('smamba'):
-                    fuse_act = self._fuse_out_act(ind, x) and not layer.use_ff
-                    x, h = layer(x, hidden_state[k], hidden_state.rnn_start, hidden_state.mask, out_act='elu' if fuse_act else None)
-                    if fuse_act:                       # the activation rode in the layer's last GEMM: skip the module below
-                        k += 1
-                        out_state.append(h)
-                        if require_full_hidden:
-                            full.append(None)
-                        continue
-                elif lid.startswith('mamba'):
-                    x, h = layer(x, hidden_state[k], hidden_state.rnn_start, hidden_state.mask, hidden_state.grad_detach)
-                elif lid.startswith('conv1d'):
-                    x, h = layer(x, hidden_state[k], hidden_state.mask)
-                elif lid.startswith('cgpt'):
-                    multi = x.dim() == 3 and x.shape[-2] > 1          # whole packed rows (training) vs one rollout step
-                    fuse_act = multi and self._fuse_out_act(ind, x)
-                    x = layer(x, inference_params=None if multi else hidden_state[k],
-                              seqlens=hidden_state.attention_concat_mask if multi else None, out_act='elu' if fuse_act else None)
-                    h = hidden_state[k]
-                    if not multi:
-                        h.seqlen_offset += x.shape[-2]        # reference :451-452
-                    if fuse_act:                       # the activation rode in the decoder's output GEMM: skip the module below
-                        k += 1
-                        out_state.append(h)
-                        if require_full_hidden:
-                            full.append(None)
-                        continue
-                else:                                   # gru: no reset / mask handling (reference :453-454)
+            kind = self.layer_kind[ind]
+            if kind is None:
+                x, fused_next, act_done = self._dense_step(ind, layer, x, first_grad_part, out_dest)
+            else:
+                # the plain ELU behind the layer rides in the layer's last kernel (training passes only, see _TRAINING_PASS): its entry
+                # in the full record is None and the activation module below is skipped
+                out_act = 'elu' if kind.fuses_out_act(layer, x) and self._fuse_out_act(ind, x) else None
+                if kind.deferred:
                     x, h = layer.finish((yield layer.recurrence_job(x, hidden_state[k])))
+                else:
+                    x, h = kind.call(layer, x, hidden_state[k], hidden_state, out_act)
                 k += 1
                 out_state.append(h)
+                act_done = out_act is not None
                 if require_full_hidden:
-                    full.append(x)
-                act = self.activation_list[ind]
-            else:
-                act = self.activation_list[ind]
-                # efc-E ELU -> efc-E(H) ELU -> efc-E(1) = the published critic: ONE node whose GEMM epilogues carry the head and the
-                # ELU backward / bias gradient between the layers (ensemble_linear_model._CriticMLP)
-                if ind + 3 == n_layers and critic_mlp_fusable(layer, act, self.layer_list[ind + 1], self.activation_list[ind + 1],
-                                                              self.layer_list[ind + 2], self.activation_list[ind + 2], x):
-                    x = critic_mlp(layer, self.layer_list[ind + 1], self.layer_list[ind + 2], x, grad_part=first_grad_part if ind == 0 else None)
-                    fused_next = 2
-                    continue
-                # efc-E(H) ELU -> efc-E(1) at the end of the stack (the critic head): one fused node
-                if ind + 2 == n_layers and head_fusable(layer, act, self.layer_list[ind + 1], self.activation_list[ind + 1], x):
-                    x = ensemble_head(layer, self.layer_list[ind + 1], x)
-                    fused_next = 1
-                    continue
-                # plain ELU behind fc / efc-E: fused into the layer's bias pass (one in-place kernel; backward from the output)
-                if isinstance(act, torch.nn.ELU) and act.alpha == 1.0 and isinstance(layer, (EnsembleLinear, torch.nn.Linear)) \
-                        and x.dtype == torch.float32:
-                    if isinstance(layer, EnsembleLinear):
-                        x = layer(x, act='elu', grad_part=first_grad_part if ind == 0 else None)
-                    else:
-                        assert not (ind == 0 and first_grad_part is not None)
-                        x = ops.linear_act(x, layer.weight, layer.bias, 'elu', dest=out_dest if ind == n_layers - 1 else None)
-                    continue
-                assert not (ind == 0 and first_grad_part is not None), 'first_grad_part needs an efc first layer with ELU'
-
-                if isinstance(layer, torch.nn.Linear):                    # the bias rides in the GEMM epilogue (every pass: whole trajectories and rollout steps)
-                    x = ops.linear_act(x, layer.weight, layer.bias, None, dest=out_dest if ind == n_layers - 1 else None)
-                else:
-                    x = layer(x)
+                    full.append(None if act_done else x)
+            if act_done:
+                continue
+            act = self.activation_list[ind]
             if isinstance(act, torch.nn.ModuleList):
                 if self.activation_type[ind].startswith('eln'):
                     x = act[0](x.transpose(-2, 0)).transpose(-2, 0)
@@ -422,6 +274,37 @@ class RNNBase(torch.nn.Module):
         if squeeze:
             x = x.squeeze(0)
         return x, out_state, full
+
+    def _dense_step(self, ind, layer, x, first_grad_part, out_dest):
+        """The `fc` / `efc-<E>` layer `ind` -> (x, number of following layers its node consumed, their / its activation already applied)."""
+        n_layers = len(self.layer_list)
+        act = self.activation_list[ind]
+        # efc-E ELU -> efc-E(H) ELU -> efc-E(1) = the published critic: ONE node whose GEMM epilogues carry the head and the
+        # ELU backward / bias gradient between the layers (ensemble_linear_model._CriticMLP)
+        if ind + 3 == n_layers and critic_mlp_fusable(layer, act, self.layer_list[ind + 1], self.activation_list[ind + 1],
+                                                      self.layer_list[ind + 2], self.activation_list[ind + 2], x):
+            x = critic_mlp(layer, self.layer_list[ind + 1], self.layer_list[ind + 2], x, grad_part=first_grad_part if ind == 0 else None)
+            return x, 2, True
+        # efc-E(H) ELU -> efc-E(1) at the end of the stack (the critic head): one fused node
+        if ind + 2 == n_layers and head_fusable(layer, act, self.layer_list[ind + 1], self.activation_list[ind + 1], x):
+            x = ensemble_head(layer, self.layer_list[ind + 1], x)
+            return x, 1, True
+        # plain ELU behind fc / efc-E: fused into the layer's bias pass (one in-place kernel; backward from the output)
+        if isinstance(act, torch.nn.ELU) and act.alpha == 1.0 and isinstance(layer, (EnsembleLinear, torch.nn.Linear)) \
+                and x.dtype == torch.float32:
+            if isinstance(layer, EnsembleLinear):
+                x = layer(x, act='elu', grad_part=first_grad_part if ind == 0 else None)
+            else:
+                assert not (ind == 0 and first_grad_part is not None)
+                x = ops.linear_act(x, layer.weight, layer.bias, 'elu', dest=out_dest if ind == n_layers - 1 else None)
+            return x, 0, True
+        assert not (ind == 0 and first_grad_part is not None), 'first_grad_part needs an efc first layer with ELU'
+
+        if isinstance(layer, torch.nn.Linear):                    # the bias rides in the GEMM epilogue (every pass: whole trajectories and rollout steps)
+            x = ops.linear_act(x, layer.weight, layer.bias, None, dest=out_dest if ind == n_layers - 1 else None)
+        else:
+            x = layer(x)
+        return x, 0, False
 
     # ------------------------------------------------------------------------------------------ weights
     @staticmethod

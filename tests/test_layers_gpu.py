@@ -85,3 +85,41 @@ def test_training_pass_fuses_the_elu_behind_smamba_without_changing_values(lid):
     assert tol(y1, y0) and tol(g1, g0)
     for a, b in zip(p1, p0):
         assert (a is None) == (b is None) and (a is None or tol(a, b))
+
+
+@pytest.mark.parametrize('lid', ['gru', 'gilr_lstm', 'conv1d_5', 'mamba_s8_c3', 'smamba_s8_c5_b1_ff'])
+def test_training_pass_leaves_layers_that_cannot_fuse_the_elu_alone(lid):
+    """The sibling of the test above for the kinds that have no kernel to carry the ELU (`gru`, `gilr_lstm`, `conv1d`, `mamba`) or not in
+    this configuration (`smamba_*_ff`: the feed-forward block closes the layer, not the head GEMM): inside `training_pass()` they run the
+    very code they run outside it - the full-hidden record holds the pre-activation sequence, output and every gradient are bit-equal."""
+    if not torch.cuda.is_available():
+        pytest.skip('needs a GPU')
+    from offpolicy_rnn.models.rnn_base import RNNBase, training_pass
+    torch.manual_seed(3)
+    net = RNNBase(32, 32, [64, 64], ['elu', 'elu', 'linear'], ['fc', lid, 'fc']).cuda()
+    B, L = 2, 40
+    x = torch.randn(B, L, 32, device='cuda')
+    start = torch.zeros(B, L, 1, device='cuda')
+    start[:, :5] = 1
+    start[0, 17] = 1
+    mask = torch.ones(B, L, 1, device='cuda')
+    w = torch.randn(B, L, 32, device='cuda')
+    res = []
+    for inside in (False, True):
+        net.zero_grad()
+        xs = x.clone().requires_grad_(True)
+        hid = net.make_init_state(B, torch.device('cuda'))
+        hid.set_rnn_start(start)
+        hid.set_mask(mask)
+        if inside:
+            with training_pass():
+                y, _, full = net.meta_forward(xs, hid, require_full_hidden=True)
+        else:
+            y, _, full = net.meta_forward(xs, hid, require_full_hidden=True)
+        (y * w).sum().backward()
+        res.append((y.detach(), xs.grad, [None if p.grad is None else p.grad.clone() for p in net.parameters()], full))
+    (y0, g0, p0, f0), (y1, g1, p1, f1) = res
+    assert torch.is_tensor(f0[0]) and torch.is_tensor(f1[0]) and f0[0].shape == f1[0].shape == (B, L, 64)
+    assert torch.equal(f1[0], f0[0]) and torch.equal(y1, y0) and torch.equal(g1, g0)
+    for a, b in zip(p1, p0):
+        assert (a is None) == (b is None) and (a is None or torch.equal(a, b))
