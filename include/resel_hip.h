@@ -693,6 +693,44 @@ int resel_tmaze_collect_step(resel_tmaze_cfg_t cfg, resel_collect_layout_t lay, 
                              const int32_t* goal, int32_t* env_state, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
                              int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream);
 
+/* ---- Wind-v0 (reference envs/meta/toy_navigation/wind.py behind envs/meta/wrappers.py VariBadWrapper; host twin env_utils/wind.py):
+ * the two entries above for a continuous-action environment.  Same shape - the LAST node of a graphed policy step, one thread per row,
+ * 64-thread blocks, no LDS, no atomics, no allocation, nothing read from the host: capturable - and the same episode handling; what
+ * differs is the state, the payload of an episode (its wind) and the action, which is the row's A = 2 fp32 values at
+ * action[b * ld_action + 0 .. 1]: the Gaussian head's `mean` columns for the evaluation, its `sample` columns for the rollout.
+ *   env_pos [B, RESEL_WIND_STATE_DOUBLES] double: x, y, wind_x, wind_y, and the position before the last step (last_x, last_y);
+ *   env_words [B, RESEL_WIND_STATE_WORDS] int32: clock (steps of the episode), ep_len, episodes_started, running.
+ *   in_block rows: state[2] | lst_state[2] | lst_action[2] | reward[1]  (ld_in >= 7).
+ * A step is `env.step(unorm_act(a, env.action_space))` of the host loops, per component, every operation ONE correctly rounded
+ * operation of the stated width, never contracted:
+ *     t = (a + 1) / 2                                   in fp32 (the fp32 action meets Python scalars)
+ *     u = (double)t * out_span + out_low                the outward Box(-1, 1) with double bounds
+ *     c = clip(u, -1, 1);   v = act_low + ((c + 1.0) * 0.5) * act_span;   v = clip(v, act_low, act_high)
+ *     p = (p + v) + wind                                the new position
+ *   clock += 1;  done = clock >= episode_length;  dx = x - goal_x, dy = y - goal_y;  r = sqrt(dx * dx + dy * dy) <= goal_radius ? 1.0 : 0.0.
+ *   clip(x, lo, hi) is numpy's: min(max(x, lo), hi) with a NaN passing through.  So a NaN action component makes that component of
+ *   the position NaN for the rest of the episode: the observation carries the NaN, the reward is 0.0, the clock and `done` are unaffected.
+ *   cfg carries the bounds as the doubles the host arithmetic meets: act_low / act_high the fp32 +-0.1 promoted, act_span their fp32
+ *   difference promoted, out_low and out_span = high - low of the outward box.
+ * The next input row: lst_state <- state, state <- (float)position, lst_action <- a as read (bits kept), reward <- (float)r.
+ * evaluation entry: winds [B, J, 2] double (row stride ld_winds >= 2 J doubles): the wind of the j-th episode of row b; n_episodes, ret_acc,
+ *   ep_ret, ep_len, flags, init, idle rows and the hand-over at an episode's end as in the T-Maze evaluation entry (a reset puts the
+ *   position at (0, 0), last position (0, 0), and the episode's wind into env_pos).
+ * rollout entry: wind [B, 2] double, read by init only; traj, lay, T_cap, ld_row, max_episode_steps, init, stopped rows as in the
+ *   T-Maze rollout entry, except that the `action` field of a transition row is A columns wide and holds a as read.
+ * RESEL_EINVAL before the device is touched: a NULL pointer, A != 2, B < 0, ld_in < 7, ld_action < 2, episode_length < 1, a goal_radius
+ *   that is not >= 0, act_low > act_high, a NaN in cfg; evaluation: J < 1, ld_winds < 2 J, ld_ep < J; rollout: T_cap < 1,
+ *   max_episode_steps < 1, lay.logp >= 0, ld_row smaller than the furthest end of a present field.  B == 0 launches nothing, returns 0. */
+#define RESEL_WIND_STATE_DOUBLES 6
+#define RESEL_WIND_STATE_WORDS 4
+typedef struct { int32_t episode_length; double goal_x, goal_y, goal_radius, act_low, act_high, act_span, out_low, out_span; } resel_wind_cfg_t;
+int resel_wind_step(resel_wind_cfg_t cfg, int init, const float* action, int64_t ld_action, const double* winds, int64_t ld_winds,
+                    const int32_t* n_episodes, int J, double* env_pos, int32_t* env_words, double* ret_acc, double* ep_ret, int32_t* ep_len,
+                    int64_t ld_ep, float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream);
+int resel_wind_collect_step(resel_wind_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                            const double* wind, double* env_pos, int32_t* env_words, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                            int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream);
+
 /* ---- discrete-action update: differentiable categorical head, all-action value, the two discrete losses --------------------
  * (reference contextual_sac_discrete_policy.py:106-121 on whole rows; sac_full_length_rnn_redq.py:52-72 target, :85-86 actor,
  * sac_full_length_rnn_ensembleQ.py:158 critic on the action taken).  Raw fp32 device pointers; logits / logp / probs [M, A];

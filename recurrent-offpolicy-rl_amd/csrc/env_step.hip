@@ -133,10 +133,11 @@ __global__ __launch_bounds__(64) void tmaze_step_kernel(resel_tmaze_cfg_t cfg, i
 
 // ---- training rollout: one iteration of `SAC._train_loop` per replay ---------------------------------------------------------
 // Columns the transition row needs: the furthest end of a present field (widths: observations 2, last action A, scalars 1).
-__device__ __host__ inline int layout_need(const resel_collect_layout_t& lay, int A) {
+// `action` is one column (an index) unless the caller says otherwise (a continuous action: A columns).
+__device__ __host__ inline int layout_need(const resel_collect_layout_t& lay, int A, int action_width = 1) {
     const int off[11] = {lay.state, lay.last_state, lay.last_action, lay.action, lay.next_state, lay.reward,
                          lay.mask,  lay.start,      lay.done,        lay.reward_input, lay.timeout};
-    const int wid[11] = {2, 2, A, 1, 2, 1, 1, 1, 1, 1, 1};
+    const int wid[11] = {2, 2, A, action_width, 2, 1, 1, 1, 1, 1, 1};
     int need = 0;
     for (int f = 0; f < 11; ++f)
         if (off[f] >= 0 && off[f] + wid[f] > need) need = off[f] + wid[f];
@@ -200,6 +201,179 @@ __global__ __launch_bounds__(64) void tmaze_collect_kernel(resel_tmaze_cfg_t cfg
     if (done) st[SRUNNING] = 0;
 }
 
+// ---- Wind-v0 (reference envs/meta/toy_navigation/wind.py behind VariBadWrapper; host twin offpolicy_rnn/env_utils/wind.py) ----------
+// The same two kernels for a continuous-action environment: position and wind are doubles, the action is the row's two fp32 values.
+// Every operation of a step is one rounding of the width the host arithmetic has there; `contract(off)` keeps the products and sums apart.
+enum { PX = 0, PY, PWX, PWY, PLX, PLY };                                  // doubles of a row of env_pos
+enum { WT = 0, WLEN, WSTARTED, WRUNNING };                                // words of a row of env_words
+constexpr int WA = 2, WIN = 2 * 2 + WA + 1;                               // action width; state[2] | lst_state[2] | lst_action[2] | reward[1]
+
+// numpy's clip, minimum(maximum(x, lo), hi): a NaN fails both comparisons and passes through.
+__device__ __forceinline__ double np_clip(double x, double lo, double hi) {
+    x = x < lo ? lo : x;
+    return x > hi ? hi : x;
+}
+
+// One component of `env.step(unorm_act(a, env.action_space))`: the new coordinate.  Plain operators: the pragma governs what is
+// written here, not the bodies of the __d*_rn helpers, which would come back contractable after inlining.
+__device__ __forceinline__ double wind_move(const resel_wind_cfg_t& cfg, double p, float a, double wind) {
+#pragma clang fp contract(off)
+    const float t = (a + 1.0f) * 0.5f;                                    // (a + 1) / 2 in fp32
+    const double u = (double)t * cfg.out_span + cfg.out_low;
+    const double c = np_clip(u, -1.0, 1.0);
+    double v = cfg.act_low + ((c + 1.0) * 0.5) * cfg.act_span;
+    v = np_clip(v, cfg.act_low, cfg.act_high);
+    return (p + v) + wind;
+}
+
+// `Wind.last_reward`: 1.0 inside the goal ball; a NaN coordinate fails the comparison.
+__device__ __forceinline__ double wind_reward(const resel_wind_cfg_t& cfg, const double* ps) {
+#pragma clang fp contract(off)
+    const double dx = ps[PX] - cfg.goal_x, dy = ps[PY] - cfg.goal_y;
+    const double d = __dsqrt_rn(dx * dx + dy * dy);
+    return d <= cfg.goal_radius ? 1.0 : 0.0;
+}
+
+// One `Wind.step`: the position moves, the clock advances.  -> done; *r: the reward
+__device__ __forceinline__ bool wind_env_step(const resel_wind_cfg_t& cfg, double* ps, int32_t* w, const float* a, double* r) {
+    ps[PLX] = ps[PX];
+    ps[PLY] = ps[PY];
+    ps[PX] = wind_move(cfg, ps[PX], a[0], ps[PWX]);
+    ps[PY] = wind_move(cfg, ps[PY], a[1], ps[PWY]);
+    const int t = w[WT] + 1;
+    w[WT] = t;
+    *r = wind_reward(cfg, ps);
+    return t >= cfg.episode_length;
+}
+
+// The input row of the next policy step: lst_state <- state, state <- (float)position, lst_action <- a as read, reward <- (float)r.
+__device__ __forceinline__ void wind_feed_back(const double* ps, float* in, const float* a, double r) {
+    in[2] = in[0];
+    in[3] = in[1];
+    in[0] = (float)ps[PX];
+    in[1] = (float)ps[PY];
+    in[4] = a[0];
+    in[5] = a[1];
+    in[6] = (float)r;
+}
+
+// `reset(task)`: the position (and the one before it) at the origin, the episode's wind, the clock at 0.
+__device__ __forceinline__ void wind_reset(const double* wind, double* ps, int32_t* w, int started) {
+    ps[PX] = ps[PY] = ps[PLX] = ps[PLY] = 0.0;
+    ps[PWX] = wind[0];
+    ps[PWY] = wind[1];
+    w[WT] = 0;
+    w[WSTARTED] = started;
+    w[WRUNNING] = 1;
+}
+
+// `begin()` of the scheduler for one row, as `begin_row` above: the reset observation is (0, 0) either way.
+__device__ __forceinline__ void wind_begin_row(int j, int n, const double* winds_row, double* ps, int32_t* w, double* ret, float* in,
+                                               int32_t* flag) {
+    for (int c = 0; c < WIN; ++c) in[c] = 0.f;
+    *flag = 1;
+    *ret = 0.0;
+    w[WLEN] = 0;
+    if (j < n)
+        wind_reset(winds_row + 2 * j, ps, w, j + 1);
+    else
+        w[WRUNNING] = 0;
+}
+
+__global__ __launch_bounds__(64) void wind_step_kernel(resel_wind_cfg_t cfg, int init, const float* __restrict__ action, int64_t ld_action,
+                                                       const double* __restrict__ winds, int64_t ld_winds,
+                                                       const int32_t* __restrict__ n_episodes, int J, double* __restrict__ env_pos,
+                                                       int32_t* __restrict__ env_words, double* __restrict__ ret_acc,
+                                                       double* __restrict__ ep_ret, int32_t* __restrict__ ep_len, int64_t ld_ep,
+                                                       float* __restrict__ in_block, int64_t ld_in, int32_t* __restrict__ flags, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double* ps = env_pos + (int64_t)b * RESEL_WIND_STATE_DOUBLES;
+    int32_t* w = env_words + (int64_t)b * RESEL_WIND_STATE_WORDS;
+    float* in = in_block + (int64_t)b * ld_in;
+    const double* winds_row = winds + (int64_t)b * ld_winds;
+    const int n = min(max(n_episodes[b], 0), J);          // never past the row's J winds / result slots
+    if (init) {
+        for (int c = 0; c < RESEL_WIND_STATE_DOUBLES; ++c) ps[c] = 0.0;
+        for (int c = 0; c < RESEL_WIND_STATE_WORDS; ++c) w[c] = 0;
+        wind_begin_row(0, n, winds_row, ps, w, ret_acc + b, in, flags + b);
+        return;
+    }
+    if (!w[WRUNNING]) {                                   // idle: zeros with the flag set
+        for (int c = 0; c < WIN; ++c) in[c] = 0.f;
+        flags[b] = 1;
+        return;
+    }
+    const float a[WA] = {action[(int64_t)b * ld_action], action[(int64_t)b * ld_action + 1]};
+    double r;
+    const bool done = wind_env_step(cfg, ps, w, a, &r);
+    wind_feed_back(ps, in, a, r);
+    const double ret = __dadd_rn(ret_acc[b], r);
+    ret_acc[b] = ret;
+    const int len = w[WLEN] + 1;
+    w[WLEN] = len;
+    flags[b] = 0;
+    if (done) {
+        const int j = w[WSTARTED] - 1;
+        if (j >= 0 && j < J) {                            // always true behind an init call
+            ep_ret[(int64_t)b * ld_ep + j] = ret;
+            ep_len[(int64_t)b * ld_ep + j] = len;
+        }
+        wind_begin_row(j + 1, n, winds_row, ps, w, ret_acc + b, in, flags + b);
+    }
+}
+
+__global__ __launch_bounds__(64) void wind_collect_kernel(resel_wind_cfg_t cfg, resel_collect_layout_t lay, int init,
+                                                          const float* __restrict__ action, int64_t ld_action,
+                                                          const double* __restrict__ wind, double* __restrict__ env_pos,
+                                                          int32_t* __restrict__ env_words, double* __restrict__ ret_acc,
+                                                          float* __restrict__ traj, int T_cap, int64_t ld_row, int max_episode_steps,
+                                                          float* __restrict__ in_block, int64_t ld_in, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double* ps = env_pos + (int64_t)b * RESEL_WIND_STATE_DOUBLES;
+    int32_t* w = env_words + (int64_t)b * RESEL_WIND_STATE_WORDS;
+    float* in = in_block + (int64_t)b * ld_in;
+    if (init) {                                           // `env_reset()`: the reset observation, zero last state / last action / reward
+        for (int c = 0; c < RESEL_WIND_STATE_WORDS; ++c) w[c] = 0;
+        for (int c = 0; c < WIN; ++c) in[c] = 0.f;
+        ret_acc[b] = 0.0;
+        wind_reset(wind + (int64_t)b * 2, ps, w, 1);
+        return;
+    }
+    if (!w[WRUNNING]) return;                             // the episode is over: the row waits for the host's next init, untouched
+    const float a[WA] = {action[(int64_t)b * ld_action], action[(int64_t)b * ld_action + 1]};
+    const int len = w[WLEN];
+    float before[WIN];                                    // state | last_state | last_action | reward_input as the policy just saw them
+    for (int c = 0; c < WIN; ++c) before[c] = in[c];
+    double r;
+    const bool done = wind_env_step(cfg, ps, w, a, &r);
+    wind_feed_back(ps, in, a, r);
+    if (len >= 0 && len < T_cap && layout_need(lay, WA, WA) <= ld_row) {   // what `SAC._push` stores, at row `len` of the episode block
+        float* row = traj + ((int64_t)b * T_cap + len) * ld_row;
+        put(row, lay.state, before, 2);
+        put(row, lay.last_state, before + 2, 2);
+        put(row, lay.last_action, before + 4, WA);
+        put(row, lay.action, a, WA);
+        put(row, lay.next_state, in, 2);
+        put1(row, lay.reward, (float)r);
+        put1(row, lay.mask, 1.f);
+        put1(row, lay.start, len == 0 ? 1.f : 0.f);
+        put1(row, lay.done, done ? 1.f : 0.f);
+        put1(row, lay.reward_input, before[4 + WA]);
+        put1(row, lay.timeout, len + 1 >= max_episode_steps ? 1.f : 0.f);
+    }
+    ret_acc[b] = __dadd_rn(ret_acc[b], r);
+    w[WLEN] = len + 1;
+    if (done) w[WRUNNING] = 0;
+}
+
+// A cfg the Wind entries refuse: a NaN anywhere fails its comparison.
+inline bool wind_cfg_bad(const resel_wind_cfg_t& c) {
+    return c.episode_length < 1 || !(c.goal_radius >= 0.0) || !(c.act_low <= c.act_high) || c.goal_x != c.goal_x || c.goal_y != c.goal_y ||
+           c.act_span != c.act_span || c.out_low != c.out_low || c.out_span != c.out_span;
+}
+
 }  // namespace
 
 extern "C" {
@@ -226,6 +400,31 @@ int resel_tmaze_step(resel_tmaze_cfg_t cfg, int init, const float* action, int64
     if (B == 0) return RESEL_OK;
     hipLaunchKernelGGL(tmaze_step_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cfg, init, action, ld_action, goals,
                        ld_goals, n_episodes, J, env_state, ret_acc, ep_ret, ep_len, ld_ep, in_block, ld_in, A, flags, B);
+    return launch_status();
+}
+
+int resel_wind_step(resel_wind_cfg_t cfg, int init, const float* action, int64_t ld_action, const double* winds, int64_t ld_winds,
+                    const int32_t* n_episodes, int J, double* env_pos, int32_t* env_words, double* ret_acc, double* ep_ret, int32_t* ep_len,
+                    int64_t ld_ep, float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream) {
+    if (!action || !winds || !n_episodes || !env_pos || !env_words || !ret_acc || !ep_ret || !ep_len || !in_block || !flags) return RESEL_EINVAL;
+    if (A != WA || B < 0 || ld_in < WIN || ld_action < WA || J < 1 || ld_winds < 2 * (int64_t)J || ld_ep < J) return RESEL_EINVAL;
+    if (wind_cfg_bad(cfg)) return RESEL_EINVAL;
+    if (B == 0) return RESEL_OK;
+    hipLaunchKernelGGL(wind_step_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cfg, init, action, ld_action, winds, ld_winds,
+                       n_episodes, J, env_pos, env_words, ret_acc, ep_ret, ep_len, ld_ep, in_block, ld_in, flags, B);
+    return launch_status();
+}
+
+int resel_wind_collect_step(resel_wind_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                            const double* wind, double* env_pos, int32_t* env_words, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                            int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream) {
+    if (!action || !wind || !env_pos || !env_words || !ret_acc || !traj || !in_block) return RESEL_EINVAL;
+    if (A != WA || B < 0 || ld_in < WIN || ld_action < WA || T_cap < 1 || max_episode_steps < 1) return RESEL_EINVAL;
+    if (wind_cfg_bad(cfg)) return RESEL_EINVAL;
+    if (lay.logp >= 0 || ld_row < 1 || layout_need(lay, WA, WA) > ld_row) return RESEL_EINVAL;
+    if (B == 0) return RESEL_OK;
+    hipLaunchKernelGGL(wind_collect_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cfg, lay, init, action, ld_action, wind,
+                       env_pos, env_words, ret_acc, traj, T_cap, ld_row, max_episode_steps, in_block, ld_in, B);
     return launch_status();
 }
 

@@ -163,8 +163,16 @@ class SAC:
             return self.policy.make_init_state(1, self.sample_device)
         return self.policy.make_rnd_init_state(1, self.sample_device)
 
+    def draw_train_task(self):
+        """The task of a meta environment's next episode: one draw from the global numpy stream (reference sac.py:150-155)."""
+        tasks = self.env_info['train_tasks']
+        return tasks[np.random.randint(0, len(tasks))]
+
     def env_reset(self):
-        self.state_np = np.asarray(self.env.reset()).reshape((1, -1))
+        if hasattr(self.env, 'meta_env_flag') and getattr(self.env, 'n_tasks', None) is not None:
+            self.state_np = np.asarray(self.env.reset(self.draw_train_task())).reshape((1, -1))
+        else:
+            self.state_np = np.asarray(self.env.reset()).reshape((1, -1))
         self.last_action_np = np.zeros((1, self.act_dim))
         self.last_state_np = np.zeros((1, self.obs_dim))
         self.reward_np = np.zeros((1, 1))
@@ -235,8 +243,9 @@ class SAC:
                 # turns out ragged (fixed-length ones never switch), 0 / unset = exact shapes only
                 graphed = GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())
                 update = graphed.step
-        # a discrete T-Maze is collected on the device (utility/device_collect.py): environment step, transition row and next inputs are the
-        # last node of the policy step's graph; RESEL_DEVICE_COLLECT (read here) switches it, every other run keeps the host loop below
+        # an environment that exists as a kernel (a discrete T-Maze, Wind-v0: env_utils/device_env.py) is collected on the device
+        # (utility/device_collect.py): environment step, transition row and next inputs are the last node of the policy step's graph;
+        # RESEL_DEVICE_COLLECT (read here) switches it, every other run keeps the host loop below
         from ..utility.device_collect import DeviceCollector
         why = DeviceCollector.refusal(self)
         self.collector = None if why else DeviceCollector(self)

@@ -1,0 +1,178 @@
+"""The environments that exist as kernels (csrc/env_step.hip), one record each: everything `DeviceEnvEval` (utility/policy_eval.py) and
+`DeviceCollector` (utility/device_collect.py) need to know about the environment they step inside the policy step's graph.
+
+A record says which observation / action widths it steps, which policy head it reads and which of its output columns, how many bytes of
+device state a row has and how they are viewed, what an episode's init payload is (the T-Maze's goal side, Wind's wind vector), which
+two `ops` entries run it, and how the state comes back into the host environment object.  `device_env_kind(env)` finds the record of an
+environment object (None: it has no device step)."""
+import numpy as np
+import torch
+
+from . import tmaze, wind
+
+
+class TMazeKind:
+    """Discrete T-Maze (env_utils/tmaze.py): int32 words x, y, goal_y, oracle_visited, t, ep_len, episodes_started, running."""
+    obs_dim, act_dim = 2, 4
+    categorical, policy_words = True, 'a categorical one'
+    state_bytes = 4 * 8
+    payload_dtype, payload_np, payload_width = torch.int32, np.int32, 1
+    SLEN, SRUNNING = 5, 7
+
+    @staticmethod
+    def steps(env) -> bool:
+        return tmaze.device_steppable(env)
+
+    @staticmethod
+    def policy_ok(policy) -> bool:
+        return bool(getattr(policy, 'categorical', False))
+
+    @staticmethod
+    def episode_length(cfg) -> int:
+        return int(cfg['episode_length'])
+
+    @staticmethod
+    def action(out_dev, sampled: bool):
+        """The head's output columns the kernel reads: the mode index (evaluation) or the sampled one (rollout)."""
+        return out_dev[:, 1 if sampled else 0]
+
+    @staticmethod
+    def state_views(block, B):
+        """uint8 [B * state_bytes] -> the state tensors the `ops` entries take."""
+        return (block.view(torch.int32).view(B, 8),)
+
+    @staticmethod
+    def eval_step(ops, cfg, init, action, payload, n_ep, state, ret_acc, ep_ret, ep_len, in_dev, flags):
+        ops.tmaze_step(cfg, init, action, payload[:, :, 0], n_ep, state[0], ret_acc, ep_ret, ep_len, in_dev, flags)
+
+    @staticmethod
+    def collect_step(ops, cfg, name2range, init, action, payload, state, ret_acc, traj, max_episode_steps, in_dev):
+        ops.tmaze_collect_step(cfg, name2range, init, action, payload[:, 0], state[0], ret_acc, traj, max_episode_steps, in_dev)
+
+    @staticmethod
+    def eval_payloads(envs, n, draw_task):
+        """The payload of episodes 0 .. n - 1 (episode k runs on row k % rows), drawn as the host loop draws: each row's own stream, in
+        the row's episode order."""
+        rows = len(envs)
+        out = [None] * n
+        for r, env in enumerate(envs):
+            for k in range(r, n, rows):
+                out[k] = (env.draw_goal(),)
+        return out
+
+    @staticmethod
+    def eval_extras(n) -> dict:
+        return {}
+
+    @staticmethod
+    def behind_reset(env) -> bool:
+        return env.time_step == 0 and env.x == env.oracle_length and env.y == 0
+
+    @staticmethod
+    def current_payload(env):
+        return (env.goal_y,)
+
+    @staticmethod
+    def next_payload(alg):
+        """`env_reset()`'s draw for the next training episode, recorded in the environment object."""
+        alg.env.goal_y = alg.env.draw_goal()
+        return (alg.env.goal_y,)
+
+    @classmethod
+    def finished(cls, state_np):
+        """state_np: the row's state bytes on the host -> (steps taken, still running)."""
+        words = state_np.view(np.int32)
+        return int(words[cls.SLEN]), bool(words[cls.SRUNNING])
+
+    @staticmethod
+    def sync_env(env, state, row, o, a):
+        """The environment object's fields from the device state; -> (state_np, last_state_np, last_action_np) as the host loop holds them
+        mid-episode.  row: the step's input row (fp32)."""
+        st = state[0][0].cpu().numpy()
+        env.x, env.y, env.goal_y, env.oracle_visited, env.time_step = int(st[0]), int(st[1]), int(st[2]), bool(st[3]), int(st[4])
+        return (row[:o].copy().reshape(1, -1), row[o:2 * o].copy().reshape(1, -1), row[2 * o:2 * o + a].astype(np.float64).reshape(1, -1))
+
+
+class WindKind:
+    """Wind-v0 (env_utils/wind.py): doubles x, y, wind_x, wind_y, last_x, last_y, then int32 words clock, ep_len, episodes_started, running."""
+    obs_dim, act_dim = 2, 2
+    categorical, policy_words = False, 'a tanh-Gaussian SAC one'
+    state_bytes = 8 * 6 + 4 * 4
+    payload_dtype, payload_np, payload_width = torch.float64, np.float64, 2
+    WLEN, WRUNNING = 1, 3
+
+    @staticmethod
+    def steps(env) -> bool:
+        return wind.device_steppable(env)
+
+    @staticmethod
+    def policy_ok(policy) -> bool:                           # (TD3's deterministic policy with clipped noise keeps the host loop)
+        return not bool(getattr(policy, 'categorical', False)) and not hasattr(policy, 'sample_std')
+
+    @staticmethod
+    def episode_length(cfg) -> int:
+        return int(cfg['episode_length'])
+
+    @staticmethod
+    def action(out_dev, sampled: bool):
+        """mean | sample | logp: the evaluation reads the mean, the rollout the sample."""
+        return out_dev[:, 2:4] if sampled else out_dev[:, 0:2]
+
+    @staticmethod
+    def state_views(block, B):
+        return block[:B * 48].view(torch.float64).view(B, 6), block[B * 48:].view(torch.int32).view(B, 4)
+
+    @staticmethod
+    def eval_step(ops, cfg, init, action, payload, n_ep, state, ret_acc, ep_ret, ep_len, in_dev, flags):
+        ops.wind_step(cfg, init, action, payload, n_ep, state[0], state[1], ret_acc, ep_ret, ep_len, in_dev, flags)
+
+    @staticmethod
+    def collect_step(ops, cfg, name2range, init, action, payload, state, ret_acc, traj, max_episode_steps, in_dev):
+        ops.wind_collect_step(cfg, name2range, init, action, payload, state[0], state[1], ret_acc, traj, max_episode_steps, in_dev)
+
+    @staticmethod
+    def eval_payloads(envs, n, draw_task):
+        """One task per episode from the evaluator's private stream, in the order the host scheduler hands episodes out: exactly n draws."""
+        return [tuple(envs[k % len(envs)].winds[draw_task()]) for k in range(n)]
+
+    @staticmethod
+    def eval_extras(n) -> dict:
+        """What the wrapper's info adds to the host loop's result: the last report of an episode is `done_mdp = True`."""
+        return {'done_mdpTest': [1.0] * n}
+
+    @staticmethod
+    def behind_reset(env) -> bool:
+        return env.step_count == 0 and not env._state.any()
+
+    @staticmethod
+    def current_payload(env):
+        return tuple(env.get_current_task())
+
+    @staticmethod
+    def next_payload(alg):
+        """`env_reset()`'s draw for the next training episode: one task from the global numpy stream."""
+        alg.env.reset(alg.draw_train_task())
+        return tuple(alg.env.get_current_task())
+
+    @classmethod
+    def finished(cls, state_np):
+        words = state_np[48:].view(np.int32)
+        return int(words[cls.WLEN]), bool(words[cls.WRUNNING])
+
+    @staticmethod
+    def sync_env(env, state, row, o, a):
+        ps, words = state[0][0].cpu().numpy(), state[1][0].cpu().numpy()
+        env._state, env._wind, env.step_count = ps[0:2].copy(), ps[2:4].copy(), int(words[0])
+        env.done_mdp = env.step_count >= env._max_episode_steps
+        return ps[0:2].copy().reshape(1, -1), ps[4:6].copy().reshape(1, -1), row[2 * o:2 * o + a].copy().reshape(1, -1)
+
+
+KINDS = (TMazeKind, WindKind)
+
+
+def device_env_kind(env):
+    """The record of the kernel that steps `env`, or None."""
+    for kind in KINDS:
+        if kind.steps(env):
+            return kind
+    return None

@@ -2,17 +2,18 @@
 
 The simulator zoo of the reference (`envs/`) is out of scope.  Names of the form
 `synthetic-o<obs>-a<act>-T<len>` (or `-d<n>-` for n discrete actions) build the Gaussian environment used by the benchmark / tests;
-`Mem-T-{passive,active}-<L>[-cont-act]-v0` build the T-Maze memory task (env_utils/tmaze.py); anything else is
-handed to `gym.make` when gym is installed and fails loudly otherwise."""
+`Mem-T-{passive,active}-<L>[-cont-act]-v0` build the T-Maze memory task (env_utils/tmaze.py); `Wind-v0` builds the meta-RL task of
+env_utils/wind.py with the reference's task split; anything else - the other meta names included - is handed to `gym.make` when gym
+is installed and fails loudly otherwise."""
 import re
 
 import numpy as np
 
 
 class Box:
-    def __init__(self, low, high, shape):
-        self.low = np.full(shape, low, dtype=np.float32)
-        self.high = np.full(shape, high, dtype=np.float32)
+    def __init__(self, low, high, shape, dtype=np.float32):
+        self.low = np.full(shape, low, dtype=dtype)
+        self.high = np.full(shape, high, dtype=dtype)
         self.shape = tuple(shape)
         self._rs = np.random.RandomState(0)
 
@@ -60,6 +61,23 @@ class SyntheticEnv:
 _SYN = re.compile(r'^synthetic-o(\d+)-([ad])(\d+)-T(\d+)$')          # a<n>: Box(n) actions, d<n>: n discrete actions
 
 
+WIND_TASKS, WIND_TRAIN_TASKS, WIND_EVAL_TASKS = 60, 40, 20            # reference envs/pomdp_config.py 'Wind-v0'
+
+
+def _make_wind(seed: int) -> dict:
+    """Wind-v0 as reference envs/make_pomdp_env.py builds a meta environment: 60 tasks, shuffled by the permutation the reference draws
+    under `fixed_seed(seed)` - `RandomState(seed).permutation(60)`, the global numpy stream stays as it is -, the first 40 for training
+    and the last 20 for evaluation; one rollout per task, 75 steps.  The reference shares ONE object between `train_env` and `eval_env`
+    (seeded `seed`, then `seed + 1`); this build keeps its convention of two objects, seeded `seed` and `seed + 1`: the environment has
+    no random draw of its own after construction, so the two conventions behave alike."""
+    from .wind import Wind
+    env, eval_env = Wind(n_tasks=WIND_TASKS, seed=seed), Wind(n_tasks=WIND_TASKS, seed=seed + 1)
+    shuffled = np.random.RandomState(seed).permutation(WIND_TASKS)
+    return dict(train_env=env, eval_env=eval_env, train_tasks=shuffled[:WIND_TRAIN_TASKS], eval_tasks=shuffled[-WIND_EVAL_TASKS:],
+                max_rollouts_per_task=1, max_trajectory_len=env.horizon_bamdp, obs_dim=2, act_dim=2, act_continuous=True, seed=seed,
+                multiagent=False)
+
+
 def make_env(env_name: str, seed: int) -> dict:
     m = _SYN.match(env_name)
     if m:
@@ -75,6 +93,8 @@ def make_env(env_name: str, seed: int) -> dict:
         return dict(train_env=env, eval_env=eval_env, train_tasks=[], eval_tasks=[None], max_rollouts_per_task=1,
                     max_trajectory_len=env.episode_length, obs_dim=2, act_dim=4, act_continuous=env.continuous_act_space, seed=seed,
                     multiagent=False)
+    if env_name == 'Wind-v0':
+        return _make_wind(seed)
     try:
         import gym
     except ImportError as e:

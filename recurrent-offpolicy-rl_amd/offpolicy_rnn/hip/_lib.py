@@ -37,6 +37,14 @@ class TMazeCfg(ctypes.Structure):                       # resel_tmaze_cfg_t, by 
 
 
 TMAZE_STATE_WORDS = 8
+WIND_CFG_DOUBLES = ('goal_x', 'goal_y', 'goal_radius', 'act_low', 'act_high', 'act_span', 'out_low', 'out_span')
+
+
+class WindCfg(ctypes.Structure):                        # resel_wind_cfg_t, by value
+    _fields_ = [('episode_length', ctypes.c_int32)] + [(name, ctypes.c_double) for name in WIND_CFG_DOUBLES]
+
+
+WIND_STATE_DOUBLES, WIND_STATE_WORDS = 6, 4
 COLLECT_FIELDS = ('state', 'last_state', 'last_action', 'action', 'next_state', 'reward', 'logp', 'mask', 'start', 'done', 'reward_input',
                   'timeout')                            # the ring's `tuplenames`, in its order
 
@@ -144,6 +152,8 @@ SIGNATURES = {
     'resel_categorical_step': (c_int, [P, L, P, F, P, L, P, P, L, I, I, S]),
     'resel_tmaze_step': (c_int, [TMazeCfg, I, P, L, P, L, P, I, P, P, P, P, L, P, L, I, P, I, S]),
     'resel_tmaze_collect_step': (c_int, [TMazeCfg, CollectLayout, I, P, L, P, P, P, P, I, L, I, P, L, I, I, S]),
+    'resel_wind_step': (c_int, [WindCfg, I, P, L, P, L, P, I, P, P, P, P, P, L, P, L, I, P, I, S]),
+    'resel_wind_collect_step': (c_int, [WindCfg, CollectLayout, I, P, L, P, P, P, P, P, I, L, I, P, L, I, I, S]),
     'resel_categorical_fwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_categorical_bwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_discrete_value': (c_int, [P, P, I, P, P, P, I, I, I, S]),

@@ -2339,6 +2339,81 @@ def tmaze_collect_step(cfg: dict, name2range: dict, init: bool, action, goal, en
                                          A, B, _stream()), 'tmaze_collect_step')
 
 
+def _wind_cfg(cfg: dict):
+    from ._lib import WIND_CFG_DOUBLES, WindCfg
+    return WindCfg(int(cfg['episode_length']), *[float(cfg[name]) for name in WIND_CFG_DOUBLES])
+
+
+def _wind_common(what, B, action, env_pos, env_words, ret_acc, in_block):
+    """The argument checks the two Wind entries share -> the action's row stride."""
+    from ._lib import WIND_STATE_DOUBLES, WIND_STATE_WORDS
+    A = 2
+    assert action.dtype == torch.float32 and action.shape == (B, A) and (action.stride(1) == 1), f'{what}: action is fp32 [B, 2], unit column stride'
+    assert env_pos.dtype == torch.float64 and env_pos.is_contiguous() and env_pos.shape == (B, WIND_STATE_DOUBLES)
+    assert env_words.dtype == torch.int32 and env_words.is_contiguous() and env_words.shape == (B, WIND_STATE_WORDS)
+    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
+    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
+    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
+    return max(action.stride(0), A)
+
+
+@torch.no_grad()
+def wind_step(cfg: dict, init: bool, action, winds, n_episodes, env_pos, env_words, ret_acc, ep_ret, ep_len, in_block, flags):
+    """One Wind-v0 environment step (or, init: the start of an evaluation) for the B rows of a graphed policy step, as one launch:
+    include/resel_hip.h `resel_wind_step`, host twin env_utils/wind.py.  cfg: `Wind.device_config()`.
+    action: fp32 [B, 2] view, any row stride - the action means (columns 0:2 of the Gaussian head's output block);
+    winds fp64 [B, J, 2], n_episodes int32 [B] (each at most J), env_pos fp64 [B, 6], env_words int32 [B, 4], ret_acc fp64 [B],
+    ep_ret fp64 / ep_len int32 [B, J]; in_block fp32 [B, >= 7] with unit column stride (state[2] | lst_state[2] | lst_action[2] | reward[1]),
+    flags int32 [B].  Everything is updated in place; nothing else on the stream, no host read, no allocation: capturable."""
+    _need_cuda('wind_step', action, winds, n_episodes, env_pos, env_words, ret_acc, ep_ret, ep_len, in_block, flags)
+    B, A = flags.numel(), 2
+    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
+    ld_action = _wind_common('wind_step', B, action, env_pos, env_words, ret_acc, in_block)
+    assert winds.dtype == torch.float64 and winds.dim() == 3 and winds.shape[0] == B and winds.shape[2] == 2 and winds.is_contiguous()
+    J = winds.shape[1]
+    assert n_episodes.dtype == torch.int32 and n_episodes.is_contiguous() and n_episodes.numel() == B
+    assert ep_ret.dtype == torch.float64 and ep_len.dtype == torch.int32 and ep_ret.shape == ep_len.shape == (B, J)
+    assert ep_ret.is_contiguous() and ep_len.is_contiguous()
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    check(lib().resel_wind_step(_wind_cfg(cfg), int(bool(init)), _p(action), ld_action, _p(winds), 2 * J, _p(n_episodes), J, _p(env_pos),
+                                _p(env_words), _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block), max(in_block.stride(0), 2 * 2 + A + 1),
+                                A, _p(flags), B, _stream()), 'wind_step')
+
+
+@torch.no_grad()
+def wind_collect_step(cfg: dict, name2range: dict, init: bool, action, wind, env_pos, env_words, ret_acc, traj, max_episode_steps: int, in_block):
+    """One iteration of the training rollout on Wind-v0 (or, init: `env_reset()` with the winds in `wind`) for the B rows of a graphed policy
+    step, as one launch: include/resel_hip.h `resel_wind_collect_step`, host twin `SAC._train_loop` / `_push` / `env_step`.
+    cfg: `Wind.device_config()`.  name2range: `MemoryArray.name2range`; a stored field must have the width the rollout produces
+    (observations, last action and action 2, scalars 1; no log-probability).  action: fp32 [B, 2] view, any row stride - the SAMPLED actions
+    (columns 2:4 of the Gaussian head's output block); wind fp64 [B, 2]; env_pos fp64 [B, 6], env_words int32 [B, 4], ret_acc fp64 [B];
+    traj fp32 [B, T_cap, >= the layout's width] with unit column stride: the episode block; in_block fp32 [B, >= 7] with unit column stride.
+    Everything is updated in place; no host read, no allocation: capturable."""
+    from ._lib import COLLECT_FIELDS, CollectLayout
+    _need_cuda('wind_collect_step', action, wind, env_pos, env_words, ret_acc, traj, in_block)
+    A = 2
+    assert wind.dtype == torch.float64 and wind.dim() == 2 and wind.shape[1] == 2 and wind.is_contiguous()
+    B = wind.shape[0]
+    ld_action = _wind_common('wind_collect_step', B, action, env_pos, env_words, ret_acc, in_block)
+    assert traj.dtype == torch.float32 and traj.dim() == 3 and traj.shape[0] == B and traj.shape[1] >= 1 and traj.shape[2] >= 1
+    T_cap, ld_row = traj.shape[1], traj.stride(1) if traj.shape[1] > 1 else max(traj.stride(1), traj.shape[2])
+    assert traj.stride(2) == 1 and ld_row >= traj.shape[2] and (B <= 1 or traj.stride(0) == T_cap * ld_row), 'rows of one episode block'
+    widths = dict(state=2, last_state=2, next_state=2, last_action=A, action=A, logp=0)
+    lay = CollectLayout()
+    for name in COLLECT_FIELDS:
+        a, b = name2range[name]
+        if b > a:
+            assert b - a == widths.get(name, 1) and a >= 0, f'wind_collect_step: field {name} is {b - a} wide in the ring'
+            assert b <= traj.shape[2], f'wind_collect_step: field {name} ends at column {b} of {traj.shape[2]}'
+        setattr(lay, name, a if b > a else -1)
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    check(lib().resel_wind_collect_step(_wind_cfg(cfg), lay, int(bool(init)), _p(action), ld_action, _p(wind), _p(env_pos), _p(env_words),
+                                        _p(ret_acc), _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block),
+                                        max(in_block.stride(0), 2 * 2 + A + 1), A, B, _stream()), 'wind_collect_step')
+
+
 @torch.no_grad()
 def soft_update_(target_flat, online_flat, tau):
     _need_cuda('soft_update', target_flat, online_flat)

@@ -1,4 +1,4 @@
-"""Training rollouts of a discrete T-Maze on the device: one graph replay per environment step, one copy back per episode.
+"""Training rollouts of an environment that exists as a kernel (a discrete T-Maze, Wind-v0) on the device: one graph replay per environment step, one copy back per episode.
 
 `SAC._train_loop` pays one H2D, one replay, one D2H, one synchronise, a Python `TMaze.step`, a `Transition` / `mem_push` and the numpy
 bookkeeping of `env_step` for every environment step.  A T-Maze episode has a fixed length, the ring only admits whole trajectories and the
@@ -10,16 +10,19 @@ Per step the host issues `replay_device()` and counts; at an episode's last step
 environment words back with ONE D2H and ONE synchronise, hands the rows to `MemoryArray.push_rows`, logs the episode, draws the next goal
 side from the environment's own stream, starts the episode with one init launch outside the graph and loads a fresh recurrent state - the
 host loop's order of side effects, which fixes every random stream.  Ring, logs, generators and parameters equal the host loop's bit for bit
-(tests/test_device_collect_gpu.py).  `RESEL_DEVICE_COLLECT` switches it (read at `train()`)."""
+(tests/test_device_collect_gpu.py).  `RESEL_DEVICE_COLLECT` switches it (read at `train()`).
+
+Wind-v0 (continuous actions, `ops.wind_collect_step`) goes the same way: the kernel reads the Gaussian head's SAMPLED action, and the next
+episode's task is one draw from the global numpy stream where the host loop's `env_reset()` makes it (tests/test_wind_env_gpu.py).  What
+differs between the two environments lives in their records (env_utils/device_env.py)."""
 import os
 
 import numpy as np
 import torch
 
-from ..env_utils.tmaze import device_steppable
+from ..env_utils.device_env import device_env_kind
 
-DEVICE_COLLECT_DEFAULT = '1'                               # RESEL_DEVICE_COLLECT when the variable is not set (measured: profiles/r20_device_collect.md)
-SX, SY, SGOAL, SVISITED, ST, SLEN, SSTARTED, SRUNNING = range(8)   # words of env_state (csrc/env_step.hip)
+DEVICE_COLLECT_DEFAULT = '1'                               # RESEL_DEVICE_COLLECT when the variable is not set (measured: profiles/r20_device_collect.md, profiles/r22_wind_env.md)
 
 
 def device_collect_enabled() -> bool:
@@ -27,18 +30,20 @@ def device_collect_enabled() -> bool:
 
 
 class DeviceCollector:
-    """The environment loop of `alg.train()` for a discrete T-Maze, with the environment, the transition rows and the next inputs inside
-    the graphed policy step.  Built behind the warm-up and `env_reset()`: the first episode is the one `env_reset()` began (the
-    environment's current goal, no extra draw).  `collect_step()` is one iteration of the loop up to (not including) the update;
-    `sync_host()` writes the rollout state back into the trainer and the environment object."""
+    """The environment loop of `alg.train()` for an environment that exists as a kernel, with the environment, the transition rows and the
+    next inputs inside the graphed policy step.  Built behind the warm-up and `env_reset()`: the first episode is the one `env_reset()` began
+    (the environment's current goal side / wind, no extra draw).  `collect_step()` is one iteration of the loop up to (not including) the
+    update; `sync_host()` writes the rollout state back into the trainer and the environment object.  Everything that depends on the
+    environment comes from its record (`self.kind`, env_utils/device_env.py)."""
 
     @staticmethod
     def refusal(alg):
         """Why `alg.train()` collects through the host loop (None: it collects on the device)."""
-        if not device_steppable(alg.env):
-            return 'the environment has no device step (a T-Maze with discrete actions has one)'
-        if alg.sample_device.type != 'cuda' or not bool(getattr(alg.policy, 'categorical', False)):
-            return 'the policy is not a categorical one sampling on a CUDA device'
+        kind = device_env_kind(alg.env)
+        if kind is None:
+            return 'the environment has no device step (a T-Maze with discrete actions and Wind-v0 have one)'
+        if alg.sample_device.type != 'cuda' or not kind.policy_ok(alg.policy):
+            return f'the policy is not {kind.policy_words} sampling on a CUDA device'
         if os.environ.get('RESEL_GRAPH_ROLLOUT', '1') == '0':
             return 'RESEL_GRAPH_ROLLOUT=0'
         if not device_collect_enabled():
@@ -48,56 +53,57 @@ class DeviceCollector:
         return None
 
     def __init__(self, alg):
-        from ..hip._lib import TMAZE_STATE_WORDS
         from ..hip.graph_step import GraphedPolicyStep
         self.alg, self.env, self.device = alg, alg.env, alg.sample_device
+        self.kind = kind = device_env_kind(self.env)
         self.cfg = self.env.device_config()
-        self.T, self.obs_dim, self.act_dim = int(self.cfg['episode_length']), 2, 4
+        self.T, self.obs_dim, self.act_dim = kind.episode_length(self.cfg), kind.obs_dim, kind.act_dim
         assert alg.obs_dim == self.obs_dim and alg.act_dim == self.act_dim
         ring = alg.replay_buffer
         self.name2range, self.width = dict(ring.name2range), int(ring.width)
         self.step = GraphedPolicyStep(alg.policy, self.device, batch_size=1, after_step=self._env_step)
-        # one device block and one D2H per episode: return fp64 [1] | env_state int32 [1, 8] | episode rows fp32 [1, T, width]
-        head = 8 + 4 * TMAZE_STATE_WORDS
+        # one device block and one D2H per episode: return fp64 [1] | the row's environment state | episode rows fp32 [1, T, width]
+        head = 8 + kind.state_bytes
         self._res_dev = torch.zeros(head + 4 * self.T * self.width, dtype=torch.uint8, device=self.device)
         self._res_host = torch.zeros(self._res_dev.numel(), dtype=torch.uint8).pin_memory()
         self._ret = self._res_dev[:8].view(torch.float64)
-        self._env_state = self._res_dev[8:head].view(torch.int32).view(1, TMAZE_STATE_WORDS)       # zeros: the row is stopped until the first init
+        self._env_state = kind.state_views(self._res_dev[8:head], 1)       # zeros: the row is stopped until the first init
         self._traj = self._res_dev[head:].view(torch.float32).view(1, self.T, self.width)
         res = self._res_host.numpy()
-        self._ret_np, self._state_np = res[:8].view(np.float64), res[8:head].view(np.int32)
+        self._ret_np, self._state_np = res[:8].view(np.float64), res[8:head]
         self._rows_np = res[head:].view(np.float32).reshape(self.T, self.width)
-        self._goal_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self._goal_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._payload_host = torch.zeros((1, kind.payload_width), dtype=kind.payload_dtype).pin_memory()
+        self._payload_dev = torch.zeros((1, kind.payload_width), dtype=kind.payload_dtype, device=self.device)
         self._counters = []
         self.t = 0                                         # steps of the running episode that have been replayed
         self.started = False
         self.replays = self.episode_syncs = self.init_launches = 0
 
     # ------------------------------------------------------------------------------------------ graph side
-    def _env_step(self, step):
+    def _launch(self, init: bool):
         from ..hip import ops
-        ops.tmaze_collect_step(self.cfg, self.name2range, False, step._out_dev[:, 1], self._goal_dev, self._env_state, self._ret, self._traj,
-                               self.alg.max_episode_steps, step._in_dev)
+        step = self.step
+        self.kind.collect_step(ops, self.cfg, self.name2range, init, self.kind.action(step._out_dev, True), self._payload_dev, self._env_state,
+                               self._ret, self._traj, self.alg.max_episode_steps, step._in_dev)
 
-    def _init_episode(self, goal: int):
-        from ..hip import ops
-        self._goal_host[0] = int(goal)
-        self._goal_dev.copy_(self._goal_host, non_blocking=True)
-        ops.tmaze_collect_step(self.cfg, self.name2range, True, self.step._out_dev[:, 1], self._goal_dev, self._env_state, self._ret,
-                               self._traj, self.alg.max_episode_steps, self.step._in_dev)
+    def _env_step(self, step):
+        self._launch(False)
+
+    def _init_episode(self, payload):
+        self._payload_host[0] = torch.as_tensor(payload, dtype=self.kind.payload_dtype)
+        self._payload_dev.copy_(self._payload_host, non_blocking=True)
+        self._launch(True)
         self.init_launches += 1
         self.t = 0
 
     def _begin(self):
         """The first sample behind the warm-up, where the host loop captures its step: capture (the warm-up passes run the hook on a
         stopped row, so they see the zero input block the host loop's capture sees), then the episode `env_reset()` began."""
-        env = self.env
-        assert env.time_step == 0 and env.x == env.oracle_length and env.y == 0, 'the collector starts behind env_reset()'
+        assert self.kind.behind_reset(self.env), 'the collector starts behind env_reset()'
         self.step.load_hidden(self.alg.sample_hidden)
         self.step.capture(self.obs_dim, self.act_dim)
         self._counters = self.step._counters()
-        self._init_episode(env.goal_y)
+        self._init_episode(self.kind.current_payload(self.env))
         self.started = True
 
     # ------------------------------------------------------------------------------------------ the loop body
@@ -121,12 +127,11 @@ class DeviceCollector:
         self._res_host.copy_(self._res_dev, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         self.episode_syncs += 1
-        length = int(self._state_np[SLEN])
-        assert length == self.T and not self._state_np[SRUNNING], (length, self.T, self._state_np.tolist())
+        length, running = self.kind.finished(self._state_np)
+        assert length == self.T and not running, (length, self.T, self._state_np.tolist())
         alg.replay_buffer.push_rows(self._rows_np[:length])
         alg.logger.add_tabular_data(tb_prefix='Train', EpRet=float(self._ret_np[0]), EpLength=length)
-        self.env.goal_y = self.env.draw_goal()             # `env_reset()`: the draw of `env.reset()`, then the fresh recurrent state
-        self._init_episode(self.env.goal_y)
+        self._init_episode(self.kind.next_payload(alg))     # `env_reset()`: the draw of the next episode, then the fresh recurrent state
         alg.sample_hidden = alg._init_sample_hidden()
         self.step.load_hidden(alg.sample_hidden)
 
@@ -139,14 +144,12 @@ class DeviceCollector:
             return
         alg, env, o, a = self.alg, self.env, self.obs_dim, self.act_dim
         row = self.step._in_dev[0].cpu().numpy()            # (synchronises)
-        st = self._env_state[0].cpu().numpy()
-        env.x, env.y, env.goal_y, env.oracle_visited, env.time_step = int(st[SX]), int(st[SY]), int(st[SGOAL]), bool(st[SVISITED]), int(st[ST])
-        alg.state_np = row[:o].copy().reshape(1, -1)
+        state, last_state, last_action = self.kind.sync_env(env, self._env_state, row, o, a)
+        alg.state_np = state
         if self.t == 0:                                    # behind `env_reset()`
             alg.last_state_np, alg.last_action_np, alg.reward_np = np.zeros((1, o)), np.zeros((1, a)), np.zeros((1, 1))
         else:
-            alg.last_state_np = row[o:2 * o].copy().reshape(1, -1)
-            alg.last_action_np = row[2 * o:2 * o + a].astype(np.float64).reshape(1, -1)
+            alg.last_state_np, alg.last_action_np = last_state, last_action
             alg.reward_np = np.array([[env.last_reward()]])  # the double the float32 in the block was rounded from
             ring = alg.replay_buffer                       # the open episode's transitions wait in the ring's `memory`, as `mem_push` leaves them
             rows = self._traj[0, :self.t].cpu().numpy()

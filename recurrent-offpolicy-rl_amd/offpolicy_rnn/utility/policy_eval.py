@@ -9,7 +9,7 @@ position are reset inside the graph, hip/graph_step.py).
 `run_episodes` is the scheduler (host only, numpy in / numpy out); `BatchedPolicyEval` owns the graph, the environments and a private
 random stream, and leaves every global generator as it found it.
 
-An environment that exists as a kernel (the discrete T-Maze, env_utils/tmaze.py / `ops.tmaze_step`) is stepped INSIDE the graph:
+An environment that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, `ops.tmaze_step`; Wind-v0, `ops.wind_step`) is stepped INSIDE the graph:
 `DeviceEnvEval` appends the environment step to the policy step as its last node, so an evaluation is `waves x episode_length`
 back-to-back replays behind one init call, with one D2H at the end and no host round trip per step.  `RESEL_DEVICE_ENV=0` keeps
 such an environment on the host loop."""
@@ -99,54 +99,63 @@ def device_env_enabled() -> bool:
 
 
 class DeviceEnvEval:
-    """`run_episodes` for `rows` discrete T-Mazes with the environment step inside the graphed policy step.
+    """`run_episodes` for `rows` environments of one kind that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, Wind-v0),
+    with the environment step inside the graphed policy step.
 
     All episodes have the same length T, so the host scheduler runs episode k on row k % rows as that row's (k // rows)-th episode and
-    takes ceil(n / rows) * T steps; this object does the same with one `ops.tmaze_step(init=True)` call, that many `replay_device()`
-    calls, one D2H of the per-episode results and one synchronise.  The goal sides come from the per-row host environments
-    (`TMaze.draw_goal`, the draw their `reset()` makes), in the order the host loop would draw them.
+    takes ceil(n / rows) * T steps; this object does the same with one init call of the kind's evaluation entry, that many
+    `replay_device()` calls, one D2H of the per-episode results and one synchronise.  What an episode starts from - the T-Maze's goal side,
+    Wind's wind vector - comes from the kind's `eval_payloads`, which draws as the host loop would: the T-Maze from the per-row host
+    environments (`TMaze.draw_goal`, the draw their `reset()` makes), a meta environment one task per episode through `draw_task`.
     The hook runs in the warm-up and in the capture too, on whatever the buffers hold: every buffer is (re)initialised by the init
     call of each evaluation, never at capture."""
 
-    def __init__(self, policy, envs: List, device):
-        from ..hip._lib import TMAZE_STATE_WORDS
+    def __init__(self, policy, envs: List, device, draw_task: Optional[Callable] = None):
+        from ..env_utils.device_env import device_env_kind
         from ..hip.graph_step import GraphedPolicyStep
-        self.envs, self.rows, self.device = envs, len(envs), torch.device(device)
+        self.envs, self.rows, self.device, self.draw_task = envs, len(envs), torch.device(device), draw_task
+        self.kind = kind = device_env_kind(envs[0])
         self.cfg = envs[0].device_config()
-        assert all(e.device_config() == self.cfg for e in envs), 'one graph steps one kind of environment'
-        self.T, self.obs_dim, self.act_dim = int(self.cfg['episode_length']), 2, 4
+        assert all(device_env_kind(e) is kind and e.device_config() == self.cfg for e in envs), 'one graph steps one kind of environment'
+        self.T, self.obs_dim, self.act_dim = kind.episode_length(self.cfg), kind.obs_dim, kind.act_dim
         self.step = GraphedPolicyStep(policy, self.device, batch_size=self.rows, row_reset=True, after_step=self._env_step)
         self.J = 0
         dev = self.device
-        self._env_state = torch.zeros((self.rows, TMAZE_STATE_WORDS), dtype=torch.int32, device=dev)
+        self._env_state = kind.state_views(torch.zeros(self.rows * kind.state_bytes, dtype=torch.uint8, device=dev), self.rows)
         self._ret_acc = torch.zeros(self.rows, dtype=torch.float64, device=dev)
 
     def _ensure(self, J: int):
         """Tables for J episodes per row.  Their addresses are part of the captured graph: growing them captures again."""
         if J <= self.J:
             return
-        B, dev = self.rows, self.device
-        self._tab_host = torch.zeros(B * J + B, dtype=torch.int32).pin_memory()           # goals [B, J] | n_episodes [B]: one H2D
-        self._tab_dev = torch.zeros(B * J + B, dtype=torch.int32, device=dev)
-        self._goals, self._n_ep = self._tab_dev[:B * J].view(B, J), self._tab_dev[B * J:]
+        B, dev, kind = self.rows, self.device, self.kind
+        w = kind.payload_width
+        pay = B * J * w * torch.empty((), dtype=kind.payload_dtype).element_size()
+        self._tab_host = torch.zeros(pay + 4 * B, dtype=torch.uint8).pin_memory()         # payloads [B, J, w] | n_episodes int32 [B]: one H2D
+        self._tab_dev = torch.zeros(pay + 4 * B, dtype=torch.uint8, device=dev)
+        self._payload, self._n_ep = self._tab_dev[:pay].view(kind.payload_dtype).view(B, J, w), self._tab_dev[pay:].view(torch.int32)
+        self._payload_np, self._n_ep_np = self._tab_host.numpy()[:pay].view(kind.payload_np).reshape(B, J, w), self._tab_host.numpy()[pay:].view(np.int32)
         self._res_dev = torch.zeros(B * J * 12, dtype=torch.uint8, device=dev)            # ep_ret fp64 [B, J] | ep_len int32 [B, J]: one D2H
         self._res_host = torch.zeros(B * J * 12, dtype=torch.uint8).pin_memory()
         self._ep_ret, self._ep_len = self._res_dev[:B * J * 8].view(torch.float64).view(B, J), self._res_dev[B * J * 8:].view(torch.int32).view(B, J)
         self.J = J
         self.step.invalidate()
 
-    def _env_step(self, step):
+    def _launch(self, init: bool):
         from ..hip import ops
-        ops.tmaze_step(self.cfg, False, step._out_dev[:, 0], self._goals, self._n_ep, self._env_state, self._ret_acc, self._ep_ret,
-                       self._ep_len, step._in_dev, step._flags_dev)
+        step = self.step
+        self.kind.eval_step(ops, self.cfg, init, self.kind.action(step._out_dev, False), self._payload, self._n_ep, self._env_state,
+                            self._ret_acc, self._ep_ret, self._ep_len, step._in_dev, step._flags_dev)
+
+    def _env_step(self, step):
+        self._launch(False)
 
     def invalidate(self):
         self.step.invalidate()
 
     @torch.no_grad()
     def run(self, n_episodes: int):
-        """-> what `run_episodes` returns for these environments: ({'EpRetTest': [...], 'EpLenTest': [...]}, [row of each episode])."""
-        from ..hip import ops
+        """-> what `run_episodes` returns for these environments: ({'EpRetTest': [...], 'EpLenTest': [...], ...}, [row of each episode])."""
         n, B, T, step = int(n_episodes), self.rows, self.T, self.step
         if n <= 0:
             return {'EpRetTest': [], 'EpLenTest': []}, []
@@ -158,15 +167,12 @@ class DeviceEnvEval:
             if T > ip.max_seqlen:
                 raise RuntimeError(f'cgpt rollout: KV cache is full (row 0: {ip.max_seqlen} tokens, max_seqlen {ip.max_seqlen})')
         per_row = [len(range(r, n, B)) for r in range(B)]                    # ceil((n - r) / rows)
-        tab = self._tab_host.numpy()
-        tab[:] = 0
-        for r, env in enumerate(self.envs):                                  # each row's own stream, in draw order
-            for j in range(per_row[r]):
-                tab[r * J + j] = env.draw_goal()
-        tab[B * J:] = per_row
+        self._tab_host.zero_()
+        for k, payload in enumerate(self.kind.eval_payloads(self.envs, n, self.draw_task)):      # drawn in the host loop's order
+            self._payload_np[k % B, k // B] = payload
+        self._n_ep_np[:] = per_row
         self._tab_dev.copy_(self._tab_host, non_blocking=True)
-        ops.tmaze_step(self.cfg, True, step._out_dev[:, 0], self._goals, self._n_ep, self._env_state, self._ret_acc, self._ep_ret,
-                       self._ep_len, step._in_dev, step._flags_dev)
+        self._launch(True)
         for _ in range(waves * T):
             step.replay_device()
         self._res_host.copy_(self._res_dev, non_blocking=True)
@@ -179,6 +185,7 @@ class DeviceEnvEval:
         res = self._res_host.numpy()
         ep_ret, ep_len = res[:B * J * 8].view(np.float64).reshape(B, J), res[B * J * 8:].view(np.int32).reshape(B, J)
         out = {'EpRetTest': [float(ep_ret[k % B, k // B]) for k in range(n)], 'EpLenTest': [int(ep_len[k % B, k // B]) for k in range(n)]}
+        out.update(self.kind.eval_extras(n))
         return out, [k % B for k in range(n)]
 
 
@@ -217,9 +224,13 @@ class BatchedPolicyEval:
         if self.device_env is not None:
             self.device_env.invalidate()
 
+    def _draw_task(self):
+        """The task of a meta environment's next evaluation episode: one draw from the private stream (reference :53-56)."""
+        return self.eval_tasks[self.rs.randint(0, len(self.eval_tasks))]
+
     def _reset_env(self, env):
         if hasattr(env, 'meta_env_flag') and getattr(env, 'n_tasks', None) is not None:
-            return env.reset(self.eval_tasks[self.rs.randint(0, len(self.eval_tasks))])
+            return env.reset(self._draw_task())
         return env.reset()
 
     def _make(self):
@@ -234,17 +245,19 @@ class BatchedPolicyEval:
                 self.env_seeds.append(seed)
         if self._on_device():
             if self.device_env is None:
-                self.device_env = DeviceEnvEval(self.policy, self.envs, self.device)
+                self.device_env = DeviceEnvEval(self.policy, self.envs, self.device, draw_task=self._draw_task)
             return
         if self.step is None:
             from ..hip.graph_step import GraphedPolicyStep
             self.step = GraphedPolicyStep(self.policy, self.device, batch_size=self.rows, row_reset=True)
 
     def _on_device(self) -> bool:
-        """The in-graph environment step: discrete T-Mazes behind a categorical policy on a CUDA device, unless RESEL_DEVICE_ENV=0."""
-        from ..env_utils.tmaze import device_steppable
-        return (not self._host_only and self.discrete and self.device.type == 'cuda' and device_env_enabled()
-                and bool(getattr(self.policy, 'categorical', False)) and all(device_steppable(e) for e in self.envs))
+        """The in-graph environment step: environments of one kind that has a kernel (env_utils/device_env.py) behind the policy head that
+        kernel reads, on a CUDA device, unless RESEL_DEVICE_ENV=0."""
+        from ..env_utils.device_env import device_env_kind
+        kind = device_env_kind(self.envs[0])
+        return (not self._host_only and kind is not None and self.discrete == kind.categorical and self.device.type == 'cuda'
+                and device_env_enabled() and kind.policy_ok(self.policy) and all(device_env_kind(e) is kind for e in self.envs))
 
     def evaluate(self, n_episodes: int) -> Dict[str, list]:
         """n_episodes deterministic episodes (action = the policy's mean) of the current parameters, which the graph reads through

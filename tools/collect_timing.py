@@ -9,6 +9,9 @@ and - in the training workload - the evaluations and updates are inside the figu
     python tools/collect_timing.py --workload train [--iterations 40]
         the short training run of profiles/r19_device_env.md, shortened: `Mem-T-passive-10-v0`, gru, D = 32, `sac_batch_size` 1100, one update
         per 11 steps behind 1100 random steps, 10 evaluation episodes at the start of each iteration of 1100 steps
+    python tools/collect_timing.py --workload collect --env Wind-v0 --rnn smamba_b1_c8_s64_ff --steps 20000
+        collection only on another environment make_env.py builds without gym (`Wind-v0`, `synthetic-o2-a2-T75`): one random warm-up
+        episode, no update, no evaluation
     --tree DIR   time the sources of another checkout (DIR/bench.py, DIR/recurrent-offpolicy-rl_amd), e.g. the parent commit's
 
 Prints one JSON line: seconds, environment steps of the loop, microseconds per step, updates, and which path collected."""
@@ -24,6 +27,7 @@ ap.add_argument('--rnn', default=None)
 ap.add_argument('--D', type=int, default=None)
 ap.add_argument('--steps', type=int, default=20020)
 ap.add_argument('--iterations', type=int, default=40)
+ap.add_argument('--env', default=None, help='collect workload: the environment (default Mem-T-passive-1000-v0)')
 ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument('--label', default='')
 args = ap.parse_args()
@@ -33,13 +37,16 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'recurrent-offpolicy-rl_amd')]
 import torch
 import bench
 from offpolicy_rnn import alg_init
+from offpolicy_rnn.env_utils.make_env import make_env
 
 if args.workload == 'collect':
     rnn = args.rnn or 'smamba_s32_c16_b2_nln'
     D = args.D or (32 if rnn == 'gru' else 256)
-    par = bench.make_parameter(rnn, 2, 1001, D=D)
-    par.env_name = 'Mem-T-passive-1000-v0'
-    par.random_num, par.start_train_num, par.update_interval = 1001, 10 ** 9, 1
+    env_name = args.env or 'Mem-T-passive-1000-v0'
+    T = make_env(env_name, 0)['max_trajectory_len']
+    par = bench.make_parameter(rnn, 2, T, D=D)
+    par.env_name = env_name
+    par.random_num, par.start_train_num, par.update_interval = T, 10 ** 9, 1
     par.total_iteration, par.step_per_iteration = 1, args.steps
     par.test_nprocess = par.test_nrollout = 0
     par.max_buffer_transition_num = 200000

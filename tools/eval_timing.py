@@ -6,6 +6,7 @@ Both run the same host loop (`run_episodes`), the same environments and the poli
 name make_env.py builds without gym) replaces the benchmark's environment; a name with discrete actions (`-d<n>-`, `Mem-T-...-v0`) is a
 discrete-action run: categorical policy, the evaluator's discrete form.  A discrete T-Maze (`Mem-T-passive-1000-v0`) is stepped inside
 the graph of leg (a) unless RESEL_DEVICE_ENV=0 (utility/policy_eval.py `DeviceEnvEval`); `device_env` in the output says which it was.
+`--env Wind-v0` is the meta-RL task (continuous actions, 75 steps, evaluation tasks of seed 0), stepped inside the graph the same way.
 
     python tools/eval_timing.py [--rnn smamba_s32_c16_b2_nln cgpt_h8_l6_p0.1_ml1024_rms] [--episodes 10] [--steps 1000] [--n 3]
                                 [--env synthetic-o17-d6-T1000]
@@ -27,7 +28,7 @@ ap.add_argument('--rnn', nargs='+', default=['smamba_s32_c16_b2_nln', 'cgpt_h8_l
 ap.add_argument('--episodes', type=int, default=10)
 ap.add_argument('--steps', type=int, default=1000)
 ap.add_argument('--n', type=int, default=3)
-ap.add_argument('--env', default=None, help='synthetic-o<obs>-[ad]<act>-T<len> or Mem-T-{passive,active}-<L>-v0: replaces the benchmark '
+ap.add_argument('--env', default=None, help='synthetic-o<obs>-[ad]<act>-T<len>, Mem-T-{passive,active}-<L>-v0 or Wind-v0: replaces the benchmark '
                                             'environment and --steps')
 ap.add_argument('--skip-one-by-one', action='store_true', help='time leg (a) only')
 args = ap.parse_args()
@@ -64,7 +65,8 @@ for rnn in args.rnn:
     alg = alg_init(par)
     assert alg.discrete_env == discrete
     factory = lambda: make_env(par.env_name, 0)['eval_env']
-    batched = BatchedPolicyEval(alg.policy, factory, alg.act_dim, args.episodes, alg.device, discrete=discrete)
+    batched = BatchedPolicyEval(alg.policy, factory, alg.act_dim, args.episodes, alg.device, discrete=discrete,
+                                eval_tasks=make_env(par.env_name, 0).get('eval_tasks'))
     t_rows = timed(lambda: batched.evaluate(args.episodes))
 
     single = GraphedPolicyStep(alg.policy, alg.device, batch_size=1)
