@@ -21,6 +21,7 @@ from ..policy_value_models.make_models import make_policy_model, make_value_mode
 from ..utility.count_parameters import count_parameters
 from ..utility.sample_utility import n2t_2dim, norm_act, t2n, unorm_act
 from ..utility.timer import Timer
+from . import run_state
 from .flat_adamw import FlatAdamW
 
 
@@ -96,6 +97,12 @@ class SAC:
         self.sample_num = 0
         self.grad_num = 0
         self.start_time = time.time()
+        # the open training episode's running return and length, and the iterations `train()` has completed: part of the run state
+        # (algorithm/run_state.py).  While a DeviceCollector runs, the first two live on the device until `sync_host()`
+        self.ep_ret, self.ep_len = 0.0, 0
+        self.iteration = 0
+        self._collecting = False                # inside `train()`'s loop: the collector, when there is one, owns the open episode
+        self._host_episode_open = False         # a resumed run finishes the episode its state was taken in through the host loop
         self.allow_nest_stack = self.allow_nest_stack_trajs()
         self.logger(f'policy parameter num: {count_parameters(self.policy)}; value[0] parameter num: {count_parameters(self.values[0])}')
 
@@ -229,8 +236,25 @@ class SAC:
         return {}
 
     def train(self):
-        self.sample_num += self.warmup()
-        self.env_reset()
+        # RESEL_CHECKPOINT_DIR (read here; unset: nothing of this happens): the run state goes there every RESEL_CHECKPOINT_EVERY
+        # iterations, and a run that finds a complete state there continues it instead of starting (algorithm/run_state.py)
+        ckpt_dir = run_state.checkpoint_dir_from_env()
+        ckpt = None
+        resumed = False
+        if ckpt_dir is not None:
+            run_state.refuse_process_groups()
+            ckpt = (ckpt_dir, run_state.checkpoint_every_from_env())
+            found = run_state.newest_state(ckpt_dir)
+            if found is None:
+                self.logger(f'no run state in {ckpt_dir}: the run starts from the beginning')
+            else:
+                self.load_state(found[1])
+                resumed = True
+                self.logger(f'resumed the run state {found[1]}: {self.iteration} iterations, {self.sample_num} samples and {self.grad_num} updates done')
+        if not resumed:
+            self.sample_num += self.warmup()
+            self.env_reset()
+            self.iteration, self.ep_ret, self.ep_len = 0, 0.0, 0
         update = self.train_one_batch
         graphed = None
         if os.environ.get('RESEL_GRAPH_UPDATE', '1') != '0':  # default: the whole update as one hipGraph replay per recurring batch shape (graphed_update.py)
@@ -248,13 +272,23 @@ class SAC:
         # RESEL_DEVICE_COLLECT (read here) switches it, every other run keeps the host loop below
         from ..utility.device_collect import DeviceCollector
         why = DeviceCollector.refusal(self)
-        self.collector = None if why else DeviceCollector(self)
+        # a resumed run captures its graphs at points where the uninterrupted run captured nothing: those captures keep out of the
+        # random streams (run_state.generators_kept)
+        self.collector = None if why else DeviceCollector(self, keep_generators=resumed)
         if why and not self._collect_refusal_logged:
             self.logger(f'training episodes are collected through the host loop ({why})')
             self._collect_refusal_logged = True
+        # a state taken inside an episode: the host loop below finishes that episode (bit for bit the device path), its `env_reset()` is
+        # where the collector starts; taken behind `env_reset()`, the collector starts at once
+        self._host_episode_open = resumed and self.collector is not None and self.ep_len > 0
+        self._collecting = True
         try:
-            self._train_loop(update)
+            if resumed and self.graph_step is not None and (self.collector is None or self._host_episode_open):
+                with run_state.generators_kept(self.sample_device):
+                    self.graph_step.capture(self.obs_dim, self.act_dim)
+            self._train_loop(update, self.iteration if resumed else 0, ckpt)
         finally:
+            self._collecting = False
             if self.collector is not None:      # rollout mirrors, environment fields and the B = 1 step's state as the host loop leaves them
                 self.collector.sync_host()
             if graphed is not None:             # detach the process-wide dropout base: later eager trainers of this process draw from torch's generator again
@@ -278,36 +312,40 @@ class SAC:
             raise RuntimeError(f'SAC.evaluate: {why}')
         n = self.parameter.test_nprocess * self.parameter.test_nrollout
         if self.evaluator is None:
-            from ..utility.policy_eval import BatchedPolicyEval
-            self.evaluator = BatchedPolicyEval(self.policy, lambda: make_env(self.env_name, self.env_info['seed'])['eval_env'], self.act_dim,
-                                               min(n, 64), self.sample_device, seed=self.parameter.seed,
-                                               eval_tasks=self.env_info.get('eval_tasks'), discrete=self.discrete_env)
+            self.evaluator = self._make_evaluator()
         return self.evaluator.evaluate(n)
 
-    def _train_loop(self, update):
-        ep_ret, ep_len = 0.0, 0
+    def _make_evaluator(self):
+        from ..utility.policy_eval import BatchedPolicyEval
+        n = self.parameter.test_nprocess * self.parameter.test_nrollout
+        return BatchedPolicyEval(self.policy, lambda: make_env(self.env_name, self.env_info['seed'])['eval_env'], self.act_dim,
+                                 min(n, 64), self.sample_device, seed=self.parameter.seed,
+                                 eval_tasks=self.env_info.get('eval_tasks'), discrete=self.discrete_env)
+
+    def _train_loop(self, update, first_iteration=0, ckpt=None):
         why_no_eval = self.eval_refusal()
         if why_no_eval and not self._eval_refusal_logged:
             self.logger(f'the policy is not evaluated during training ({why_no_eval})')
             self._eval_refusal_logged = True
-        for it in range(self.parameter.total_iteration):
+        for it in range(first_iteration, self.parameter.total_iteration):
             test_log = None if why_no_eval else self.evaluate()   # the policy at the start of the iteration (reference :284-300)
             self.policy.train()
             self.policy.to(self.sample_device)
             for _ in range(self.parameter.step_per_iteration):
-                if self.collector is not None:                    # the same iteration inside the step's graph; an episode's last step pushes and logs it
+                if self.collector is not None and not self._host_episode_open:   # the same iteration inside the step's graph; an episode's last step pushes and logs it
                     self.collector.collect_step()
                 else:
                     act_sample = self.sample_action()
                     act_env = unorm_act(act_sample[0], self.env.action_space)
                     next_state, reward, done, _ = self.env.step(int(np.asarray(act_env).reshape(-1)[0]) if self.discrete_env else act_env)
-                    ep_ret += reward
-                    ep_len += 1
-                    self._push(act_sample, next_state, reward, done, ep_len)
+                    self.ep_ret += reward
+                    self.ep_len += 1
+                    self._push(act_sample, next_state, reward, done, self.ep_len)
                     self.env_step(next_state, act_sample, reward, done)
                     if done:
-                        self.logger.add_tabular_data(tb_prefix='Train', EpRet=ep_ret, EpLength=ep_len)
-                        ep_ret, ep_len = 0.0, 0
+                        self.logger.add_tabular_data(tb_prefix='Train', EpRet=self.ep_ret, EpLength=self.ep_len)
+                        self.ep_ret, self.ep_len = 0.0, 0
+                        self._host_episode_open = False           # (a resumed run: the collector, when there is one, takes over behind this `env_reset()`)
                 if self.sample_num % self.parameter.update_interval == 0 and self.sample_num >= self.parameter.start_train_num:
                     self.logger.add_tabular_data(tb_prefix='train', **update())
                     self.grad_num += 1
@@ -321,6 +359,9 @@ class SAC:
             self.logger.dump_tabular()
             if it % 25 == 0:
                 self.save()
+            self.iteration = it + 1
+            if ckpt is not None and (it + 1) % ckpt[1] == 0:
+                run_state.write_checkpoint(ckpt[0], it + 1, self.save_state)
 
     # ------------------------------------------------------------------------------------------ checkpoints
     def save(self, model_dir=None):
@@ -346,3 +387,138 @@ class SAC:
         # in place: optimizer_alpha holds this tensor (rebinding it, as the reference does, silently freezes the temperature)
         with torch.no_grad():
             self.log_sac_alpha.copy_(torch.load(os.path.join(path, 'log_sac_alpha.pt'), map_location=self.device))
+
+    # ------------------------------------------------------------------------------------------ run state (algorithm/run_state.py)
+    def _state_networks(self):
+        nets = {'policy': self.policy}
+        for i, (value, target) in enumerate(zip(self.values, self.target_values)):
+            nets[f'value{i}'], nets[f'target_value{i}'] = value, target
+        if getattr(self, 'target_policy', None) is not None:      # the full-trajectory trainers; TD3 updates it
+            nets['target_policy'] = self.target_policy
+        return nets
+
+    def _state_optimizers(self):
+        return dict({'policy': self.optimizer_policy}, **{f'value{i}': opt for i, opt in enumerate(self.optimizers_value)})
+
+    def state_fingerprint(self) -> dict:
+        """What must be equal between the trainer that wrote a run state and the one that loads it; a mismatch names its key."""
+        p, ring = self.parameter, self.replay_buffer
+        out = dict(env_name=p.env_name, alg_name=p.alg_name, base_algorithm=self.base_algorithm, seed=int(p.seed), obs_dim=int(self.obs_dim),
+                   act_dim=int(self.act_dim), trainer=type(self).__name__)
+        for which in ('policy', 'value'):
+            for key in ('embedding_layer_type', 'embedding_hidden_size', 'layer_type', 'hidden_size'):
+                out[f'{which}_{key}'] = list(getattr(p, f'{which}_{key}'))
+        for name, net in self._state_networks().items():
+            out[f'numel_{name}'] = int(net.store.numel)
+        has_layout = ring.memory_buffer is not None               # (fixed by the first trajectory: a fresh trainer has none to compare)
+        out['ring_width'] = int(ring.width) if has_layout else None
+        out['ring_name2range'] = {k: list(v) for k, v in ring.name2range.items()} if has_layout else None
+        return out
+
+    def _collect_state(self):
+        """-> (manifest, host payload, tensor payload) of this trainer as it stands (the ring goes separately).  Reads only."""
+        dev, cuda = self.sample_device, self.sample_device.type == 'cuda'
+        if cuda:
+            torch.cuda.synchronize(dev)
+        cpu = lambda t: t.detach().cpu().clone()
+        ev = self.evaluator
+        subset_rng = getattr(self, '_subset_rng', None)
+        host = dict(
+            python_random=random.getstate(), numpy_random=np.random.get_state(),
+            subset_rng=None if subset_rng is None else subset_rng.get_state(),
+            env=self.env, state_np=self.state_np, last_state_np=self.last_state_np, last_action_np=self.last_action_np, reward_np=self.reward_np,
+            ep_ret=self.ep_ret, ep_len=self.ep_len, sample_num=self.sample_num, grad_num=self.grad_num, iteration=self.iteration,
+            elapsed=time.time() - self.start_time, pending=list(self.replay_buffer.memory),
+            optimizer_steps={name: opt.step_count for name, opt in self._state_optimizers().items()},
+            evaluator=None if ev is None else dict(rs=ev.rs.get_state(), env_seeds=list(ev.env_seeds), envs=ev.envs))
+        hidden = self.graph_step._hidden if self.graph_step is not None else self.sample_hidden
+        tensors = dict(
+            stores={name: cpu(net.store.flat) for name, net in self._state_networks().items()},
+            moments={name: dict(m=cpu(opt.m), v=cpu(opt.v)) for name, opt in self._state_optimizers().items()},
+            log_sac_alpha=cpu(self.log_sac_alpha), optimizer_alpha=self.optimizer_alpha.state_dict(),
+            q_guard=cpu(self.Q_guard.state) if hasattr(self, 'Q_guard') else None,
+            torch_cpu_rng=torch.get_rng_state(), device_rng=torch.cuda.get_rng_state(dev) if cuda else None,
+            hidden=run_state.hidden_to_host(hidden))
+        manifest = dict(iteration=self.iteration, sample_num=self.sample_num, grad_num=self.grad_num, fingerprint=self.state_fingerprint())
+        return manifest, host, tensors
+
+    def save_state(self, path):
+        """The whole run state into the directory `path` (algorithm/run_state.py): networks, optimizers, guard, counters, the ring's
+        occupied rows, every random stream, the environment, the open episode with its recurrent state, the evaluator.  The trainer goes
+        on afterwards exactly as if nothing had been written.  `save()` is something else: the reference's model files."""
+        run_state.refuse_process_groups()
+        ring = self.replay_buffer
+        live = self._collecting and self.collector is not None    # the open episode is on the device: fetch the host loop's view of it
+        pending = ring.memory
+        try:
+            if live:
+                self.collector.sync_host()
+            manifest, host, tensors = self._collect_state()
+            return run_state.write_state(path, manifest, ring, host, tensors)
+        finally:
+            if live:                                              # `sync_host()` left the episode's transitions pending: `push_rows` would refuse
+                ring.memory = pending
+
+    def load_state(self, path):
+        """A state that `save_state` wrote, into a trainer built from the same `Parameter`: afterwards this trainer is the one that
+        wrote it.  Everything is read and checked before anything is touched; `run_state.RunStateMismatch` names what does not fit."""
+        run_state.refuse_process_groups()
+        manifest, ring_st, host, tensors = run_state.read_state(path)
+        current = self.state_fingerprint()
+        run_state.check_fingerprint(manifest['fingerprint'], current)
+        nets, opts = self._state_networks(), self._state_optimizers()
+        for name, net in nets.items():                            # (the fingerprint compared the sizes; the payload itself)
+            if tensors['stores'][name].shape != net.store.flat.shape:
+                raise run_state.RunStateMismatch(f'stores[{name}].shape', tuple(tensors['stores'][name].shape), tuple(net.store.flat.shape))
+        if set(host['optimizer_steps']) != set(opts) or (tensors['q_guard'] is None) != (not hasattr(self, 'Q_guard')):
+            raise run_state.RunStateMismatch('optimizers', sorted(host['optimizer_steps']), sorted(opts))
+        self._apply_state(ring_st, host, tensors)
+
+    @torch.no_grad()
+    def _apply_state(self, ring_st, host, tensors):
+        dev, cuda = self.sample_device, self.sample_device.type == 'cuda'
+        for name, net in self._state_networks().items():          # in place: parameters, optimizers and graphs hold these buffers
+            net.store.flat.copy_(tensors['stores'][name])
+            net.store._amax = None
+        for name, opt in self._state_optimizers().items():
+            opt.m.copy_(tensors['moments'][name]['m'])
+            opt.v.copy_(tensors['moments'][name]['v'])
+            opt.step_count = int(host['optimizer_steps'][name])
+        self.log_sac_alpha.copy_(tensors['log_sac_alpha'])
+        self.optimizer_alpha.load_state_dict(tensors['optimizer_alpha'])
+        if tensors['q_guard'] is not None:
+            self.Q_guard.state.copy_(tensors['q_guard'])
+        self.sample_num, self.grad_num, self.iteration = int(host['sample_num']), int(host['grad_num']), int(host['iteration'])
+        self.start_time = time.time() - float(host['elapsed'])
+        run_state.load_ring(self.replay_buffer, ring_st, host['pending'])
+        self.env.__dict__.clear()                                 # in place: `env_info` and whoever else holds the object see the loaded one
+        self.env.__dict__.update(host['env'].__dict__)
+        self.state_np, self.last_state_np = host['state_np'], host['last_state_np']
+        self.last_action_np, self.reward_np = host['last_action_np'], host['reward_np']
+        self.ep_ret, self.ep_len = host['ep_ret'], int(host['ep_len'])
+        saved_hidden = tensors['hidden']
+        if saved_hidden is not None:
+            # `sample_hidden` is what `env_reset()` made; behind a reset it equals the step's state, and nobody reads it elsewhere
+            self.sample_hidden = self.policy.make_init_state(1, dev)
+            run_state.hidden_from_host(self.sample_hidden, saved_hidden, dev, in_place=False)
+            if self.graph_step is not None:
+                self.graph_step.load_hidden(None)
+                run_state.hidden_from_host(self.graph_step._hidden, saved_hidden, dev, in_place=True)
+                if any(tag == 'kv' for tag, _ in saved_hidden):   # the KV caches are new tensors: a graph captured earlier reads the old ones
+                    self.graph_step.invalidate()
+        ev = host['evaluator']
+        self.evaluator = None
+        if ev is not None:                                        # the evaluator continues its private streams instead of drawing new seeds
+            self.evaluator = self._make_evaluator()
+            self.evaluator.rs.set_state(ev['rs'])
+            self.evaluator.env_seeds, self.evaluator.envs = list(ev['env_seeds']), ev['envs']
+        if hasattr(self, '_subset_rng'):
+            self._subset_rng = None
+            if host['subset_rng'] is not None:
+                self._subset_rng = np.random.RandomState()
+                self._subset_rng.set_state(host['subset_rng'])
+        random.setstate(host['python_random'])
+        np.random.set_state(host['numpy_random'])
+        torch.set_rng_state(tensors['torch_cpu_rng'])
+        if cuda and tensors['device_rng'] is not None:
+            torch.cuda.set_rng_state(tensors['device_rng'], dev)

@@ -52,9 +52,12 @@ class DeviceCollector:
             return 'the ring has no column layout yet (no warm-up trajectory)'
         return None
 
-    def __init__(self, alg):
+    def __init__(self, alg, keep_generators: bool = False):
+        """keep_generators: the capture in `_begin` leaves every random stream as it found it - a run resumed from a run state
+        (algorithm/run_state.py) captures where the uninterrupted run, which captured at its first step, draws nothing."""
         from ..hip.graph_step import GraphedPolicyStep
         self.alg, self.env, self.device = alg, alg.env, alg.sample_device
+        self.keep_generators = bool(keep_generators)
         self.kind = kind = device_env_kind(self.env)
         self.cfg = self.env.device_config()
         self.T, self.obs_dim, self.act_dim = kind.episode_length(self.cfg), kind.obs_dim, kind.act_dim
@@ -101,7 +104,12 @@ class DeviceCollector:
         stopped row, so they see the zero input block the host loop's capture sees), then the episode `env_reset()` began."""
         assert self.kind.behind_reset(self.env), 'the collector starts behind env_reset()'
         self.step.load_hidden(self.alg.sample_hidden)
-        self.step.capture(self.obs_dim, self.act_dim)
+        if self.keep_generators:
+            from ..algorithm.run_state import generators_kept
+            with generators_kept(self.device):
+                self.step.capture(self.obs_dim, self.act_dim)
+        else:
+            self.step.capture(self.obs_dim, self.act_dim)
         self._counters = self.step._counters()
         self._init_episode(self.kind.current_payload(self.env))
         self.started = True
@@ -138,12 +146,15 @@ class DeviceCollector:
     # ------------------------------------------------------------------------------------------ back to the host loop's state
     @torch.no_grad()
     def sync_host(self):
-        """On return from `train()`: the trainer's rollout mirrors, the environment object's fields, the B = 1 step's recurrent state
-        and the ring's pending transitions (the open episode) hold what the host loop would have left there."""
+        """On return from `train()`: the trainer's rollout mirrors, the environment object's fields, the B = 1 step's recurrent state,
+        the open episode's running return and length and the ring's pending transitions (that episode) hold what the host loop would
+        have left there.  The collector itself is not changed: it may go on afterwards, once the pending transitions are taken out of the
+        ring again (`SAC.save_state`)."""
         if not self.started:
             return
         alg, env, o, a = self.alg, self.env, self.obs_dim, self.act_dim
         row = self.step._in_dev[0].cpu().numpy()            # (synchronises)
+        alg.ep_ret, alg.ep_len = float(self._ret.cpu()[0]), self.t
         state, last_state, last_action = self.kind.sync_env(env, self._env_state, row, o, a)
         alg.state_np = state
         if self.t == 0:                                    # behind `env_reset()`
