@@ -11,13 +11,28 @@ import torch
 from . import tmaze, wind
 
 
-class TMazeKind:
+class DeviceEnvKind:
+    """What the records share.  Every kernel keeps three consecutive int32 next to its environment's own state - steps of the episode,
+    episodes started, running (csrc/env_step.hip `BLEN`, `BSTARTED`, `BRUNNING`) - at byte `book_offset` of a row's state."""
+
+    @staticmethod
+    def episode_length(cfg) -> int:
+        return int(cfg['episode_length'])
+
+    @classmethod
+    def finished(cls, state_np):
+        """state_np: the row's state bytes on the host -> (steps taken, still running)."""
+        book = state_np[cls.book_offset:cls.book_offset + 12].view(np.int32)
+        return int(book[0]), bool(book[2])
+
+
+class TMazeKind(DeviceEnvKind):
     """Discrete T-Maze (env_utils/tmaze.py): int32 words x, y, goal_y, oracle_visited, t, ep_len, episodes_started, running."""
     obs_dim, act_dim = 2, 4
     categorical, policy_words = True, 'a categorical one'
     state_bytes = 4 * 8
     payload_dtype, payload_np, payload_width = torch.int32, np.int32, 1
-    SLEN, SRUNNING = 5, 7
+    book_offset = 4 * 5
 
     @staticmethod
     def steps(env) -> bool:
@@ -26,10 +41,6 @@ class TMazeKind:
     @staticmethod
     def policy_ok(policy) -> bool:
         return bool(getattr(policy, 'categorical', False))
-
-    @staticmethod
-    def episode_length(cfg) -> int:
-        return int(cfg['episode_length'])
 
     @staticmethod
     def action(out_dev, sampled: bool):
@@ -78,12 +89,6 @@ class TMazeKind:
         alg.env.goal_y = alg.env.draw_goal()
         return (alg.env.goal_y,)
 
-    @classmethod
-    def finished(cls, state_np):
-        """state_np: the row's state bytes on the host -> (steps taken, still running)."""
-        words = state_np.view(np.int32)
-        return int(words[cls.SLEN]), bool(words[cls.SRUNNING])
-
     @staticmethod
     def sync_env(env, state, row, o, a):
         """The environment object's fields from the device state; -> (state_np, last_state_np, last_action_np) as the host loop holds them
@@ -93,13 +98,13 @@ class TMazeKind:
         return (row[:o].copy().reshape(1, -1), row[o:2 * o].copy().reshape(1, -1), row[2 * o:2 * o + a].astype(np.float64).reshape(1, -1))
 
 
-class WindKind:
+class WindKind(DeviceEnvKind):
     """Wind-v0 (env_utils/wind.py): doubles x, y, wind_x, wind_y, last_x, last_y, then int32 words clock, ep_len, episodes_started, running."""
     obs_dim, act_dim = 2, 2
     categorical, policy_words = False, 'a tanh-Gaussian SAC one'
     state_bytes = 8 * 6 + 4 * 4
     payload_dtype, payload_np, payload_width = torch.float64, np.float64, 2
-    WLEN, WRUNNING = 1, 3
+    book_offset = 8 * 6 + 4 * 1
 
     @staticmethod
     def steps(env) -> bool:
@@ -108,10 +113,6 @@ class WindKind:
     @staticmethod
     def policy_ok(policy) -> bool:                           # (TD3's deterministic policy with clipped noise keeps the host loop)
         return not bool(getattr(policy, 'categorical', False)) and not hasattr(policy, 'sample_std')
-
-    @staticmethod
-    def episode_length(cfg) -> int:
-        return int(cfg['episode_length'])
 
     @staticmethod
     def action(out_dev, sampled: bool):
@@ -153,11 +154,6 @@ class WindKind:
         """`env_reset()`'s draw for the next training episode: one task from the global numpy stream."""
         alg.env.reset(alg.draw_train_task())
         return tuple(alg.env.get_current_task())
-
-    @classmethod
-    def finished(cls, state_np):
-        words = state_np[48:].view(np.int32)
-        return int(words[cls.WLEN]), bool(words[cls.WRUNNING])
 
     @staticmethod
     def sync_env(env, state, row, o, a):

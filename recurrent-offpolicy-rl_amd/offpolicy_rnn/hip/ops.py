@@ -2270,6 +2270,64 @@ def categorical_step(logits, u, floor=0.01, out=None):
     return mode, sample, logp
 
 
+# ---- environment steps inside the graphed policy step (csrc/env_step.hip): what the entries of every environment check alike ----------
+def _env_rows(what, B, A, action, action_width, ret_acc, in_block):
+    """The blocks every entry takes: action fp32 [B] (action_width 1) or [B, action_width], unit column stride, any row stride; ret_acc
+    fp64 [B]; in_block fp32 [B, >= 2 * 2 + A + 1], unit column stride (A: the width of lst_action).  -> (ld_action, ld_in)."""
+    assert action.dtype == torch.float32 and (action.shape == (B,) if action_width == 1 else
+                                              action.shape == (B, action_width) and action.stride(1) == 1), f'{what}: the action view'
+    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
+    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
+    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
+    return max(action.stride(0), action_width), max(in_block.stride(0), 2 * 2 + A + 1)
+
+
+def _env_eval_tables(B, flags, n_episodes, ep_ret, ep_len):
+    """The tables of an evaluation: flags / n_episodes int32 [B], ep_ret fp64 / ep_len int32 [B, J], all contiguous.  -> J."""
+    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous() and flags.numel() == B
+    assert n_episodes.dtype == torch.int32 and n_episodes.is_contiguous() and n_episodes.numel() == B
+    assert ep_ret.dtype == torch.float64 and ep_len.dtype == torch.int32 and ep_ret.dim() == 2 and ep_ret.shape == ep_len.shape
+    assert ep_ret.shape[0] == B and ep_ret.is_contiguous() and ep_len.is_contiguous()
+    return ep_ret.shape[1]
+
+
+def _env_episode_block(B, traj):
+    """The episode block of a rollout, fp32 [B, T_cap, width] with unit column stride.  -> (T_cap, ld_row)."""
+    assert traj.dtype == torch.float32 and traj.dim() == 3 and traj.shape[0] == B and traj.shape[1] >= 1 and traj.shape[2] >= 1
+    T_cap, ld_row = traj.shape[1], traj.stride(1) if traj.shape[1] > 1 else max(traj.stride(1), traj.shape[2])
+    assert traj.stride(2) == 1 and ld_row >= traj.shape[2] and (B <= 1 or traj.stride(0) == T_cap * ld_row), 'rows of one episode block'
+    return T_cap, ld_row
+
+
+def _collect_layout(what, name2range, widths, ring_width):
+    """`MemoryArray.name2range` -> the `CollectLayout`: first columns, -1 for an empty range.  widths: of the fields not one column wide."""
+    from ._lib import COLLECT_FIELDS, CollectLayout
+    lay = CollectLayout()
+    for name in COLLECT_FIELDS:
+        a, b = name2range[name]
+        if b > a:
+            assert b - a == widths.get(name, 1) and a >= 0, f'{what}: field {name} is {b - a} wide in the ring'
+            assert b <= ring_width, f'{what}: field {name} ends at column {b} of {ring_width}'
+        setattr(lay, name, a if b > a else -1)
+    return lay
+
+
+def _tmaze_cfg(cfg: dict, B, env_state):
+    """`TMaze.device_config()` -> the entries' cfg struct, behind the check of the environment's state block."""
+    from ._lib import TMAZE_STATE_WORDS, TMazeCfg
+    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, TMAZE_STATE_WORDS)
+    return TMazeCfg(int(cfg['corridor_length']), int(cfg['oracle_length']), int(cfg['episode_length']), float(cfg['goal_reward']),
+                    float(cfg['penalty']), float(cfg['distract_reward']))
+
+
+def _wind_cfg(cfg: dict, B, env_pos, env_words):
+    """`Wind.device_config()` -> the entries' cfg struct, behind the check of the environment's two state blocks."""
+    from ._lib import WIND_CFG_DOUBLES, WIND_STATE_DOUBLES, WIND_STATE_WORDS, WindCfg
+    assert env_pos.dtype == torch.float64 and env_pos.is_contiguous() and env_pos.shape == (B, WIND_STATE_DOUBLES)
+    assert env_words.dtype == torch.int32 and env_words.is_contiguous() and env_words.shape == (B, WIND_STATE_WORDS)
+    return WindCfg(int(cfg['episode_length']), *[float(cfg[name]) for name in WIND_CFG_DOUBLES])
+
+
 @torch.no_grad()
 def tmaze_step(cfg: dict, init: bool, action, goals, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags):
     """One T-Maze environment step (or, init: the start of an evaluation) for the B rows of a graphed policy step, as one launch:
@@ -2278,27 +2336,16 @@ def tmaze_step(cfg: dict, init: bool, action, goals, n_episodes, env_state, ret_
     goals int32 [B, J], n_episodes int32 [B] (each at most J), env_state int32 [B, 8], ret_acc fp64 [B], ep_ret fp64 / ep_len int32 [B, J];
     in_block fp32 [B, >= 9] with unit column stride (state[2] | lst_state[2] | lst_action[4] | reward[1]), flags int32 [B].
     Everything is updated in place; nothing else on the stream, no host read, no allocation: capturable."""
-    from ._lib import TMAZE_STATE_WORDS, TMazeCfg
     _need_cuda('tmaze_step', action, goals, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags)
     B, A = flags.numel(), 4
-    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
-    assert action.dtype == torch.float32 and action.dim() == 1 and action.numel() == B
-    assert goals.dtype == torch.int32 and goals.dim() == 2 and goals.shape[0] == B and (goals.stride(1) == 1 or goals.shape[1] == 1)
-    J = goals.shape[1]
-    assert n_episodes.dtype == torch.int32 and n_episodes.is_contiguous() and n_episodes.numel() == B
-    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, TMAZE_STATE_WORDS)
-    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
-    assert ep_ret.dtype == torch.float64 and ep_len.dtype == torch.int32 and ep_ret.shape == ep_len.shape == (B, J)
-    assert ep_ret.is_contiguous() and ep_len.is_contiguous()
-    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
-    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
+    ld_action, ld_in = _env_rows('tmaze_step', B, A, action, 1, ret_acc, in_block)
+    J = _env_eval_tables(B, flags, n_episodes, ep_ret, ep_len)
+    assert goals.dtype == torch.int32 and goals.shape == (B, J) and (goals.stride(1) == 1 or J == 1)
+    c = _tmaze_cfg(cfg, B, env_state)
     if B == 0:                                           # empty tensors have no address to hand over
         return
-    c = TMazeCfg(int(cfg['corridor_length']), int(cfg['oracle_length']), int(cfg['episode_length']), float(cfg['goal_reward']),
-                 float(cfg['penalty']), float(cfg['distract_reward']))
-    check(lib().resel_tmaze_step(c, int(bool(init)), _p(action), max(action.stride(0), 1), _p(goals), max(goals.stride(0), J),
-                                 _p(n_episodes), J, _p(env_state), _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block),
-                                 max(in_block.stride(0), 2 * 2 + A + 1), A, _p(flags), B, _stream()), 'tmaze_step')
+    check(lib().resel_tmaze_step(c, int(bool(init)), _p(action), ld_action, _p(goals), max(goals.stride(0), J), _p(n_episodes), J,
+                                 _p(env_state), _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block), ld_in, A, _p(flags), B, _stream()), 'tmaze_step')
 
 
 @torch.no_grad()
@@ -2310,51 +2357,17 @@ def tmaze_collect_step(cfg: dict, name2range: dict, init: bool, action, goal, en
     action: fp32 [B] view, any stride - the SAMPLED indices (column 1 of the categorical step's output block); goal int32 [B];
     env_state int32 [B, 8], ret_acc fp64 [B]; traj fp32 [B, T_cap, >= the layout's width] with unit column stride: the episode block;
     in_block fp32 [B, >= 9] with unit column stride.  Everything is updated in place; no host read, no allocation: capturable."""
-    from ._lib import COLLECT_FIELDS, TMAZE_STATE_WORDS, CollectLayout, TMazeCfg
     _need_cuda('tmaze_collect_step', action, goal, env_state, ret_acc, traj, in_block)
     B, A = goal.numel(), 4
     assert goal.dtype == torch.int32 and goal.dim() == 1 and goal.is_contiguous()
-    assert action.dtype == torch.float32 and action.dim() == 1 and action.numel() == B
-    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, TMAZE_STATE_WORDS)
-    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
-    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
-    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
-    assert traj.dtype == torch.float32 and traj.dim() == 3 and traj.shape[0] == B and traj.shape[1] >= 1 and traj.shape[2] >= 1
-    T_cap, ld_row = traj.shape[1], traj.stride(1) if traj.shape[1] > 1 else max(traj.stride(1), traj.shape[2])
-    assert traj.stride(2) == 1 and ld_row >= traj.shape[2] and (B <= 1 or traj.stride(0) == T_cap * ld_row), 'rows of one episode block'
-    widths = dict(state=2, last_state=2, next_state=2, last_action=A, logp=0)
-    lay = CollectLayout()
-    for name in COLLECT_FIELDS:
-        a, b = name2range[name]
-        if b > a:
-            assert b - a == widths.get(name, 1) and a >= 0, f'tmaze_collect_step: field {name} is {b - a} wide in the ring'
-            assert b <= traj.shape[2], f'tmaze_collect_step: field {name} ends at column {b} of {traj.shape[2]}'
-        setattr(lay, name, a if b > a else -1)
+    ld_action, ld_in = _env_rows('tmaze_collect_step', B, A, action, 1, ret_acc, in_block)
+    c = _tmaze_cfg(cfg, B, env_state)
+    T_cap, ld_row = _env_episode_block(B, traj)
+    lay = _collect_layout('tmaze_collect_step', name2range, dict(state=2, last_state=2, next_state=2, last_action=A, logp=0), traj.shape[2])
     if B == 0:                                           # empty tensors have no address to hand over
         return
-    c = TMazeCfg(int(cfg['corridor_length']), int(cfg['oracle_length']), int(cfg['episode_length']), float(cfg['goal_reward']),
-                 float(cfg['penalty']), float(cfg['distract_reward']))
-    check(lib().resel_tmaze_collect_step(c, lay, int(bool(init)), _p(action), max(action.stride(0), 1), _p(goal), _p(env_state), _p(ret_acc),
-                                         _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block), max(in_block.stride(0), 2 * 2 + A + 1),
-                                         A, B, _stream()), 'tmaze_collect_step')
-
-
-def _wind_cfg(cfg: dict):
-    from ._lib import WIND_CFG_DOUBLES, WindCfg
-    return WindCfg(int(cfg['episode_length']), *[float(cfg[name]) for name in WIND_CFG_DOUBLES])
-
-
-def _wind_common(what, B, action, env_pos, env_words, ret_acc, in_block):
-    """The argument checks the two Wind entries share -> the action's row stride."""
-    from ._lib import WIND_STATE_DOUBLES, WIND_STATE_WORDS
-    A = 2
-    assert action.dtype == torch.float32 and action.shape == (B, A) and (action.stride(1) == 1), f'{what}: action is fp32 [B, 2], unit column stride'
-    assert env_pos.dtype == torch.float64 and env_pos.is_contiguous() and env_pos.shape == (B, WIND_STATE_DOUBLES)
-    assert env_words.dtype == torch.int32 and env_words.is_contiguous() and env_words.shape == (B, WIND_STATE_WORDS)
-    assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
-    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
-    assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
-    return max(action.stride(0), A)
+    check(lib().resel_tmaze_collect_step(c, lay, int(bool(init)), _p(action), ld_action, _p(goal), _p(env_state), _p(ret_acc), _p(traj), T_cap,
+                                         ld_row, int(max_episode_steps), _p(in_block), ld_in, A, B, _stream()), 'tmaze_collect_step')
 
 
 @torch.no_grad()
@@ -2367,18 +2380,14 @@ def wind_step(cfg: dict, init: bool, action, winds, n_episodes, env_pos, env_wor
     flags int32 [B].  Everything is updated in place; nothing else on the stream, no host read, no allocation: capturable."""
     _need_cuda('wind_step', action, winds, n_episodes, env_pos, env_words, ret_acc, ep_ret, ep_len, in_block, flags)
     B, A = flags.numel(), 2
-    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
-    ld_action = _wind_common('wind_step', B, action, env_pos, env_words, ret_acc, in_block)
-    assert winds.dtype == torch.float64 and winds.dim() == 3 and winds.shape[0] == B and winds.shape[2] == 2 and winds.is_contiguous()
-    J = winds.shape[1]
-    assert n_episodes.dtype == torch.int32 and n_episodes.is_contiguous() and n_episodes.numel() == B
-    assert ep_ret.dtype == torch.float64 and ep_len.dtype == torch.int32 and ep_ret.shape == ep_len.shape == (B, J)
-    assert ep_ret.is_contiguous() and ep_len.is_contiguous()
+    ld_action, ld_in = _env_rows('wind_step', B, A, action, A, ret_acc, in_block)
+    J = _env_eval_tables(B, flags, n_episodes, ep_ret, ep_len)
+    assert winds.dtype == torch.float64 and winds.shape == (B, J, 2) and winds.is_contiguous()
+    c = _wind_cfg(cfg, B, env_pos, env_words)
     if B == 0:                                           # empty tensors have no address to hand over
         return
-    check(lib().resel_wind_step(_wind_cfg(cfg), int(bool(init)), _p(action), ld_action, _p(winds), 2 * J, _p(n_episodes), J, _p(env_pos),
-                                _p(env_words), _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block), max(in_block.stride(0), 2 * 2 + A + 1),
-                                A, _p(flags), B, _stream()), 'wind_step')
+    check(lib().resel_wind_step(c, int(bool(init)), _p(action), ld_action, _p(winds), 2 * J, _p(n_episodes), J, _p(env_pos), _p(env_words),
+                                _p(ret_acc), _p(ep_ret), _p(ep_len), J, _p(in_block), ld_in, A, _p(flags), B, _stream()), 'wind_step')
 
 
 @torch.no_grad()
@@ -2390,28 +2399,18 @@ def wind_collect_step(cfg: dict, name2range: dict, init: bool, action, wind, env
     (columns 2:4 of the Gaussian head's output block); wind fp64 [B, 2]; env_pos fp64 [B, 6], env_words int32 [B, 4], ret_acc fp64 [B];
     traj fp32 [B, T_cap, >= the layout's width] with unit column stride: the episode block; in_block fp32 [B, >= 7] with unit column stride.
     Everything is updated in place; no host read, no allocation: capturable."""
-    from ._lib import COLLECT_FIELDS, CollectLayout
     _need_cuda('wind_collect_step', action, wind, env_pos, env_words, ret_acc, traj, in_block)
-    A = 2
     assert wind.dtype == torch.float64 and wind.dim() == 2 and wind.shape[1] == 2 and wind.is_contiguous()
-    B = wind.shape[0]
-    ld_action = _wind_common('wind_collect_step', B, action, env_pos, env_words, ret_acc, in_block)
-    assert traj.dtype == torch.float32 and traj.dim() == 3 and traj.shape[0] == B and traj.shape[1] >= 1 and traj.shape[2] >= 1
-    T_cap, ld_row = traj.shape[1], traj.stride(1) if traj.shape[1] > 1 else max(traj.stride(1), traj.shape[2])
-    assert traj.stride(2) == 1 and ld_row >= traj.shape[2] and (B <= 1 or traj.stride(0) == T_cap * ld_row), 'rows of one episode block'
+    B, A = wind.shape[0], 2
+    ld_action, ld_in = _env_rows('wind_collect_step', B, A, action, A, ret_acc, in_block)
+    c = _wind_cfg(cfg, B, env_pos, env_words)
+    T_cap, ld_row = _env_episode_block(B, traj)
     widths = dict(state=2, last_state=2, next_state=2, last_action=A, action=A, logp=0)
-    lay = CollectLayout()
-    for name in COLLECT_FIELDS:
-        a, b = name2range[name]
-        if b > a:
-            assert b - a == widths.get(name, 1) and a >= 0, f'wind_collect_step: field {name} is {b - a} wide in the ring'
-            assert b <= traj.shape[2], f'wind_collect_step: field {name} ends at column {b} of {traj.shape[2]}'
-        setattr(lay, name, a if b > a else -1)
+    lay = _collect_layout('wind_collect_step', name2range, widths, traj.shape[2])
     if B == 0:                                           # empty tensors have no address to hand over
         return
-    check(lib().resel_wind_collect_step(_wind_cfg(cfg), lay, int(bool(init)), _p(action), ld_action, _p(wind), _p(env_pos), _p(env_words),
-                                        _p(ret_acc), _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block),
-                                        max(in_block.stride(0), 2 * 2 + A + 1), A, B, _stream()), 'wind_collect_step')
+    check(lib().resel_wind_collect_step(c, lay, int(bool(init)), _p(action), ld_action, _p(wind), _p(env_pos), _p(env_words), _p(ret_acc),
+                                        _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block), ld_in, A, B, _stream()), 'wind_collect_step')
 
 
 @torch.no_grad()
