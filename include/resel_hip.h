@@ -731,6 +731,43 @@ int resel_wind_collect_step(resel_wind_cfg_t cfg, resel_collect_layout_t lay, in
                             const double* wind, double* env_pos, int32_t* env_words, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream);
 
+/* ---- Catch-<runs>-v0 (reference envs/credit_assign/catch.py DelayedCatch; host twin env_utils/catch.py): the T-Maze pair of entries
+ * for the delayed-reward task.  Same shape - the LAST node of a graphed policy step, one thread per row, 64-thread blocks, no LDS, no
+ * atomics, no allocation, nothing read from the host: capturable - and the same episode handling; what differs is the state, the
+ * payload of an episode (a table of draws) and the widths: A = 3 actions, a 49-wide observation.
+ *   cfg: num_catches runs of 7 steps (6 falling steps, then - except behind the last run - one soft-reset step);
+ *     episode_length = 7 * num_catches - 1.
+ *   action: the fp32 action index of row b at action[b * ld_action] (evaluation: column 0 of the categorical head's output block, the
+ *     mode; rollout: column 1, the sample), clamped into [0, 3) (NaN: 0); 0 / 1 / 2 move the basket left / not / right.
+ *   draws: one episode's payload is 2 * RESEL_CATCH_MAX_RUNS int32, the fruit columns ns[40] first, then the basket start columns
+ *     ms[40]; entries behind num_catches are not read by a step (the host sends zeros).  Evaluation: draws [B, J, 80] with row stride
+ *     ld_draws >= 80 J; rollout: draws [B, 80], read by init only.
+ *   env_state [B, RESEL_CATCH_STATE_WORDS] int32: fruit_row, fruit_col, basket, catch_count, t, accumulated, ep_len, episodes_started,
+ *     running, a pad word, ns[40], ms[40] - a reset copies the episode's draws into the row, a step never reads the payload.
+ *   in_block rows: state[49] | lst_state[49] | lst_action[3] | reward[1]  (ld_in >= 102).  The observation is the flattened 7 x 7
+ *     canvas: -1 at (fruit_row, fruit_col), then +1 at (6, basket), everything else 0; a caught fruit is covered by the basket.
+ * A step: t += 1.  fruit_row == 6 (the steps t = 7 k): the action is ignored, (fruit_row, fruit_col, basket) <- (0, ns[c], ms[c]) with
+ *   c = catch_count clamped into [0, num_catches), catch_count <- c + 1, reward 0, not done.  Otherwise basket <- clip(basket + a - 1,
+ *   0, 6), fruit_row += 1, accumulated += 1 when fruit_row == 6 and fruit_col == basket; done = t >= episode_length; the reward is
+ *   (double)accumulated on the done step and 0.0 before it.  Rows, columns and the count are clamped where they index: a corrupted
+ *   state word never becomes an access outside the row.
+ * The next input row: lst_state <- state, state <- the new observation, lst_action <- one-hot(a), reward <- (float)r.
+ * n_episodes, ret_acc, ep_ret, ep_len, flags, init, idle rows and the hand-over at an episode's end as in the T-Maze evaluation entry;
+ * traj, lay (widths: state, last_state, next_state 49; last_action 3; everything else 1; lay.logp = -1), T_cap, ld_row,
+ * max_episode_steps, init and stopped rows as in the T-Maze rollout entry.
+ * RESEL_EINVAL before the device is touched: a NULL pointer, A != 3, B < 0, ld_in < 102, ld_action < 1, num_catches < 1 or >
+ *   RESEL_CATCH_MAX_RUNS, episode_length != 7 * num_catches - 1; evaluation: J < 1, ld_draws < 80 J, ld_ep < J; rollout: T_cap < 1,
+ *   max_episode_steps < 1, lay.logp >= 0, ld_row smaller than the furthest end of a present field.  B == 0 launches nothing, returns 0. */
+#define RESEL_CATCH_MAX_RUNS 40
+#define RESEL_CATCH_STATE_WORDS 90
+typedef struct { int32_t num_catches, episode_length; } resel_catch_cfg_t;
+int resel_catch_step(resel_catch_cfg_t cfg, int init, const float* action, int64_t ld_action, const int32_t* draws, int64_t ld_draws,
+                     const int32_t* n_episodes, int J, int32_t* env_state, double* ret_acc, double* ep_ret, int32_t* ep_len,
+                     int64_t ld_ep, float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream);
+int resel_catch_collect_step(resel_catch_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                             const int32_t* draws, int32_t* env_state, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream);
+
 /* ---- discrete-action update: differentiable categorical head, all-action value, the two discrete losses --------------------
  * (reference contextual_sac_discrete_policy.py:106-121 on whole rows; sac_full_length_rnn_redq.py:52-72 target, :85-86 actor,
  * sac_full_length_rnn_ensembleQ.py:158 critic on the action taken).  Raw fp32 device pointers; logits / logp / probs [M, A];

@@ -4,12 +4,15 @@
 //   `eval_step_kernel`     the per-row body of the evaluation scheduler (utility/policy_eval.py `run_episodes` and its `begin()`);
 //   `collect_step_kernel`  the per-row body of one iteration of `SAC._train_loop`: the same step on the SAMPLED action, plus the
 //                          transition row the replay ring stores.
-// A record (`TMazeEnv`, `WindEnv`) holds what is specific to one environment - state, payload, action, arithmetic, widths - and no
-// scheduling.  One thread per row, 64-thread blocks, a few dozen scalar operations: latency of one launch, nothing to tune.
-// No LDS, no atomics, nothing read from the host, no allocation: capturable.
+// A record (`TMazeEnv`, `WindEnv`, `CatchEnv`) holds what is specific to one environment - state, payload, action, arithmetic, widths -
+// and no scheduling.  One thread per row, 64-thread blocks, a few dozen scalar operations plus the row's columns (9 or 7 floats, 102 for
+// Catch): latency of one launch, nothing to tune.  No LDS, no atomics, nothing read from the host, no allocation: capturable.
 //
-// Adding an environment: one record below with the members the two here have, two `extern "C"` entries that instantiate the templates,
-// two wrappers in hip/ops.py, a record in env_utils/device_env.py, and a host twin to compare against bit for bit.
+// Adding an environment: one record below with the members the three here have, two `extern "C"` entries that instantiate the templates
+// (prototypes, cfg struct and state-size constants in include/resel_hip.h, mirrored in hip/_lib.py), two wrappers in hip/ops.py, a
+// record in env_utils/device_env.py, and a host twin to compare against bit for bit.  `Env::step` sees the state and the cfg only: an
+// environment that needs its payload in mid-episode (Catch) copies it into its state in `reset`.  NPAY is a compile-time constant: a
+// payload of varying length is a fixed-capacity row with an unused tail.
 #include "resel_common.h"
 
 namespace {
@@ -198,6 +201,87 @@ struct WindEnv {
         out[1] = a.v[1];
     }
     __device__ static void ring_action(Action a, float* out) { last_action(a, out); }
+};
+
+// ---- Catch-<runs>-v0 (reference envs/credit_assign/catch.py `DelayedCatch`; host twin env_utils/catch.py) ------------------------------
+// Integer state, a 49-wide observation, and a per-episode payload that is a table: the fruit and basket columns of every run.
+// `step` sees no payload, so `reset` copies the episode's draws into the row's state and a soft reset reads them from there.
+struct CatchEnv {
+    using Cfg = resel_catch_cfg_t;
+    using State = int32_t*;                                               // base of env_state, or one row of it
+    using Payload = int32_t;                                              // ns[MAX_RUNS] | ms[MAX_RUNS] of an episode
+    using Action = int;                                                   // the clamped index
+    static constexpr int GRID = 7, MAX_RUNS = RESEL_CATCH_MAX_RUNS;
+    static constexpr int NPAY = 2 * MAX_RUNS, OBS = GRID * GRID, LAST_ACTION = 3, ACTION = 1, IN = 2 * OBS + LAST_ACTION + 1;
+    // words of a row of env_state; SBOOK: the bookkeeping trio, SPAD keeps the row a multiple of 8 bytes
+    enum { SROW = 0, SCOL, SBASKET, SCOUNT, ST, SACC, SBOOK, SPAD = SBOOK + 3, SNS, SMS = SNS + MAX_RUNS, SWORDS = SMS + MAX_RUNS };
+    static_assert(SWORDS == RESEL_CATCH_STATE_WORDS && SWORDS % 2 == 0, "the header's row of state words");
+
+    static bool cfg_bad(const Cfg& c) {
+        return c.num_catches < 1 || c.num_catches > MAX_RUNS || c.episode_length != GRID * c.num_catches - 1;
+    }
+    static bool null(State s) { return !s; }
+    __device__ static State row(State base, int b) { return base + (int64_t)b * SWORDS; }
+    __device__ static int32_t* book(State st) { return st + SBOOK; }
+    __device__ static int cell(int v) { return min(max(v, 0), GRID - 1); }       // a row / column of the grid, whatever the word holds
+
+    __device__ static void clear(State st) {
+        for (int w = 0; w < SWORDS; ++w) st[w] = 0;
+    }
+
+    // `reset()`: the episode's draws into the state, the first fruit and basket in place, nothing caught, the clock at 0.
+    __device__ static void reset(const Cfg&, State st, const Payload* draws, int started) {
+        for (int k = 0; k < NPAY; ++k) st[SNS + k] = draws[k];
+        st[SROW] = 0;
+        st[SCOL] = draws[0];
+        st[SBASKET] = draws[MAX_RUNS];
+        st[SCOUNT] = 1;
+        st[ST] = 0;
+        st[SACC] = 0;
+        st[SBOOK + BSTARTED] = started;
+        st[SBOOK + BRUNNING] = 1;
+    }
+
+    // The flattened canvas: -1 at the fruit, then +1 at the basket in the last row (it covers a fruit in its cell).
+    __device__ static void observe(const Cfg&, State st, float* obs) {
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) obs[c] = 0.f;
+        obs[GRID * cell(st[SROW]) + cell(st[SCOL])] = -1.f;
+        obs[GRID * (GRID - 1) + cell(st[SBASKET])] = 1.f;
+    }
+
+    // The action index as the head kernel wrote it (fp32), clamped into [0, 3); NaN fails both tests: 0.
+    __device__ static int clamp_action(float af) { return af >= 2.f ? 2 : (af >= 0.f ? (int)af : 0); }
+    __device__ static Action read_action(const float* a) { return clamp_action(a[0]); }
+
+    // One `DelayedCatch.step`: the clock advances; a fruit in the last row is replaced (the action is ignored), any other falls one
+    // row while the basket moves.  Every reward but the last step's is 0; the last pays the catches.  -> done
+    __device__ static bool step(const Cfg& cfg, State st, Action a, double* r) {
+        const int t = st[ST] + 1;
+        st[ST] = t;
+        *r = 0.0;
+        if (st[SROW] >= GRID - 1) {                       // soft reset; the count is clamped: a corrupted word reads inside the draws
+            const int k = min(max(st[SCOUNT], 0), cfg.num_catches - 1);
+            st[SROW] = 0;
+            st[SCOL] = st[SNS + k];
+            st[SBASKET] = st[SMS + k];
+            st[SCOUNT] = k + 1;
+            return false;
+        }
+        const int basket = cell(st[SBASKET] + a - 1), fruit_row = st[SROW] + 1;
+        st[SBASKET] = basket;
+        st[SROW] = fruit_row;
+        int acc = st[SACC];
+        if (fruit_row == GRID - 1 && st[SCOL] == basket) st[SACC] = ++acc;
+        const bool done = t >= cfg.episode_length;
+        if (done) *r = (double)acc;
+        return done;
+    }
+
+    __device__ static void last_action(Action a, float* out) {           // one-hot(a)
+        for (int c = 0; c < LAST_ACTION; ++c) out[c] = c == a ? 1.f : 0.f;
+    }
+    __device__ static void ring_action(Action a, float* out) { out[0] = (float)a; }
 };
 
 // ---- what the two kernels share ---------------------------------------------------------------------------------------------------
@@ -414,6 +498,20 @@ int resel_wind_collect_step(resel_wind_cfg_t cfg, resel_collect_layout_t lay, in
                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream) {
     return collect_step<WindEnv>(cfg, lay, init, action, ld_action, wind, {env_pos, env_words}, ret_acc, traj, T_cap, ld_row,
                                  max_episode_steps, in_block, ld_in, A, B, stream);
+}
+
+int resel_catch_step(resel_catch_cfg_t cfg, int init, const float* action, int64_t ld_action, const int32_t* draws, int64_t ld_draws,
+                     const int32_t* n_episodes, int J, int32_t* env_state, double* ret_acc, double* ep_ret, int32_t* ep_len, int64_t ld_ep,
+                     float* in_block, int64_t ld_in, int A, int32_t* flags, int B, resel_stream_t stream) {
+    return eval_step<CatchEnv>(cfg, init, action, ld_action, draws, ld_draws, n_episodes, J, env_state, ret_acc, ep_ret, ep_len, ld_ep,
+                               in_block, ld_in, A, flags, B, stream);
+}
+
+int resel_catch_collect_step(resel_catch_cfg_t cfg, resel_collect_layout_t lay, int init, const float* action, int64_t ld_action,
+                             const int32_t* draws, int32_t* env_state, double* ret_acc, float* traj, int T_cap, int64_t ld_row,
+                             int max_episode_steps, float* in_block, int64_t ld_in, int A, int B, resel_stream_t stream) {
+    return collect_step<CatchEnv>(cfg, lay, init, action, ld_action, draws, env_state, ret_acc, traj, T_cap, ld_row, max_episode_steps,
+                                  in_block, ld_in, A, B, stream);
 }
 
 }  // extern "C"

@@ -267,7 +267,7 @@ class SAC:
                 # turns out ragged (fixed-length ones never switch), 0 / unset = exact shapes only
                 graphed = GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())
                 update = graphed.step
-        # an environment that exists as a kernel (a discrete T-Maze, Wind-v0: env_utils/device_env.py) is collected on the device
+        # an environment that exists as a kernel (a discrete T-Maze, Wind-v0, Catch: env_utils/device_env.py) is collected on the device
         # (utility/device_collect.py): environment step, transition row and next inputs are the last node of the policy step's graph;
         # RESEL_DEVICE_COLLECT (read here) switches it, every other run keeps the host loop below
         from ..utility.device_collect import DeviceCollector

@@ -2,13 +2,13 @@
 `DeviceCollector` (utility/device_collect.py) need to know about the environment they step inside the policy step's graph.
 
 A record says which observation / action widths it steps, which policy head it reads and which of its output columns, how many bytes of
-device state a row has and how they are viewed, what an episode's init payload is (the T-Maze's goal side, Wind's wind vector), which
-two `ops` entries run it, and how the state comes back into the host environment object.  `device_env_kind(env)` finds the record of an
-environment object (None: it has no device step)."""
+device state a row has and how they are viewed, what an episode's init payload is (the T-Maze's goal side, Wind's wind vector, Catch's
+fruit and basket columns), which two `ops` entries run it, and how the state comes back into the host environment object.
+`device_env_kind(env)` finds the record of an environment object (None: it has no device step)."""
 import numpy as np
 import torch
 
-from . import tmaze, wind
+from . import catch, tmaze, wind
 
 
 class DeviceEnvKind:
@@ -163,12 +163,80 @@ class WindKind(DeviceEnvKind):
         return ps[0:2].copy().reshape(1, -1), ps[4:6].copy().reshape(1, -1), row[2 * o:2 * o + a].copy().reshape(1, -1)
 
 
+class CatchKind(DeviceEnvKind):
+    """Catch-<runs>-v0 (env_utils/catch.py), runs <= 40: int32 words fruit_row, fruit_col, basket, catch_count, t, accumulated, ep_len,
+    episodes_started, running, a pad word, then the episode's draws ns[40] | ms[40] - the payload, which the kernel's reset copies into the
+    row because a soft reset reads it in mid-episode."""
+    obs_dim, act_dim = 49, 3
+    categorical, policy_words = True, 'a categorical one'
+    MAX_RUNS, STATE_WORDS, DRAWS = 40, 90, 10               # RESEL_CATCH_MAX_RUNS, RESEL_CATCH_STATE_WORDS; DRAWS: the first word of ns
+    state_bytes = 4 * STATE_WORDS
+    payload_dtype, payload_np, payload_width = torch.int32, np.int32, 2 * MAX_RUNS
+    book_offset = 4 * 6
+
+    steps = staticmethod(catch.device_steppable)
+    # the categorical head, its mode / sample columns and an info-free evaluation, as the T-Maze's
+    policy_ok, action, eval_extras = (staticmethod(f) for f in (TMazeKind.policy_ok, TMazeKind.action, TMazeKind.eval_extras))
+
+    @classmethod
+    def state_views(cls, block, B):
+        return (block.view(torch.int32).view(B, cls.STATE_WORDS),)
+
+    @staticmethod
+    def eval_step(ops, cfg, init, action, payload, n_ep, state, ret_acc, ep_ret, ep_len, in_dev, flags):
+        ops.catch_step(cfg, init, action, payload, n_ep, state[0], ret_acc, ep_ret, ep_len, in_dev, flags)
+
+    @staticmethod
+    def collect_step(ops, cfg, name2range, init, action, payload, state, ret_acc, traj, max_episode_steps, in_dev):
+        ops.catch_collect_step(cfg, name2range, init, action, payload, state[0], ret_acc, traj, max_episode_steps, in_dev)
+
+    @classmethod
+    def _row(cls, ns, ms):
+        """(ns, ms) of an episode -> the kernel's payload row: ns[40] | ms[40], zeros behind the runs."""
+        out = np.zeros(2 * cls.MAX_RUNS, dtype=np.int32)
+        out[:len(ns)], out[cls.MAX_RUNS:cls.MAX_RUNS + len(ms)] = ns, ms
+        return out
+
+    @classmethod
+    def eval_payloads(cls, envs, n, draw_task):
+        """As the T-Maze's: each row's own stream, in the row's episode order - the two draws its `reset()` makes."""
+        rows = len(envs)
+        out = [None] * n
+        for r, env in enumerate(envs):
+            for k in range(r, n, rows):
+                out[k] = cls._row(*env.draw_fruits())
+        return out
+
+    @staticmethod
+    def behind_reset(env) -> bool:
+        return env.time_step == 0 and env.fruit_row == 0 and env.catch_count == 1 and env.accumulated == 0
+
+    @classmethod
+    def current_payload(cls, env):
+        return cls._row(env.ns, env.ms)
+
+    @classmethod
+    def next_payload(cls, alg):
+        """`env_reset()`'s draws for the next training episode, recorded in the environment object."""
+        alg.env.ns, alg.env.ms = alg.env.draw_fruits()
+        return cls._row(alg.env.ns, alg.env.ms)
+
+    @classmethod
+    def sync_env(cls, env, state, row, o, a):
+        st = state[0][0].cpu().numpy()
+        env.fruit_row, env.fruit_col, env.basket, env.catch_count, env.time_step, env.accumulated = (int(v) for v in st[:6])
+        ns = st[cls.DRAWS:cls.DRAWS + cls.MAX_RUNS]
+        env.ns, env.ms = ns[:env.runs].astype(np.int64), st[cls.DRAWS + cls.MAX_RUNS:][:env.runs].astype(np.int64)
+        return (row[:o].copy().reshape(1, -1), row[o:2 * o].copy().reshape(1, -1), row[2 * o:2 * o + a].astype(np.float64).reshape(1, -1))
+
+
 KINDS = (TMazeKind, WindKind)
+GRID_KINDS = (CatchKind,)                                  # apart from KINDS: tests/test_wind_env_host.py holds every member of KINDS to a 2-wide observation
 
 
 def device_env_kind(env):
     """The record of the kernel that steps `env`, or None."""
-    for kind in KINDS:
+    for kind in KINDS + GRID_KINDS:
         if kind.steps(env):
             return kind
     return None

@@ -3,8 +3,8 @@
 The simulator zoo of the reference (`envs/`) is out of scope.  Names of the form
 `synthetic-o<obs>-a<act>-T<len>` (or `-d<n>-` for n discrete actions) build the Gaussian environment used by the benchmark / tests;
 `Mem-T-{passive,active}-<L>[-cont-act]-v0` build the T-Maze memory task (env_utils/tmaze.py); `Wind-v0` builds the meta-RL task of
-env_utils/wind.py with the reference's task split; anything else - the other meta names included - is handed to `gym.make` when gym
-is installed and fails loudly otherwise."""
+env_utils/wind.py with the reference's task split; `Catch-<runs>-v0` builds the delayed-reward task of env_utils/catch.py; anything
+else - the other meta names included - is handed to `gym.make` when gym is installed and fails loudly otherwise."""
 import re
 
 import numpy as np
@@ -95,6 +95,12 @@ def make_env(env_name: str, seed: int) -> dict:
                     multiagent=False)
     if env_name == 'Wind-v0':
         return _make_wind(seed)
+    from . import catch
+    kw = catch.parse_name(env_name)
+    if kw is not None:                                   # Catch-<runs>-v0: the reference's delayed-reward task
+        env, eval_env = catch.Catch(seed=seed, **kw), catch.Catch(seed=seed + 1, **kw)
+        return dict(train_env=env, eval_env=eval_env, train_tasks=[], eval_tasks=[None], max_rollouts_per_task=1,
+                    max_trajectory_len=env.episode_length, obs_dim=49, act_dim=3, act_continuous=False, seed=seed, multiagent=False)
     try:
         import gym
     except ImportError as e:

@@ -45,6 +45,15 @@ class WindCfg(ctypes.Structure):                        # resel_wind_cfg_t, by v
 
 
 WIND_STATE_DOUBLES, WIND_STATE_WORDS = 6, 4
+
+
+class CatchCfg(ctypes.Structure):                       # resel_catch_cfg_t, by value
+    _fields_ = [('num_catches', ctypes.c_int32), ('episode_length', ctypes.c_int32)]
+
+
+# RESEL_CATCH_MAX_RUNS; RESEL_CATCH_STATE_WORDS: six environment words, the bookkeeping trio, a pad word, ns[40], ms[40]
+CATCH_MAX_RUNS, CATCH_STATE_WORDS = 40, 90
+CATCH_PAYLOAD_WORDS = 2 * CATCH_MAX_RUNS                # ns[40] | ms[40] of one episode
 COLLECT_FIELDS = ('state', 'last_state', 'last_action', 'action', 'next_state', 'reward', 'logp', 'mask', 'start', 'done', 'reward_input',
                   'timeout')                            # the ring's `tuplenames`, in its order
 
@@ -154,6 +163,8 @@ SIGNATURES = {
     'resel_tmaze_collect_step': (c_int, [TMazeCfg, CollectLayout, I, P, L, P, P, P, P, I, L, I, P, L, I, I, S]),
     'resel_wind_step': (c_int, [WindCfg, I, P, L, P, L, P, I, P, P, P, P, P, L, P, L, I, P, I, S]),
     'resel_wind_collect_step': (c_int, [WindCfg, CollectLayout, I, P, L, P, P, P, P, P, I, L, I, P, L, I, I, S]),
+    'resel_catch_step': (c_int, [CatchCfg, I, P, L, P, L, P, I, P, P, P, P, L, P, L, I, P, I, S]),
+    'resel_catch_collect_step': (c_int, [CatchCfg, CollectLayout, I, P, L, P, P, P, P, I, L, I, P, L, I, I, S]),
     'resel_categorical_fwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_categorical_bwd': (c_int, [P, F, P, P, P, I, I, S]),
     'resel_discrete_value': (c_int, [P, P, I, P, P, P, I, I, I, S]),

@@ -2271,15 +2271,17 @@ def categorical_step(logits, u, floor=0.01, out=None):
 
 
 # ---- environment steps inside the graphed policy step (csrc/env_step.hip): what the entries of every environment check alike ----------
-def _env_rows(what, B, A, action, action_width, ret_acc, in_block):
+def _env_rows(what, B, A, action, action_width, ret_acc, in_block, obs=2):
     """The blocks every entry takes: action fp32 [B] (action_width 1) or [B, action_width], unit column stride, any row stride; ret_acc
-    fp64 [B]; in_block fp32 [B, >= 2 * 2 + A + 1], unit column stride (A: the width of lst_action).  -> (ld_action, ld_in)."""
+    fp64 [B]; in_block fp32 [B, >= 2 * obs + A + 1], unit column stride (obs: the width of an observation, A: of lst_action).
+    -> (ld_action, ld_in)."""
+    width = 2 * obs + A + 1
     assert action.dtype == torch.float32 and (action.shape == (B,) if action_width == 1 else
                                               action.shape == (B, action_width) and action.stride(1) == 1), f'{what}: the action view'
     assert ret_acc.dtype == torch.float64 and ret_acc.is_contiguous() and ret_acc.numel() == B
-    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= 2 * 2 + A + 1
+    assert in_block.dtype == torch.float32 and in_block.dim() == 2 and in_block.shape[0] == B and in_block.shape[1] >= width
     assert (in_block.stride(1) == 1) and (B <= 1 or in_block.stride(0) >= in_block.shape[1]), 'unit stride along a row, rows do not overlap'
-    return max(action.stride(0), action_width), max(in_block.stride(0), 2 * 2 + A + 1)
+    return max(action.stride(0), action_width), max(in_block.stride(0), width)
 
 
 def _env_eval_tables(B, flags, n_episodes, ep_ret, ep_len):
@@ -2411,6 +2413,58 @@ def wind_collect_step(cfg: dict, name2range: dict, init: bool, action, wind, env
         return
     check(lib().resel_wind_collect_step(c, lay, int(bool(init)), _p(action), ld_action, _p(wind), _p(env_pos), _p(env_words), _p(ret_acc),
                                         _p(traj), T_cap, ld_row, int(max_episode_steps), _p(in_block), ld_in, A, B, _stream()), 'wind_collect_step')
+
+
+def _catch_cfg(cfg: dict, B, env_state):
+    """`Catch.device_config()` -> the entries' cfg struct, behind the check of the environment's state block."""
+    from ._lib import CATCH_STATE_WORDS, CatchCfg
+    assert env_state.dtype == torch.int32 and env_state.is_contiguous() and env_state.shape == (B, CATCH_STATE_WORDS)
+    return CatchCfg(int(cfg['num_catches']), int(cfg['episode_length']))
+
+
+@torch.no_grad()
+def catch_step(cfg: dict, init: bool, action, draws, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags):
+    """One Catch environment step (or, init: the start of an evaluation) for the B rows of a graphed policy step, as one launch:
+    include/resel_hip.h `resel_catch_step`, host twin env_utils/catch.py.  cfg: `Catch.device_config()`.
+    action: fp32 [B] view, any stride - the action indices (column 0 of the categorical step's output block);
+    draws int32 [B, J, 80] (ns[40] | ms[40] per episode, zeros behind the runs), n_episodes int32 [B] (each at most J), env_state int32
+    [B, 90], ret_acc fp64 [B], ep_ret fp64 / ep_len int32 [B, J]; in_block fp32 [B, >= 102] with unit column stride
+    (state[49] | lst_state[49] | lst_action[3] | reward[1]), flags int32 [B].
+    Everything is updated in place; nothing else on the stream, no host read, no allocation: capturable."""
+    from ._lib import CATCH_PAYLOAD_WORDS as W
+    _need_cuda('catch_step', action, draws, n_episodes, env_state, ret_acc, ep_ret, ep_len, in_block, flags)
+    B, A = flags.numel(), 3
+    ld_action, ld_in = _env_rows('catch_step', B, A, action, 1, ret_acc, in_block, obs=49)
+    J = _env_eval_tables(B, flags, n_episodes, ep_ret, ep_len)
+    assert draws.dtype == torch.int32 and draws.shape == (B, J, W) and draws.is_contiguous()
+    c = _catch_cfg(cfg, B, env_state)
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    check(lib().resel_catch_step(c, int(bool(init)), _p(action), ld_action, _p(draws), W * J, _p(n_episodes), J, _p(env_state), _p(ret_acc),
+                                 _p(ep_ret), _p(ep_len), J, _p(in_block), ld_in, A, _p(flags), B, _stream()), 'catch_step')
+
+
+@torch.no_grad()
+def catch_collect_step(cfg: dict, name2range: dict, init: bool, action, draws, env_state, ret_acc, traj, max_episode_steps: int, in_block):
+    """One iteration of the training rollout on Catch (or, init: `env_reset()` with the episode's draws in `draws`) for the B rows of a
+    graphed policy step, as one launch: include/resel_hip.h `resel_catch_collect_step`, host twin `SAC._train_loop` / `_push` / `env_step`.
+    cfg: `Catch.device_config()`.  name2range: `MemoryArray.name2range`; a stored field must have the width the rollout produces
+    (observations 49, last action 3, scalars 1; no log-probability).  action: fp32 [B] view, any stride - the SAMPLED indices (column 1
+    of the categorical step's output block); draws int32 [B, 80]; env_state int32 [B, 90], ret_acc fp64 [B]; traj fp32 [B, T_cap, >= the
+    layout's width] with unit column stride: the episode block; in_block fp32 [B, >= 102] with unit column stride.
+    Everything is updated in place; no host read, no allocation: capturable."""
+    from ._lib import CATCH_PAYLOAD_WORDS as W
+    _need_cuda('catch_collect_step', action, draws, env_state, ret_acc, traj, in_block)
+    assert draws.dtype == torch.int32 and draws.dim() == 2 and draws.shape[1] == W and draws.is_contiguous()
+    B, A = draws.shape[0], 3
+    ld_action, ld_in = _env_rows('catch_collect_step', B, A, action, 1, ret_acc, in_block, obs=49)
+    c = _catch_cfg(cfg, B, env_state)
+    T_cap, ld_row = _env_episode_block(B, traj)
+    lay = _collect_layout('catch_collect_step', name2range, dict(state=49, last_state=49, next_state=49, last_action=A, logp=0), traj.shape[2])
+    if B == 0:                                           # empty tensors have no address to hand over
+        return
+    check(lib().resel_catch_collect_step(c, lay, int(bool(init)), _p(action), ld_action, _p(draws), _p(env_state), _p(ret_acc), _p(traj), T_cap,
+                                         ld_row, int(max_episode_steps), _p(in_block), ld_in, A, B, _stream()), 'catch_collect_step')
 
 
 @torch.no_grad()

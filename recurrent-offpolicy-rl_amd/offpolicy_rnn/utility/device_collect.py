@@ -1,4 +1,4 @@
-"""Training rollouts of an environment that exists as a kernel (a discrete T-Maze, Wind-v0) on the device: one graph replay per environment step, one copy back per episode.
+"""Training rollouts of an environment that exists as a kernel (a discrete T-Maze, Wind-v0, Catch) on the device: one graph replay per environment step, one copy back per episode.
 
 `SAC._train_loop` pays one H2D, one replay, one D2H, one synchronise, a Python `TMaze.step`, a `Transition` / `mem_push` and the numpy
 bookkeeping of `env_step` for every environment step.  A T-Maze episode has a fixed length, the ring only admits whole trajectories and the
@@ -14,7 +14,8 @@ host loop's order of side effects, which fixes every random stream.  Ring, logs,
 
 Wind-v0 (continuous actions, `ops.wind_collect_step`) goes the same way: the kernel reads the Gaussian head's SAMPLED action, and the next
 episode's task is one draw from the global numpy stream where the host loop's `env_reset()` makes it (tests/test_wind_env_gpu.py).  What
-differs between the two environments lives in their records (env_utils/device_env.py)."""
+differs between the environments lives in their records (env_utils/device_env.py).  Catch (`ops.catch_collect_step`) is the T-Maze's case with a
+49-wide observation and a payload of 80 words: nothing here knows a width."""
 import os
 
 import numpy as np
@@ -41,7 +42,7 @@ class DeviceCollector:
         """Why `alg.train()` collects through the host loop (None: it collects on the device)."""
         kind = device_env_kind(alg.env)
         if kind is None:
-            return 'the environment has no device step (a T-Maze with discrete actions and Wind-v0 have one)'
+            return 'the environment has no device step (a T-Maze with discrete actions, Wind-v0 and Catch up to 40 runs have one)'
         if alg.sample_device.type != 'cuda' or not kind.policy_ok(alg.policy):
             return f'the policy is not {kind.policy_words} sampling on a CUDA device'
         if os.environ.get('RESEL_GRAPH_ROLLOUT', '1') == '0':

@@ -9,7 +9,8 @@ position are reset inside the graph, hip/graph_step.py).
 `run_episodes` is the scheduler (host only, numpy in / numpy out); `BatchedPolicyEval` owns the graph, the environments and a private
 random stream, and leaves every global generator as it found it.
 
-An environment that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, `ops.tmaze_step`; Wind-v0, `ops.wind_step`) is stepped INSIDE the graph:
+An environment that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, `ops.tmaze_step`; Wind-v0, `ops.wind_step`; Catch up to 40
+runs, `ops.catch_step`) is stepped INSIDE the graph:
 `DeviceEnvEval` appends the environment step to the policy step as its last node, so an evaluation is `waves x episode_length`
 back-to-back replays behind one init call, with one D2H at the end and no host round trip per step.  `RESEL_DEVICE_ENV=0` keeps
 such an environment on the host loop."""
@@ -99,14 +100,15 @@ def device_env_enabled() -> bool:
 
 
 class DeviceEnvEval:
-    """`run_episodes` for `rows` environments of one kind that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, Wind-v0),
+    """`run_episodes` for `rows` environments of one kind that exists as a kernel (env_utils/device_env.py: the discrete T-Maze, Wind-v0, Catch),
     with the environment step inside the graphed policy step.
 
     All episodes have the same length T, so the host scheduler runs episode k on row k % rows as that row's (k // rows)-th episode and
     takes ceil(n / rows) * T steps; this object does the same with one init call of the kind's evaluation entry, that many
     `replay_device()` calls, one D2H of the per-episode results and one synchronise.  What an episode starts from - the T-Maze's goal side,
-    Wind's wind vector - comes from the kind's `eval_payloads`, which draws as the host loop would: the T-Maze from the per-row host
-    environments (`TMaze.draw_goal`, the draw their `reset()` makes), a meta environment one task per episode through `draw_task`.
+    Wind's wind vector, Catch's fruit and basket columns - comes from the kind's `eval_payloads`, which draws as the host loop would: the
+    T-Maze and Catch from the per-row host environments (`TMaze.draw_goal`, `Catch.draw_fruits`: the draws their `reset()` makes), a meta
+    environment one task per episode through `draw_task`.
     The hook runs in the warm-up and in the capture too, on whatever the buffers hold: every buffer is (re)initialised by the init
     call of each evaluation, never at capture."""
 
