@@ -699,7 +699,7 @@ def test_attn_layout_with_integer_data(ops):
 
 
 # ------------------------------------------------------------------------------------------ fused Mamba mixer node
-@pytest.mark.parametrize('B,L,Dm,N,Kw', [(2, 70, 32, 32, 16), (3, 129, 64, 16, 4)])
+@pytest.mark.parametrize('B,L,Dm,N,Kw', [(2, 70, 32, 32, 16), (3, 129, 64, 16, 4), (2, 37, 32, 64, 8), (2, 175, 32, 8, 8)])
 def test_mamba_inner_fused_vs_oracle_chain(ops, B, L, Dm, N, Kw):
     """One autograd node for the whole mixer (reference MambaInnerFn, selective_scan_interface_new.py:169) against the
     chain of CPU oracle ops under torch autograd: output and every parameter / input gradient."""
