@@ -144,6 +144,28 @@ int resel_add_layernorm_bwd(const float* dy, const float* dres_in, const float* 
                             int M, int C, int rms, int has_bias, int act, void* amax_dx, unsigned amax_epoch, resel_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * LayerNorm over a token's E segments of C floats: the `ln+<act>` (E = 1) and `eln-<E>+<act>` tails of the dense stacks
+ * (reference offpolicy_rnn/models/rnn_base.py:250-258,461-467; `eln` normalises all E x C features of a token jointly, weight [E, C]).
+ * Segment e of token m of an operand lies at  base + m * ld_m + e * ld_e  (floats; every operand brings its own pair), so the
+ * token-major [M, E C] output of a shared-input ensemble layer (ld_e = C, ld_m = E C) and the member-major [E, M, C] tensors of the
+ * deeper layers (ld_e = M C, ld_m = C) are read and written where they are.  ld_e is not used when E == 1, ld_m not when M == 1.
+ *   y = act((x - mean) * rstd * w + b),  mean / rstd over the token's E C values;  w, b: dense [E, C], b may be NULL.
+ * act: 0 none, 1 ELU (alpha 1); the backward re-forms elu' from the recomputed pre-activation.  stats: [M, 2] (mean, rstd).
+ * amax_y: optional magnitude handle, gets the bound sqrt(E C) max|w| + max|b| (as resel_add_layernorm_fwd); amax_dx: max |dx|.
+ * dw [E, C]; db [E, C] or NULL (needs b); workspace resel_member_layernorm_bwd_workspace_bytes() (0 for a refused shape).
+ * RESEL_EINVAL: a NULL / misaligned (16 B) operand, C % 4 != 0, E * C > 2048, a stride that is not a positive multiple of 4 or
+ * with E * ld_e >= 2^31, act outside {0, 1}.
+ */
+int resel_member_layernorm_fwd(const float* x, int64_t ldx_e, int64_t ldx_m, const float* w, const float* b,
+                               float* y, int64_t ldy_e, int64_t ldy_m, float* stats, int M, int E, int C, float eps, int act,
+                               void* amax_y, unsigned amax_epoch, resel_stream_t stream);
+size_t resel_member_layernorm_bwd_workspace_bytes(int M, int E, int C);
+int resel_member_layernorm_bwd(const float* dy, int64_t ldg_e, int64_t ldg_m, const float* x, int64_t ldx_e, int64_t ldx_m,
+                               const float* w, const float* b, const float* stats, float* dx, int64_t ldd_e, int64_t ldd_m,
+                               float* dw, float* db, void* workspace, int M, int E, int C, int act,
+                               void* amax_dx, unsigned amax_epoch, resel_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Linear-recurrence scans (gilr, lru).  Replace the Triton kernels
  *   fwd_sequential_scan / bwd_sequential_scan          offpolicy_rnn/models/gilr/scan_triton/real_rnn_tie_input_gate.py:9,67
  *   fwd_sequential_scan_complex / bwd_...               offpolicy_rnn/models/lru/scan_triton/complex_rnn.py:44,91
@@ -498,7 +520,7 @@ int resel_place_blocks(float* out, int64_t ld_out, int rows, int cols, int nblk,
  * are never zeroed, give every tensor a fresh epoch - and kernels that fill parts of one tensor may share handle and epoch.  Readers
  * (amax_a / amax_b above) take the newest epoch among the eight words and the largest magnitude carrying it.  Publishers:
  * resel_amax (a pre-pass), resel_gemm_f32x (amax_c: the values stored to C), resel_bias_act_bwd (gy), resel_ensemble_head_bwd (gy), resel_add_layernorm_fwd
- * (y: the analytic bound sqrt(C) max|w| + max|b|, published by one wave), resel_add_layernorm_bwd (dx), resel_selective_scan_fwd (out), resel_selective_scan_bwd (dz, ddelta),
+ * (y: the analytic bound sqrt(C) max|w| + max|b|, published by one wave), resel_add_layernorm_bwd (dx), resel_member_layernorm_fwd / _bwd (likewise), resel_selective_scan_fwd (out), resel_selective_scan_bwd (dz, ddelta),
  * resel_causal_conv1d_fwd (y), resel_causal_conv1d_bwd (dx), resel_gelu_dropout_fwd / _bwd (y / dx). */
 /* Magnitude pre-pass: max |x| over a [batch][rows][cols] box (row stride ld, batch stride `stride`, cols % 4 == 0) written into the
  * magnitude handle `out` with epoch `epoch` (see "magnitude handles" above); one HBM-bound pass, no host synchronisation.

@@ -81,6 +81,9 @@ SIGNATURES = {
     'resel_add_layernorm_fwd': (c_int, [P, P, P, P, P, P, P, I, I, F, I, I, P, E, S]),
     'resel_add_layernorm_bwd_workspace_bytes': (c_size_t, [I, I]),
     'resel_add_layernorm_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, E, S]),
+    'resel_member_layernorm_fwd': (c_int, [P, L, L, P, P, P, L, L, P, I, I, I, F, I, P, E, S]),
+    'resel_member_layernorm_bwd_workspace_bytes': (c_size_t, [I, I, I]),
+    'resel_member_layernorm_bwd': (c_int, [P, L, L, P, L, L, P, P, P, P, L, L, P, P, P, I, I, I, I, P, E, S]),
     'resel_linrec_real_fwd': (c_int, [P, P, L, P, P, P, I, I, I, I, P, E, S]),
     'resel_linrec_real_bwd': (c_int, [P, P, L, P, P, P, P, P, P, L, I, I, I, I, P, E, S]),
     'resel_linrec_complex_fwd': (c_int, [P, P, L, P, P, P, P, P, P, P, P, I, I, I, P, E, S]),

@@ -406,6 +406,108 @@ def rms_norm_fn(x, weight, bias, residual=None, eps=1e-6, prenorm=False, residua
     return _add_norm(x, residual, weight, bias, eps, True, prenorm)
 
 
+# ---------------------------------------------------------------------------------------------- ln / eln tails of the dense stacks
+MEMBER_NORM_MAX = 2048          # E * C of a token the kernels take (csrc/member_layernorm.hip `MAX_ROW`)
+NORM_FUSED_DEFAULT = '1'        # what an unset RESEL_NORM_FUSED means (README; measured in profiles/r26_norm_blocks.md)
+
+
+def norm_fused_on():
+    """RESEL_NORM_FUSED, read per call: 0 keeps the `ln+` / `eln-E+` tails of the dense stacks on the torch spelling."""
+    return os.environ.get('RESEL_NORM_FUSED', NORM_FUSED_DEFAULT) != '0'
+
+
+def member_layer_norm_ok(E, C):
+    """The shapes `resel_member_layernorm_*` take (anything else is RESEL_EINVAL there)."""
+    return C % 4 == 0 and 0 < E * C <= MEMBER_NORM_MAX
+
+
+def _member_tokens(t, E, C):
+    """t: [E, ..., C] (E == 1: [..., C]) -> (t3 [E, M, C] addressable in place, ld_e, ld_m): segment e of token m at
+    `t3.data_ptr() + 4 (m ld_m + e ld_e)`.  The [E, ..., C] view of a shared-input EnsembleLinear's [M, E C] output qualifies as it is
+    (ld_e = C, ld_m = E C), so does a dense tensor (ld_e = M C, ld_m = C) and a column block of a wider matrix; anything whose token
+    axes do not collapse to ONE stride, or that is not 16-byte addressable, is copied to dense."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    try:
+        t3 = t.view(E, -1, C)
+    except RuntimeError:
+        t3 = None
+    if t3 is not None:
+        se, sm, sc = t3.stride()
+        M = t3.shape[1]
+        if not (sc == 1 and t3.data_ptr() % 16 == 0 and (E == 1 or (se % 4 == 0 and se >= C)) and (M == 1 or (sm % 4 == 0 and sm >= C))):
+            t3 = None
+    if t3 is None:
+        t3 = t.contiguous().view(E, -1, C)
+    M = t3.shape[1]
+    return t3, (t3.stride(0) if E > 1 else C), (t3.stride(1) if M > 1 else E * C)
+
+
+def _like_tokens(t3, ld_e, ld_m):
+    """Uninitialised [E, M, C] in t3's layout when that is one of the two dense ones (token-major [M, E C] seen as [E, M, C], or
+    member-major), else member-major -> (tensor, ld_e, ld_m)."""
+    E, M, C = t3.shape
+    if E > 1 and M > 1 and (ld_e, ld_m) == (C, E * C):
+        return torch.empty(M, E, C, dtype=torch.float32, device=t3.device).transpose(0, 1), C, E * C
+    return torch.empty(E, M, C, dtype=torch.float32, device=t3.device), M * C, C
+
+
+def _aligned_param(p):
+    p = p.float().contiguous()
+    return p if p.data_ptr() % 16 == 0 else p.clone()
+
+
+class MemberLayerNormFn(torch.autograd.Function):
+    """y = act(LayerNorm over the E C features of a token), weight / bias [E, C] (`eln-E`) or [C] (`ln`, E = 1), on the activations
+    where their producer left them (include/resel_hip.h `resel_member_layernorm_*`); the gradient goes back in the input's layout."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, act):
+        _need_cuda('member_layer_norm', x, weight, bias)
+        assert act in (None, 'elu')
+        C = x.shape[-1]
+        E = weight.shape[0] if weight.dim() == 2 else 1
+        assert weight.shape[-1] == C and (weight.dim() == 1 or (x.dim() >= 2 and x.shape[0] == E)), (tuple(x.shape), tuple(weight.shape))
+        x3, lxe, lxm = _member_tokens(x, E, C)
+        M = x3.shape[1]
+        w = _aligned_param(weight)
+        b = None if bias is None else _aligned_param(bias)
+        y3, lye, lym = _like_tokens(x3, lxe, lxm)
+        stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+        slot, slot_p, epoch = _slot_args(amax_tracking() and M * E * C >= (1 << 20), x.device)
+        check(lib().resel_member_layernorm_fwd(_p(x3), lxe, lxm, _p(w), _p(b), _p(y3), lye, lym, _p(stats), M, E, C, float(eps),
+                                               int(act == 'elu'), slot_p, epoch, _stream()), 'member_layernorm_fwd')
+        publish_amax(slot)
+        ctx.save_for_backward(x3, w, b, stats)
+        ctx.cfg = (E, C, int(act == 'elu'), x.shape, weight.shape)
+        return y3.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x3, w, b, stats = ctx.saved_tensors
+        E, C, act, shape, wshape = ctx.cfg
+        M = x3.shape[1]
+        g3, lge, lgm = _member_tokens(dy, E, C)
+        _, lxe, lxm = _member_tokens(x3, E, C)
+        dx3, lde, ldm = _like_tokens(x3, lxe, lxm)
+        dw = torch.empty(wshape, dtype=torch.float32, device=x3.device)
+        db = None if b is None else torch.empty(wshape, dtype=torch.float32, device=x3.device)
+        ws = _ws(lib().resel_member_layernorm_bwd_workspace_bytes(M, E, C), x3.device)
+        slot, slot_p, epoch = _slot_args(amax_tracking() and M * E * C >= (1 << 20), x3.device)
+        check(lib().resel_member_layernorm_bwd(_p(g3), lge, lgm, _p(x3), lxe, lxm, _p(w), _p(b), _p(stats), _p(dx3), lde, ldm, _p(dw), _p(db),
+                                               _p(ws), M, E, C, act, slot_p, epoch, _stream()), 'member_layernorm_bwd')
+        dx = tag_amax(dx3.view(shape), slot, whole=True)            # the gradient the layer in front multiplies with its weights
+        return dx, dw, db, None, None
+
+
+def member_layer_norm(x, weight, bias, eps=1e-5, act=None):
+    """The `ln+<act>` / `eln-<E>+<act>` norm of a dense stack (reference rnn_base.py:250-258,461-467) with the ELU, if `act='elu'`, in the same
+    pass.  x: [E, ..., C] with weight / bias [E, C] - one LayerNorm over all E x C features of a token, jointly across the members, what
+    the reference spells `LayerNorm([E, C])(x.transpose(-2, 0)).transpose(-2, 0)` - or [..., C] with weight / bias [C].  The output
+    carries the magnitude bound the kernel published, for the GEMM behind it."""
+    return apply_tagged(MemberLayerNormFn.apply, True, x, weight, bias, eps, act)
+
+
 # ---------------------------------------------------------------------------------------------- linear recurrences
 def _token_rows(*ts):
     """[B, L, C] fp32 operands of a scan -> (operands usable in place, ld): their (b, t) axes collapse to token rows `ld` floats apart with unit

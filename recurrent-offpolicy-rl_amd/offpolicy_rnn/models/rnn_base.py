@@ -81,6 +81,7 @@ class RNNBase(torch.nn.Module):
             self.activation_list.append(self._make_activation(activation[ind], width))
             width_in = width
         self.rnn_layer_kind = [kind for kind in self.layer_kind if kind is not None]           # beside rnn_layer_type
+        self._norm_refused = set()              # layers whose `+` norm the HIP kernels refused (logged once each)
         self.xavier_initialize_weights()
 
     @staticmethod
@@ -144,6 +145,10 @@ class RNNBase(torch.nn.Module):
     def sequence_layers(self):
         """[(kind, module)] of the sequence layers, in stack order: what the trainers ask about a network's layers, they ask here."""
         return [(kind, layer) for kind, layer in zip(self.layer_kind, self.layer_list) if kind is not None]
+
+    def members_coupled(self) -> bool:
+        """An `eln-<E>` norm normalises a token over ALL members jointly: the members of this stack cannot be evaluated as a subset."""
+        return any(spec.startswith('eln') for spec in self.activation_type)
 
     def rnn_parameters(self, recursive=True):
         out = []
@@ -264,16 +269,46 @@ class RNNBase(torch.nn.Module):
                 continue
             act = self.activation_list[ind]
             if isinstance(act, torch.nn.ModuleList):
-                if self.activation_type[ind].startswith('eln'):
-                    x = act[0](x.transpose(-2, 0)).transpose(-2, 0)
-                else:
-                    x = act[0](x)
-                x = act[1](x)
+                x = self._norm_tail(ind, act, x)
             else:
                 x = act(x)
         if squeeze:
             x = x.squeeze(0)
         return x, out_state, full
+
+    def _norm_fused(self, ind, norm, x) -> bool:
+        """The `ln+` / `eln-E+` norm behind layer `ind` runs in `ops.member_layer_norm`: an fp32 GPU tensor of a shape the kernels take -
+        for `eln-E`, one whose axis 0 is the E members the norm was built for - unless RESEL_NORM_FUSED=0 (read per call)."""
+        if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 and norm.elementwise_affine and ops.norm_fused_on()):
+            return False
+        shape = tuple(norm.normalized_shape)
+        if len(shape) == 2 and not (x.dim() >= 3 and x.shape[0] == shape[0]):
+            return False
+        E, C = (shape[0], shape[1]) if len(shape) == 2 else (1, shape[0])
+        if x.shape[-1] != C:
+            return False
+        if not ops.member_layer_norm_ok(E, C):
+            if ind not in self._norm_refused:                 # said once per layer
+                self._norm_refused.add(ind)
+                print(f'[ WARNING ] {self.activation_type[ind]} behind layer {ind}: {E} x {C} is outside what the HIP norm kernels take '
+                      f'(width % 4 == 0, E * width <= {ops.MEMBER_NORM_MAX}); this layer keeps the torch LayerNorm')
+            return False
+        return True
+
+    def _norm_tail(self, ind, act, x):
+        """The (norm, activation) tail of a `+` spec (reference rnn_base.py:461-467).  On the GPU the norm is one pass over the activations
+        where the layer left them, with a plain ELU riding in it; any other activation module runs behind it.  Parameters stay those of
+        `activation_list.<ind>.0` (a torch LayerNorm), which also is the spelling for everything the kernels do not take."""
+        norm, tail = act[0], act[1]
+        if self._norm_fused(ind, norm, x):
+            elu = isinstance(tail, torch.nn.ELU) and tail.alpha == 1.0
+            x = ops.member_layer_norm(x, norm.weight, norm.bias, norm.eps, 'elu' if elu else None)
+            return x if elu else tail(x)
+        if self.activation_type[ind].startswith('eln'):
+            x = norm(x.transpose(-2, 0)).transpose(-2, 0)
+        else:
+            x = norm(x)
+        return tail(x)
 
     def _dense_step(self, ind, layer, x, first_grad_part, out_dest):
         """The `fc` / `efc-<E>` layer `ind` -> (x, number of following layers its node consumed, their / its activation already applied)."""
