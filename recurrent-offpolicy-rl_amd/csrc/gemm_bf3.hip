@@ -70,6 +70,16 @@ __device__ __forceinline__ int plane_off(int row, int c) {
     return ((row ^ (q & 1)) << 6) + ((c ^ (q & 3)) << 4);
 }
 
+// The third edition's image: the chunk permutation is (0, 3, 2, 1)[q & 3].  Its consumers read a 16-row tile of the 16x16x32 operand with one
+// ds_read_b128 (row lane & 15, chunk lane >> 4), which the hardware serves in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...:
+// rows of q = 0, 3 with chunk c and of q = 1, 2 with chunk c + 1 meet in one group, and `c ^ q` puts two of them on the same 16-byte slots
+// (2-way); this permutation gives the four their own.  The producers' stores keep their bank sets (a row group's chunks are permuted among
+// themselves), and the period stays 16 rows.
+__device__ __forceinline__ int plane_off_ws(int row, int c) {
+    const int q = row >> 2;
+    return ((row ^ (q & 1)) << 6) + ((c ^ (-q & 3)) << 4);
+}
+
 // ---- four fp32 values -> three planes of four bf16 (8 bytes each).  NP = 2 (mode 3): the second plane is the residual ROUNDED to
 // nearest even (v_cvt_pk_bf16_f32) instead of truncated - the dropped part is then unbiased and at most 2^-17 |x|
 __device__ __forceinline__ uint32_t rne_pair(float lo, float hi) {
@@ -222,7 +232,9 @@ struct Src {
             step = (int64_t)BK * ld * 4;
         }
     }
+    template <bool WS = false>                      // WS: the third edition's image (plane_off_ws)
     __device__ __forceinline__ void init_lds(int tid) {
+        auto plane_off = [](int row, int c) { return WS ? plane_off_ws(row, c) : ::plane_off(row, c); };
         if (KC) {
 #pragma unroll
             for (int i = 0; i < NPC; ++i) loff[i] = plane_off((tid >> 3) + 64 * i, (tid & 7) >> 1) + 8 * (tid & 1);
@@ -645,10 +657,12 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 // different waves.  In the second edition every wave loads, splits, stores planes, reads fragments, issues matrix instructions and stores
 // C in program order - a wave parked on `vmcnt` issues no matrix instruction either - and its parts ADD (profiles/r04_gemm.md: data path
 // 192 us + split 50 + C stores 113 + matrix instructions 158 = 513 against 455 measured at 66 752 x 2048 x 384).  Here, 512 threads:
-//   * waves 0..3 (consumers, 2 x 2 over the 256 x 128 tile, wave tile 128 x 64 = 4 x 2 tiles of 32 x 32, 128 accumulator registers) only
-//     read fragments (12 ds_read_b128 per 16-k slab, two register sets), issue matrix instructions and store C; they never wait for a
-//     load.  2^-11 b1 - the third B "plane" of mode 2 - is formed from b1's fragment with four packed fp16 multiplies (the values
-//     the producer's packed multiply used to store): LDS holds two planes per operand;
+//   * waves 0..3 (consumers, 2 x 2 over the 256 x 128 tile, wave tile 128 x 64 = 8 x 4 tiles of 16 x 16 on v_mfma_f32_16x16x32_f16, 128
+//     accumulator registers) only read fragments (24 ds_read_b128 per K step: one read is a 16-row tile's whole 32-k step; B held per
+//     step in one of two register sets, A tiles through a ring of two), issue matrix instructions and store C; they never wait for a
+//     load.  2^-11 b1 - the third B "plane" of mode 2 - is formed from b1's fragments with sixteen packed fp16 multiplies per step (the
+//     values the producer's packed multiply used to store): LDS holds two planes per operand, in this edition's own chunk
+//     permutation (plane_off_ws: the 16-row reads are conflict-free);
 //   * waves 4..7 (producers, one per SIMD) hold two register sets = two K steps of the fp32 tiles; ALL their tile loads are inline
 //     assembly the compiler does not count, and every unit (a piece of a [rows][K] operand, an instance of a transposed one) waits for
 //     ITS loads with a hand-written `s_waitcnt vmcnt(24 - n)` tied to its registers through "+v" operands (24 loads in flight, the
@@ -665,8 +679,10 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 //   * after the K loop a K slice goes to the slab and a whole-K item through ONE of three separate epilogues, chosen at compile time:
 //     EPI 0 plain (bias, Params::act 0 .. 3), EPI 4 dact (whole tiles only: the host entry refuses other shapes), EPI 5 head (bias, ELU,
 //     row dots; whole and edge tiles).  Each spells out its own tile loop: see the note at EPI 0's whole-tile block.
-// 256 registers, 24 bytes of scratch (EPI 5: 84-92, EPI 4: 288), two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
+// 256 registers, 24-32 bytes of scratch (EPI 5: 84-88, EPI 4: none), two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
 // us): fwd [T,384] -> 256 77 -> 67, [T,256] -> 256 55 -> 48, [T,256] -> 1024 171 -> 150, [T,384] -> 2048 420 -> 365.
+// The 16x16x32 consumers against the 32x32x16 ones on a box that holds the clock down: 357.8 -> 349.2 at [T,384] -> 2048, 53.1 -> 48.0 at [T,256] -> 256,
+// level at K = 1024 and on fast-class boxes (profiles/r29_gemm_mfma16.md).
 constexpr int NTH_WS = 512;
 constexpr int WS_LDS = 2 * STAGE;
 #define WS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
@@ -690,8 +706,8 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
         typedef Src<BKC, BN> SB;
         SA a0, a1;
         SB b0, b1;
-        a0.init_lds(pt); a1.init_lds(pt + 256);
-        b0.init_lds(pt); b1.init_lds(pt + 256);
+        a0.template init_lds<true>(pt); a1.template init_lds<true>(pt + 256);
+        b0.template init_lds<true>(pt); b1.template init_lds<true>(pt + 256);
         // Register sets as native 128-bit values: they are operands of the inline assembly below.  ALL tile loads of this wave are inline
         // assembly the compiler does not count, and every unit (a piece of a [rows][K] operand, an instance of a transposed one) waits for
         // its own loads with a hand-written `s_waitcnt vmcnt(24 - n)` tied to its registers through "+v" operands (24 loads = two register
@@ -828,122 +844,146 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
     }
 
     // ---------------------------------------------------------------------------------------------------- consumers
-    // wave w: rows 128 (w >> 1) .. + 127, columns 64 (w & 1) .. + 63 of the 256 x 128 block tile = 4 x 2 tiles of 32 x 32 = 128 accumulator
-    // registers; fragments of a 16-k slab: A 2 planes x 4 tiles + B 2 planes x 2 tiles = 12 ds_read_b128 (48 registers), two sets
+    // wave w: rows 128 (w >> 1) .. + 127, columns 64 (w & 1) .. + 63 of the 256 x 128 block tile = 8 x 4 tiles of 16 x 16 (v_mfma_f32_16x16x32_f16),
+    // 128 accumulator registers: acc[i][j][r] is row 16 i + 4 (lane >> 4) + r, column 16 j + (lane & 15) of the wave tile.  An operand
+    // fragment of a 16-row tile is ONE ds_read_b128 at chunk lane >> 4 of row lane & 15: the whole 32-k step (plane_off has a period of 16
+    // rows, so tile t sits 16 t rows on).  Held per K step: B, 4 tiles x 2 planes (two sets: the next step's is read under this step's last
+    // products), 2^-11 b1 (16 registers), and the A tiles streaming through a ring of two (2 planes x 4 registers each): 24 reads per step.
+#ifdef BF3_AB_CLOCK
+    const unsigned long long ck_t0 = __builtin_amdgcn_s_memtime(), ck_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
     const float unscale = (1.f / sa_) * (1.f / sb_);
     const int lane = tid & 63, w = tid >> 6;
     const int wm = (w >> 1) * 128, wn = (w & 1) * 64;
-    const int li = lane & 31, lh = lane >> 5;
-    const char* fa[2];
-    const char* fb[2];
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const char* fa = lds + wm * ROWB + plane_off_ws(l15, l4);
+    const char* fb = lds + 3 * PLA + wn * ROWB + plane_off_ws(l15, l4);
+    typedef float f32x4v __attribute__((ext_vector_type(4)));
+    struct BF { f16x8 p[2][4]; };
+    f16x8 ar[2][2];                                  // the A ring: [slot][plane]
+    f32x4v acc[8][4];
+    // the lane's 16 values of the 32 x 32 region (a, b) = a 2 x 2 group of accumulators, e = 8 ii + 4 jj + r: the exits walk these regions
+#define WS_ACC(a, b, e) acc[2 * (a) + ((e) >> 3)][2 * (b) + (((e) >> 2) & 1)][(e) & 3]
+#define WS_DROW(e) (16 * ((e) >> 3) + ((e) & 3))      /* row inside the region, less 4 (lane >> 4) */
+#define WS_DCOL(e) (16 * (((e) >> 2) & 1))            /* column inside the region, less lane & 15 */
+#define WS_BV(b, e) bv[2 * (b) + (((e) >> 2) & 1)]
+    auto rdB = [&](BF& f, const char* pb) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        fa[s] = lds + wm * ROWB + plane_off(li, 2 * s + lh);
-        fb[s] = lds + 3 * PLA + wn * ROWB + plane_off(li, 2 * s + lh);
-    }
-    struct F4 { f16x8 a[2][4], b[2][2]; };
-    auto rd = [&](F4& f, const char* pa, const char* pb) {
+        for (int pi = 0; pi < 2; ++pi)
 #pragma unroll
-        for (int pi = 0; pi < 2; ++pi) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) f.a[pi][t] = *reinterpret_cast<const f16x8*>(pa + pi * PLA + t * 32 * ROWB);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) f.b[pi][t] = *reinterpret_cast<const f16x8*>(pb + pi * PLB + t * 32 * ROWB);
-        }
+            for (int t = 0; t < 4; ++t) f.p[pi][t] = *reinterpret_cast<const f16x8*>(pb + pi * PLB + t * 16 * ROWB);
     };
-    f32x16 acc[4][2];
-    auto mm = [&](const F4& f) {                    // a2 (2^-11 b1) + a1 b2 + a1 b1, the small terms first
+    // one K step: a2 (2^-11 b1) + a1 b2 + a1 b1 per A tile, the small terms first, four independent accumulators between two products of
+    // one.  Behind tile i's products the ring slot takes tile i + 2; behind tile 5's the stage has been read to the end, so the step's
+    // barrier stands behind tile 6's products and the next stage's B set and first A tiles are read under tile 7's.
+    auto step = [&](const BF& bc, BF& bn, const char* pa, const char* pan, const char* pbn, bool next) {
         const f16x8 k = {(_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f,
                          (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f};
-        const f16x8 bs0 = f.b[0][0] * k, bs1 = f.b[0][1] * k;
+        f16x8 bs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bs[j] = bc.p[0][j] * k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f16x8 a1 = ar[i & 1][0], a2 = ar[i & 1][1];
 #ifdef BF3_AB_NOMFMA
+            asm volatile("" :: "v"(a1), "v"(a2), "v"(bs[0]), "v"(bs[1]), "v"(bs[2]), "v"(bs[3]));
+            asm volatile("" :: "v"(bc.p[0][0]), "v"(bc.p[0][1]), "v"(bc.p[0][2]), "v"(bc.p[0][3]), "v"(bc.p[1][0]), "v"(bc.p[1][1]), "v"(bc.p[1][2]), "v"(bc.p[1][3]));
+#else
 #pragma unroll
-        for (int a = 0; a < 4; ++a) asm volatile("" :: "v"(f.a[0][a]), "v"(f.a[1][a]), "v"(bs0), "v"(bs1), "v"(f.b[0][0]), "v"(f.b[0][1]), "v"(f.b[1][0]), "v"(f.b[1][1]));
-        return;
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, bs[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bc.p[1][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bc.p[0][j], acc[i][j], 0, 0, 0);
 #endif
+            BF3_FENCE();
+            if (i < 6) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[1][a], bs0, acc[a][0], 0, 0, 0);
-            acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[1][a], bs1, acc[a][1], 0, 0, 0);
-        }
+                for (int pi = 0; pi < 2; ++pi) ar[i & 1][pi] = *reinterpret_cast<const f16x8*>(pa + pi * PLA + (i + 2) * 16 * ROWB);
+            } else if (i == 6) {
+                WS_BARRIER();
+                if (next) {
+                    rdB(bn, pbn);
 #pragma unroll
-        for (int q = 1; q >= 0; --q)
+                    for (int pi = 0; pi < 2; ++pi) ar[0][pi] = *reinterpret_cast<const f16x8*>(pan + pi * PLA);
+                }
+            } else if (next) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[0][a], f.b[q][0], acc[a][0], 0, 0, 0);
-                acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[0][a], f.b[q][1], acc[a][1], 0, 0, 0);
+                for (int pi = 0; pi < 2; ++pi) ar[1][pi] = *reinterpret_cast<const f16x8*>(pan + pi * PLA + 16 * ROWB);
             }
+            BF3_FENCE();
+        }
+    };
+    // the first fragments of an item: its first stage's B set and A tiles 0 and 1
+    auto rd_first = [&](BF& f, int so) {
+        rdB(f, fb + so);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int pi = 0; pi < 2; ++pi) ar[t][pi] = *reinterpret_cast<const f16x8*>(fa + so + pi * PLA + t * 16 * ROWB);
     };
     float cmax = 0.f;
-    F4 f0, f1;
-    WS_BARRIER();
-    rd(f0, fa[0], fb[0]);
-    int cur_st = 0;
-    // EPI 4 keeps four tiles of Y in flight through its epilogue (64 registers): the first fragments of the NEXT item are then read behind
-    // the epilogue instead of under the item's last matrix instructions (their stage stays valid until this wave passes the next barrier)
+    BF b0, b1;
+    // EPI 4 keeps four tiles of Y in flight through its epilogue (64 registers): the first fragments of an item are then read at its start,
+    // behind the epilogue of the one before, instead of under that item's last matrix instructions (their stage stays valid until this
+    // wave passes the next barrier), and no fragment register is live across the epilogue
     constexpr bool DEFER_F0 = EPI == 4;
+    WS_BARRIER();
+    if (!DEFER_F0) rd_first(b0, 0);
+    int cur_st = 0;
     for (int c_item = blockIdx.x; c_item < total; c_item += G) {
         const Item cur = decode<BM, BN>(p, c_item);
-        if (DEFER_F0 && c_item != (int)blockIdx.x) rd(f0, fa[0] + cur_st * STAGE, fb[0] + cur_st * STAGE);
+        if (DEFER_F0) rd_first(b0, cur_st * STAGE);
         float zero = 0.f;
         asm volatile("" : "+v"(zero));
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+        for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = zero;
-        float bv[2] = {0.f, 0.f};
-        for (int c_k0 = cur.kbeg; c_k0 < cur.kend; c_k0 += BK) {
-            const int so = cur_st * STAGE, sn = (cur_st ^ 1) * STAGE;
-            if (c_k0 + BK >= cur.kend && p.bias && !cur.split) {
+                for (int r = 0; r < 4; ++r) acc[i][j][r] = zero;
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};
+        int c_k0 = cur.kbeg;
+        auto one = [&](const BF& bc, BF& bn) {           // the B sets alternate from step to step
+            const bool last = c_k0 + BK >= cur.kend;
+            if (last && p.bias && !cur.split) {
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int n = cur.n0 + wn + 32 * b + li;
-                    bv[b] = p.bias[(int64_t)cur.z * p.sBias + (n < p.N ? n : 0)];
+                for (int j = 0; j < 4; ++j) {
+                    const int n = cur.n0 + wn + 16 * j + l15;
+                    bv[j] = p.bias[(int64_t)cur.z * p.sBias + (n < p.N ? n : 0)];
                 }
             }
+            const int so = cur_st * STAGE, sn = (cur_st ^ 1) * STAGE;
             BF3_FENCE();
-            rd(f1, fa[1] + so, fb[1] + so);
-            mm(f0);
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {              // one fragment read behind each of the first matrix instructions
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            BF3_FENCE();
-            WS_BARRIER();
-            BF3_FENCE();
-            if (!(DEFER_F0 && c_k0 + BK >= cur.kend)) rd(f0, fa[0] + sn, fb[0] + sn);
-            mm(f1);
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            BF3_FENCE();
+            step(bc, bn, fa + so, fa + sn, fb + sn, !(DEFER_F0 && last));
             cur_st ^= 1;
+            c_k0 += BK;
+        };
+        while (c_k0 + BK < cur.kend) { one(b0, b1); one(b1, b0); }
+        if (c_k0 < cur.kend) {                           // an odd number of steps: the next item starts from set 0 again
+            one(b0, b1);
+            if (!DEFER_F0) b0 = b1;
         }
 #ifdef BF3_AB_NOEPI
-        if (lane == 0) p.C[(int64_t)cur.m0 * p.ldc + cur.n0 + w] = acc[0][0][0] + acc[1][1][1] + acc[2][0][2] + acc[3][1][3];
+        if (lane == 0) p.C[(int64_t)cur.m0 * p.ldc + cur.n0 + w] = acc[0][0][0] + acc[3][1][1] + acc[4][2][2] + acc[7][3][3];
         continue;
 #endif
         // every item: undo the operand scales (powers of two, exact).  A K slice then leaves for the slab; a whole-K item leaves through ONE
         // of three epilogues - plain (EPI 0), dact (EPI 4), head (EPI 5) - each ending the item
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+        for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] *= unscale;
+                for (int r = 0; r < 4; ++r) acc[i][j][r] *= unscale;
         if (cur.split) {                                             // slab_store's twin (gemm_splitk.h): through the helper every EPI 0 instantiation changed
-            float* o = p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * lh) * BN + wn + li;
+            float* o = p.slab + (int64_t)(cur.split - 1) * TILE + (wm + 4 * l4) * BN + wn + l15;
 #pragma unroll
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) o[(32 * a + (e & 3) + 8 * (e >> 2)) * BN + 32 * b] = acc[a][b][e];
+                    for (int e = 0; e < 16; ++e) o[(32 * a + WS_DROW(e)) * BN + 32 * b + WS_DCOL(e)] = WS_ACC(a, b, e);
             continue;
         }
         if constexpr (EPI == 0) {
@@ -951,15 +991,16 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             float* C = p.C + (int64_t)cur.z * p.sC;
             const bool full_m = cur.m0 + BM <= p.M;
             if (full_m && cur.n0 + BN <= p.N && p.act != 2) {
-                // whole tiles: every 32 x 32 tile is turned through a wave-private 5 KB LDS scratch (rows of 40 words: the two half-waves of a
-                // dword write hit disjoint banks) and leaves as FOUR 16-byte-per-lane stores of eight whole 128-byte lines each - 32 store
+                // whole tiles: every 32 x 32 region (a 2 x 2 group of accumulators) is turned through a wave-private 5 KB LDS scratch (rows of 40
+                // words; the two 16-lane row groups of a half-wave's dword write are 160 words apart: 2-way, 4 M of 53 M LDS cycles per launch
+                // at 66 752 x 2048 x 384, profiles/r29_gemm_mfma16.md) and leaves as FOUR 16-byte-per-lane stores of eight whole 128-byte lines each - 32 store
                 // instructions per wave and tile instead of 128: a wave may have 63 vector-memory operations in flight, and with four
                 // consumer waves 128 dword stores each stalled on that limit (160 of 415 us at 66 752 x 2048 x 384).
                 // Scratch: the third A plane of the stages, which mode 2 does not use (waves 0, 1 in stage 0's, 2, 3 in stage 1's).
                 // Kept apart from head's whole-tile block (row tiles outermost there): through one shared loop every plain instantiation
                 // changed and its scratch grew from 24 to 92 - 96 bytes.  The same holds for helper functions (profiles/r13_gemm_epilogues.md).
                 char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
-                float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
+                float* wr = reinterpret_cast<float*>(sc) + (4 * l4) * 40 + l15;
                 const float4* rdp = reinterpret_cast<const float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -967,7 +1008,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     for (int a = 0; a < 4; ++a) {
                         float v[16];
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
+                        for (int e = 0; e < 16; ++e) v[e] = WS_ACC(a, b, e) + WS_BV(b, e);
                         if (p.act == 1) {
 #pragma unroll
                             for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
@@ -981,7 +1022,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                             for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
                         }
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = v[e];
+                        for (int e = 0; e < 16; ++e) wr[WS_DROW(e) * 40 + WS_DCOL(e)] = v[e];
                         float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
@@ -997,53 +1038,47 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                 }
                 continue;
             }
-            // edge tiles and the accumulating form
+            // edge tiles and the accumulating form: the accumulator layout goes out as it is - column n = lane & 15 of column tile j,
+            // rows 4 (lane >> 4) + r of row tile i
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int n = cur.n0 + wn + 32 * b + li;
+            for (int j = 0; j < 4; ++j) {
+                const int n = cur.n0 + wn + 16 * j + l15;
                 if (n >= p.N) continue;
 #pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    float v[16];
+                for (int i = 0; i < 8; ++i) {
+                    float v[4];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
+                    for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bv[j];
                     if (p.act == 1) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
+                        for (int r = 0; r < 4; ++r) v[r] = elu1(v[r]);
                     }
                     if (p.act == 3) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
+                        for (int r = 0; r < 4; ++r) v[r] = softplus_nb(v[r]);
                     }
-                    const int mb = cur.m0 + wm + 32 * a + 4 * lh;
+                    const int mb = cur.m0 + wm + 16 * i + 4 * l4;
                     float* crow = C + (int64_t)mb * p.ldc + n;
                     if (p.act == 2) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int dm = (e & 3) + 8 * (e >> 2);
-                            if (mb + dm < p.M) v[e] += crow[(int64_t)dm * p.ldc];
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            if (mb + r < p.M) v[r] += crow[(int64_t)r * p.ldc];
                     }
                     if (full_m) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) crow[(int64_t)((e & 3) + 8 * (e >> 2)) * p.ldc] = v[e];
+                        for (int r = 0; r < 4; ++r) crow[(int64_t)r * p.ldc] = v[r];
                     } else {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int dm = (e & 3) + 8 * (e >> 2);
-                            if (mb + dm < p.M) crow[(int64_t)dm * p.ldc] = v[e];
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            if (mb + r < p.M) crow[(int64_t)r * p.ldc] = v[r];
                     }
-                    if (p.amaxC.slot) {
-#pragma unroll
-                        for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
-                    }
+                    if (p.amaxC.slot) cmax = fmaxf(fmaxf(cmax, fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1]))), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
                 }
             }
         } else if constexpr (EPI == 4) {
             // ---- dact: C = product * elu'(Y), column sums.  Whole tiles only (the host entry sends the rows past the last whole 256-row
             // tile elsewhere and refuses N % 128 != 0).  Two phases:
-            //   A  the Y values are loaded IN THE ACCUMULATOR LAYOUT (column = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2): a dword load
+            //   A  the Y values are loaded IN THE ACCUMULATOR LAYOUT (column = lane & 15 of column tile j, rows 4 (lane >> 4) + r of row tile i: a dword load
             //      covers two whole 128-byte lines) and multiplied into the accumulators in place, tile by tile with PF tiles of loads in
             //      flight; column sums and the magnitude come from the same registers;
             //   B  the tiles leave exactly as in the plain epilogue (LDS turn, 16-byte full-line non-temporal stores).
@@ -1058,7 +1093,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             // per-lane constants are formed HERE from the lane id (v_mbcnt) and the wave id in a scalar register: kept across the K loop
             // they were spilled
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            const int li = lane & 31, lh = lane >> 5;
+            const int l15 = lane & 15, l4 = lane >> 4;
             const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
             const int wm = (w >> 1) * 128, wn = (w & 1) * 64;
             typedef float f32x4a __attribute__((ext_vector_type(4)));
@@ -1067,7 +1102,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             // tiles leave in) and is turned INTO the accumulator layout through the wave's LDS scratch: dword loads in the accumulator
             // layout cost four times the address work per byte (128 load instructions per item and wave; measured 542 us, this form: r05_gemm.md)
             char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
-            float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
+            float* wr = reinterpret_cast<float*>(sc) + (4 * l4) * 40 + l15;
             float4* rdp = reinterpret_cast<float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
             const uint32_t ylane = (uint32_t)(((lane >> 3) * (int)p.ldaux + 4 * (lane & 7)) * 4);
             const float* ybase = p.aux + (int64_t)cur.z * p.sAux + (int64_t)(cur.m0 + wm) * p.ldaux + cur.n0 + wn;
@@ -1085,7 +1120,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     for (int g = 0; g < 4; ++g) yld(yv[t][g], ylane, yb + (int64_t)(8 * g) * p.ldaux);
                 }
             };
-            float cs[2] = {0.f, 0.f}, cmx = 0.f;
+            float cs[4] = {0.f, 0.f, 0.f, 0.f}, cmx = 0.f;
             auto mul = [&](auto TC) {
                 constexpr int t = decltype(TC)::value;
                 constexpr int a = t >> 1, b = t & 1;
@@ -1095,10 +1130,10 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                 for (int g = 0; g < 4; ++g) rdp[g * 8 * 10] = make_float4(yv[t][g].x, yv[t][g].y, yv[t][g].z, yv[t][g].w);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const float y = wr[((e & 3) + 8 * (e >> 2)) * 40];
-                    const float v = acc[a][b][e] * (y > 0.f ? 1.f : y + 1.f);
-                    acc[a][b][e] = v;
-                    cs[b] += v;
+                    const float y = wr[WS_DROW(e) * 40 + WS_DCOL(e)];
+                    const float v = WS_ACC(a, b, e) * (y > 0.f ? 1.f : y + 1.f);
+                    WS_ACC(a, b, e) = v;
+                    cs[2 * b + ((e >> 2) & 1)] += v;
                     cmx = fmaxf(cmx, __builtin_fabsf(v));
                 }
             };
@@ -1109,9 +1144,10 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             mul(std::integral_constant<int, 6>{}); mul(std::integral_constant<int, 7>{});
             if (p.red) {
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const float c = cs[b] + __shfl_xor(cs[b], 32, 64);       // the two row halves of the accumulator layout
-                    if (lh == 0) p.red[((int64_t)cur.z * p.redrows + 2 * (cur.m0 / BM) + (w >> 1)) * p.N + cur.n0 + wn + 32 * b + li] = c;
+                for (int j = 0; j < 4; ++j) {
+                    float c = cs[j] + __shfl_xor(cs[j], 16, 64);             // the four row groups of the accumulator layout
+                    c += __shfl_xor(c, 32, 64);
+                    if (l4 == 0) p.red[((int64_t)cur.z * p.redrows + 2 * (cur.m0 / BM) + (w >> 1)) * p.N + cur.n0 + wn + 16 * j + l15] = c;
                 }
             }
             amax_publish_wave(cmx, p.amaxC);                         // one conditional atomic per wave and item (a maximum carried across the K loops was spilled)
@@ -1121,7 +1157,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = acc[a][b][e];
+                    for (int e = 0; e < 16; ++e) wr[WS_DROW(e) * 40 + WS_DCOL(e)] = WS_ACC(a, b, e);
                     float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
@@ -1138,14 +1174,14 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
             if (full_m && cur.n0 + BN <= p.N) {
                 // whole tiles through the wave's LDS scratch, as in the plain epilogue
                 char* sc = lds + (w >> 1) * STAGE + 2 * PLA + (w & 1) * 5120;
-                float* wr = reinterpret_cast<float*>(sc) + (4 * lh) * 40 + li;
+                float* wr = reinterpret_cast<float*>(sc) + (4 * l4) * 40 + l15;
                 const float4* rdp = reinterpret_cast<const float4*>(sc + (lane >> 3) * 160 + (lane & 7) * 16);
                 // one 32 x 32 tile (row tile a, column block b).  In the turned form a lane holds rows 8 g + (lane >> 3), columns 4 (lane & 7) .. + 3:
                 // w3 = the output layer's weights of the lane's four columns, qr[g] += the lane's share of the row dots
                 auto tile = [&](int a, int b, const float4& w3, float (&qr)[4]) {
                     float v[16];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
+                    for (int e = 0; e < 16; ++e) v[e] = WS_ACC(a, b, e) + WS_BV(b, e);
 #pragma unroll
                     for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
                     if (p.amaxC.slot) {
@@ -1153,7 +1189,7 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                         for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
                     }
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) wr[((e & 3) + 8 * (e >> 2)) * 40] = v[e];
+                    for (int e = 0; e < 16; ++e) wr[WS_DROW(e) * 40 + WS_DCOL(e)] = v[e];
                     float* q = C + (int64_t)(cur.m0 + wm + 32 * a + (lane >> 3)) * p.ldc + cur.n0 + wn + 32 * b + 4 * (lane & 7);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
@@ -1187,54 +1223,49 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                 }
                 continue;
             }
-            // edge tiles: the accumulator layout goes out as it is - column n = li of block b, rows 4 lh + (e & 3) + 8 (e >> 2)
+            // edge tiles: the accumulator layout goes out as it is - column n = lane & 15 of column tile j, rows 4 (lane >> 4) + r of row tile i
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                float qe[16];
+            for (int i = 0; i < 8; ++i) {
+                float qe[4] = {0.f, 0.f, 0.f, 0.f};
+                const int mb = cur.m0 + wm + 16 * i + 4 * l4;
 #pragma unroll
-                for (int e = 0; e < 16; ++e) qe[e] = 0.f;
-                const int mb = cur.m0 + wm + 32 * a + 4 * lh;
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int n = cur.n0 + wn + 32 * b + li;
+                for (int j = 0; j < 4; ++j) {
+                    const int n = cur.n0 + wn + 16 * j + l15;
                     if (n >= p.N) continue;
-                    float v[16];
+                    float v[4];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = acc[a][b][e] + bv[b];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) v[e] = elu1(v[e]);
+                    for (int r = 0; r < 4; ++r) v[r] = elu1(acc[i][j][r] + bv[j]);
                     const float w3 = p.aux[(int64_t)cur.z * p.sAux + n];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) qe[e] += v[e] * w3;
+                    for (int r = 0; r < 4; ++r) qe[r] += v[r] * w3;
                     float* crow = C + (int64_t)mb * p.ldc + n;
-                    if (full_m) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) crow[(int64_t)((e & 3) + 8 * (e >> 2)) * p.ldc] = v[e];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int dm = (e & 3) + 8 * (e >> 2);
-                            if (mb + dm < p.M) crow[(int64_t)dm * p.ldc] = v[e];
-                        }
-                    }
-                    if (p.amaxC.slot) {
-#pragma unroll
-                        for (int e = 0; e < 16; e += 2) cmax = fmaxf(cmax, fmaxf(__builtin_fabsf(v[e]), __builtin_fabsf(v[e + 1])));
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        if (full_m || mb + r < p.M) crow[(int64_t)r * p.ldc] = v[r];
+                    if (p.amaxC.slot) cmax = fmaxf(fmaxf(cmax, fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1]))), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
                 }
-                float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M;     // a row's 32 columns of a block sit in the 32 lanes of a half-wave
+                float* qp = p.red + ((int64_t)cur.z * 2 * p.nt + 2 * (cur.n0 / BN) + (w & 1)) * p.M;     // a row's 64 columns of a wave sit in 16 lanes, four per lane
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    float r = qe[e];
+                for (int r = 0; r < 4; ++r) {
+                    float q = qe[r];
 #pragma unroll
-                    for (int o = 1; o < 32; o <<= 1) r += __shfl_xor(r, o, 64);
-                    const int m = mb + (e & 3) + 8 * (e >> 2);
-                    if (li == 0 && m < p.M) qp[m] = r;
+                    for (int o = 1; o < 16; o <<= 1) q += __shfl_xor(q, o, 64);
+                    if (l15 == 0 && mb + r < p.M) qp[mb + r] = q;
                 }
             }
         }
     }
+#undef WS_ACC
+#undef WS_DROW
+#undef WS_DCOL
+#undef WS_BV
     amax_publish_wave(cmax, p.amaxC);
+#ifdef BF3_AB_CLOCK
+    if (tid == 0) {
+        g_bf3_clock[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - ck_t0;
+        g_bf3_clock[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - ck_r0;
+    }
+#endif
 }
 
 // one flag table per kernel instantiation (launch_big_lds)
