@@ -401,7 +401,14 @@ int resel_sumsq(const float* x, int64_t n, float* out, void* workspace, resel_st
  * Replaces `activation(linear(x))` of reference models/rnn_base.py:462-474 (nn.Linear / EnsembleLinear followed by the
  * per-layer activation module) for act = ELU, and the bias add of EnsembleLinear (ensemble_linear_model.py:60-67).
  * y [rows, C] contiguous, rows grouped in rows / rows_per_seg segments with one bias row [C] each (bias [nseg, C]).
- * fwd (in place): y <- act(y + bias);  act: 0 = identity, 1 = ELU(alpha = 1).
+ * fwd (in place): y <- act(y + bias);  act: 0 = identity, 1 = ELU(alpha = 1), and the other activations of the reference's ACTIVATIONS
+ *      table that are derivable from their output (no ABI change: codes the entries used to refuse):
+ *          code  activation                        act'(.) from the output a
+ *            6   relu        max(v, 0)             a > 0 ? 1 : 0
+ *            7   leaky_relu  v > 0 ? v : 0.01f v   a > 0 ? 1 : 0.01     (torch's default slope; an fp32 product: torch's bits)
+ *            8   tanh                              1 - a^2              (v_exp / v_rcp; tanh(+-0) = +-0, exactly +-1 past |v| = 44)
+ *            9   sigmoid                           a (1 - a)            (exactly 0 below v = -88.8, exactly 1 above 17.4)
+ *      Any other code (2 .. 5 belong to the GEMM entries) is RESEL_EINVAL before anything is enqueued.
  * bwd (from the forward OUTPUT a): gy = g * act'(.), dbias[nseg, C] = per-segment column sums of gy (dbias may be NULL).  g has row
  *      stride ldg >= C (a column block of a wider gradient is read in place: ABI 7), a has row stride lda >= C (a block of a row buffer
  *      that its producing GEMM wrote in place: ABI 8), gy is dense; gy NULL with act == 0 = column sums only.
@@ -430,7 +437,10 @@ int resel_ensemble_head_bwd(const float* gq, const float* a, const float* w3, fl
  *   dgrad    dx = dy W                 A = dy (1), B = W (0)      EnsembleLinear (models/ensemble_linear_model.py:36-49)
  *   wgrad    dW = dy^T x               A = dy (0), B = x (0)      K = number of tokens: split over blocks, partial tiles summed in
  *                                                                  a fixed order (workspace: resel_gemm_f32_workspace_bytes)
- * act: 0 none, 1 ELU, 2 accumulate (C += product + bias: the accumulating form of an input gradient; no activation), 3 softplus (resel_gemm_f32x only).
+ * act: 0 none, 1 ELU, 2 accumulate (C += product + bias: the accumulating form of an input gradient; no activation), 3 softplus (resel_gemm_f32x only),
+ *      6 relu, 7 leaky_relu (slope 0.01), 8 tanh, 9 sigmoid: the code table of resel_bias_act_fwd, in every plain epilogue (the third edition
+ *      compiles them as an instantiation of its own); amax_c is the magnitude of the stored, activated values, as for ELU.  4 / 5 are the fused
+ *      entries' (resel_gemm_f32_dact / _head: ELU only) and are refused here, like anything else.
  * EVERY extent and alignment is taken (round 6; no ABI change): the matrix-core kernels need the contiguous extent of each operand (K or rows) to be a
  * multiple of 4, 16-byte aligned rows and row strides < 2^22; operands that are not - the 6-wide TD3 / discrete heads and their gradients, a rank-2
  * dt_proj, odd action counts - and the M <= 8 rows of a rollout step against a whole weight matrix (models/rnn_base.py single-step branch,

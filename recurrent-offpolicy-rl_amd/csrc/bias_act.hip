@@ -1,7 +1,8 @@
 // Bias + activation tail of the fc / efc-E layers, fused around the library GEMM (HBM-bound, one pass each way).
 //   forward  (in place on the GEMM output):   a[r, c] = act(y[r, c] + bias[seg(r), c])
 //   backward (from the OUTPUT, so the pre-activation is never kept):
-//            gy[r, c] = g[r, c] * act'(.)        ELU: a > 0 ? 1 : a + 1
+//            gy[r, c] = g[r, c] * act'(.)        ELU: a > 0 ? 1 : a + 1;  relu: a > 0 ? 1 : 0;  leaky_relu: a > 0 ? 1 : 0.01;
+//                                                tanh: 1 - a^2;  sigmoid: a (1 - a)
 //            dbias[s, c] = sum_{r in segment s} gy[r, c]   (per-block partials -> colsum_kernel, fixed order, no atomics)
 // Rows are grouped in `nseg` segments of `rows_per_seg` consecutive rows, each with its own bias row: nseg = E for the
 // per-member layers of the ensemble critic ([E, M, out] contiguous, reference EnsembleLinear bias [E, 1, out],
@@ -16,7 +17,18 @@ using namespace resel;
 constexpr int BWD_ROWS = 128;        // rows per backward block of the head kernel; bias_act_bwd picks 128 / 64 / 32 (block_rows) to fill the chip
 
 __device__ __forceinline__ float elu_(float x) { return x > 0.f ? x : fast_exp(x) - 1.f; }
+// the activation codes of resel_bias_act_fwd / _bwd: 0 none, 1 ELU, 6 relu, 7 leaky_relu (slope 0.01), 8 tanh, 9 sigmoid
+inline bool act_ok(int act) { return act == 0 || act == 1 || (act >= 6 && act <= 9); }
+// codes 6 .. 9 run instantiations of their own (OTHER = true): the kernels of codes 0 / 1 stay the ones the ELU stacks have always run
+__device__ __forceinline__ float act_fwd(float x, int act) {
+    return act == 6 ? relu_(x) : act == 7 ? leaky_relu_(x) : act == 8 ? tanh_(x) : sigmoidf_(x);
+}
+// act'(.) from the layer OUTPUT a
+__device__ __forceinline__ float act_slope(float a, int act) {
+    return act == 6 ? (a > 0.f ? 1.f : 0.f) : act == 7 ? (a > 0.f ? 1.f : 0.01f) : act == 8 ? 1.f - a * a : a * (1.f - a);
+}
 
+template <bool OTHER>
 __global__ __launch_bounds__(256) void bias_act_fwd_kernel(float* __restrict__ y, const float* __restrict__ bias, int64_t rows,
                                                            int C, int64_t rows_per_seg, int act) {
     const int c4n = C / 4;
@@ -29,12 +41,17 @@ __global__ __launch_bounds__(256) void bias_act_fwd_kernel(float* __restrict__ y
             const float4 b = ld4(bias + (r / rows_per_seg) * C + c);
             v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
         }
-        if (act == 1) { v.x = elu_(v.x); v.y = elu_(v.y); v.z = elu_(v.z); v.w = elu_(v.w); }
+        if constexpr (OTHER) {
+            v.x = act_fwd(v.x, act); v.y = act_fwd(v.y, act); v.z = act_fwd(v.z, act); v.w = act_fwd(v.w, act);
+        } else {
+            if (act == 1) { v.x = elu_(v.x); v.y = elu_(v.y); v.z = elu_(v.z); v.w = elu_(v.w); }
+        }
         st4(y + r * C + c, v);
     }
 }
 
 // grid = (row blocks inside a segment, column blocks of 256 floats, segments); 256 threads = 64 float4 columns x 4 row lanes
+template <bool OTHER>
 __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const float* __restrict__ g, int64_t ldg, const float* __restrict__ a, int64_t lda,
                                                            float* __restrict__ gy, float* __restrict__ db_part,
                                                            int C, int64_t rows_per_seg, int act, int nrb, int brows, AmaxOut amax) {
@@ -50,7 +67,10 @@ __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const float* __restri
         for (int64_t r = r0 + rl; r < r1; r += 4) {
             const int64_t o = (seg * rows_per_seg + r) * C + c;
             float4 v = ld4(g + (seg * rows_per_seg + r) * ldg + c);          // g may be a column block of a wider gradient (row stride ldg)
-            if (act == 1) {
+            if constexpr (OTHER) {
+                const float4 av = ld4(a + (seg * rows_per_seg + r) * lda + c);
+                v.x *= act_slope(av.x, act); v.y *= act_slope(av.y, act); v.z *= act_slope(av.z, act); v.w *= act_slope(av.w, act);
+            } else if (act == 1) {
                 const float4 av = ld4(a + (seg * rows_per_seg + r) * lda + c);   // so may the activation (a block of a row buffer)
                 v.x *= av.x > 0.f ? 1.f : av.x + 1.f; v.y *= av.y > 0.f ? 1.f : av.y + 1.f;
                 v.z *= av.z > 0.f ? 1.f : av.z + 1.f; v.w *= av.w > 0.f ? 1.f : av.w + 1.f;
@@ -152,11 +172,12 @@ inline bool shape_ok(int64_t rows, int C, int64_t rows_per_seg) {
 
 extern "C" int resel_bias_act_fwd(float* y, const float* bias, int64_t rows, int C, int64_t rows_per_seg, int act,
                                   resel_stream_t stream) {
-    if (!y || !shape_ok(rows, C, rows_per_seg) || act < 0 || act > 1 || !aligned16(y) || (bias && !aligned16(bias))) return RESEL_EINVAL;
+    if (!y || !shape_ok(rows, C, rows_per_seg) || !act_ok(act) || !aligned16(y) || (bias && !aligned16(bias))) return RESEL_EINVAL;
     const int64_t n4 = rows * (C / 4);
     const int64_t want = (n4 + 255) / 256;
     const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);      // <= 32 blocks per CU, grid-stride beyond
-    hipLaunchKernelGGL(bias_act_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, bias, rows, C, rows_per_seg, act);
+    hipLaunchKernelGGL(act >= 6 ? bias_act_fwd_kernel<true> : bias_act_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, bias, rows, C,
+                       rows_per_seg, act);
     return launch_status();
 }
 
@@ -168,7 +189,7 @@ extern "C" size_t resel_bias_act_bwd_workspace_bytes(int64_t rows, int C, int64_
 extern "C" int resel_bias_act_bwd(const float* g, int64_t ldg, const float* a, int64_t lda, float* gy, float* dbias, void* workspace, int64_t rows, int C,
                                   int64_t rows_per_seg, int act, void* amax_gy, unsigned amax_epoch, resel_stream_t stream) {
     if (amax_gy && (reinterpret_cast<uintptr_t>(amax_gy) & 7u)) return RESEL_EINVAL;
-    if (!g || !shape_ok(rows, C, rows_per_seg) || act < 0 || act > 1 || (act == 1 && (!a || !gy)) || (dbias && !workspace) || ldg < C || (ldg & 3))
+    if (!g || !shape_ok(rows, C, rows_per_seg) || !act_ok(act) || (act != 0 && (!a || !gy)) || (dbias && !workspace) || ldg < C || (ldg & 3))
         return RESEL_EINVAL;
     if (a && (lda < C || (lda & 3))) return RESEL_EINVAL;
     if (!aligned16(g) || (gy && !aligned16(gy)) || (a && !aligned16(a)) || (workspace && !aligned16(workspace))) return RESEL_EINVAL;
@@ -176,8 +197,8 @@ extern "C" int resel_bias_act_bwd(const float* g, int64_t ldg, const float* a, i
     const int nseg = (int)(rows / rows_per_seg), nrb = row_blocks_of(rows_per_seg, brows);
     hipStream_t s = (hipStream_t)stream;
     float* part = dbias ? (float*)workspace : nullptr;
-    hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(nrb, (C + 255) / 256, nseg), dim3(256), 0, s, g, ldg, a, lda, gy, part, C, rows_per_seg, act, nrb, brows,
-                       AmaxOut{(unsigned long long*)amax_gy, amax_epoch});
+    hipLaunchKernelGGL(act >= 6 ? bias_act_bwd_kernel<true> : bias_act_bwd_kernel<false>, dim3(nrb, (C + 255) / 256, nseg), dim3(256), 0, s, g, ldg, a, lda, gy,
+                       part, C, rows_per_seg, act, nrb, brows, AmaxOut{(unsigned long long*)amax_gy, amax_epoch});
     if (dbias) launch_colsum(part, C, nrb, C, dbias, s, 1, 0, nseg);      // dbias[sg, :] = sum over the segment's row blocks
     return launch_status();
 }

@@ -18,7 +18,7 @@ struct AnyParams {
     const float *B, *bias;
     void* C;
     int64_t a_rs, a_cs, b_rs, b_cs, ldc, sA, sB, sC, sBias;
-    int M, N, K, act;            // act: 0 none, 1 ELU, 2 C += product (+ bias), 3 softplus
+    int M, N, K, act;            // act: 0 none, 1 ELU, 2 C += product (+ bias), 3 softplus, 6 relu, 7 leaky_relu, 8 tanh, 9 sigmoid
     int kchunk, nz;              // K elements per grid.z slice; nz > 1: raw partial tiles go to `part` [nz][batch][M][N]
     float* part;
     AmaxOut amax;
@@ -38,6 +38,7 @@ __device__ __forceinline__ void store_out(const AnyParams& p, int z, int m, int 
     if (p.bias) v += (RND & RND_B) ? rbf(p.bias[(int64_t)z * p.sBias + n]) : p.bias[(int64_t)z * p.sBias + n];
     if (p.act == 1) v = elu1(v);
     if (p.act == 3) v = softplus_nb(v);
+    if (p.act >= 6) v = p.act == 6 ? relu_(v) : p.act == 7 ? leaky_relu_(v) : p.act == 8 ? tanh_(v) : sigmoidf_(v);
     if (RND & OUT_BF16) {
         __bf16* c = reinterpret_cast<__bf16*>(p.C) + (int64_t)z * p.sC + (int64_t)m * p.ldc + n;
         *c = (__bf16)v;

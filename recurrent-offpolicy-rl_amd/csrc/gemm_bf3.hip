@@ -25,7 +25,7 @@
 // Blocks are persistent (256 = one per CU) and walk items exactly as in gemm_f32.hip: whole tiles, and K slices for the last
 // partly filled round and for weight gradients, summed by a fix-up kernel in a fixed order (deterministic, no atomics): the item
 // walk, the slice plan and the fix-up kernel are gemm_splitk.h, shared with gemm_f32.hip.
-// SPLIT of gemm_bf3_kernel is 2, 3 or 6; gemm_ws_kernel is mode 2 only (EPI: 0 the plain epilogues, 4 / 5 the fused ones).
+// SPLIT of gemm_bf3_kernel is 2, 3 or 6; gemm_ws_kernel is mode 2 only (EPI: 0 / 6 the plain epilogues, 4 / 5 the fused ones).
 #include "gemm_splitk.h"
 #include "gemm_call.h"
 
@@ -616,6 +616,21 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 #pragma unroll
                         for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
                     }
+                    if (p.act >= 6) {                                // relu, leaky_relu, tanh, sigmoid (the dense stacks' other activations)
+                        if (p.act == 6) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = relu_(v[e]);
+                        } else if (p.act == 7) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = leaky_relu_(v[e]);
+                        } else if (p.act == 8) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = tanh_(v[e]);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = sigmoidf_(v[e]);
+                        }
+                    }
                     const int mb = cur.m0 + wm + 32 * a + 4 * lh;
                     float* crow = C + (int64_t)mb * p.ldc + n;
                     if (p.act == 2) {                                // C += product (the accumulating form of an input gradient)
@@ -677,7 +692,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf3_kernel(Params p) {
 //     stores of eight whole 128-byte lines: 32 store instructions per wave and tile instead of 128 (a wave may have 63 in flight);
 //     edge tiles and the accumulating form leave in the accumulator layout, as in the second edition;
 //   * after the K loop a K slice goes to the slab and a whole-K item through ONE of three separate epilogues, chosen at compile time:
-//     EPI 0 plain (bias, Params::act 0 .. 3), EPI 4 dact (whole tiles only: the host entry refuses other shapes), EPI 5 head (bias, ELU,
+//     EPI 0 plain (bias, Params::act 0 .. 3), EPI 6 plain with act 6 .. 9 (relu, leaky_relu, tanh, sigmoid), EPI 4 dact (whole tiles only: the host entry refuses other shapes), EPI 5 head (bias, ELU,
 //     row dots; whole and edge tiles).  Each spells out its own tile loop: see the note at EPI 0's whole-tile block.
 // 256 registers, 24-32 bytes of scratch (EPI 5: 84-88, EPI 4: none), two waves per SIMD, one block per CU, persistent.  Measured against the second edition (same box,
 // us): fwd [T,384] -> 256 77 -> 67, [T,256] -> 256 55 -> 48, [T,256] -> 1024 171 -> 150, [T,384] -> 2048 420 -> 365.
@@ -689,7 +704,7 @@ constexpr int WS_LDS = 2 * STAGE;
 
 template <bool AKC, bool BKC, int EPI = 0>
 __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
-    static_assert(EPI == 0 || EPI == 4 || EPI == 5, "EPI: 0 plain, 4 dact, 5 head (the act codes of the fused host entries)");
+    static_assert(EPI == 0 || EPI == 4 || EPI == 5 || EPI == 6, "EPI: 0 plain, 6 plain with act 6 .. 9, 4 dact, 5 head (the act codes of the fused host entries)");
     extern __shared__ __attribute__((aligned(16))) char lds[];           // 2 stages
     const int tid = threadIdx.x;
     const int total = p.nfull + p.nsplit * p.nsl;
@@ -986,8 +1001,10 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     for (int e = 0; e < 16; ++e) o[(32 * a + WS_DROW(e)) * BN + 32 * b + WS_DCOL(e)] = WS_ACC(a, b, e);
             continue;
         }
-        if constexpr (EPI == 0) {
-            // ---- plain: bias, p.act (ELU / accumulate / softplus), exactly as before the fused forms existed
+        if constexpr (EPI == 0 || EPI == 6) {
+            // ---- plain: bias, p.act (ELU / accumulate / softplus), exactly as before the fused forms existed.  EPI 6 is the same epilogue for
+            // act 6 .. 9 (relu, leaky_relu, tanh, sigmoid): spelled as run-time branches next to act 1 / 3, even relu alone took the scratch of
+            // every EPI 0 instantiation from 24-32 to 72-76 bytes (profiles/r30_dense_activations.md); compiled apart, EPI 0 is untouched.
             float* C = p.C + (int64_t)cur.z * p.sC;
             const bool full_m = cur.m0 + BM <= p.M;
             if (full_m && cur.n0 + BN <= p.N && p.act != 2) {
@@ -1016,6 +1033,21 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                         if (p.act == 3) {
 #pragma unroll
                             for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
+                        }
+                        if constexpr (EPI == 6) {                       // relu, leaky_relu, tanh, sigmoid: an instantiation of their own (note above)
+                            if (p.act == 6) {
+#pragma unroll
+                                for (int e = 0; e < 16; ++e) v[e] = relu_(v[e]);
+                            } else if (p.act == 7) {
+#pragma unroll
+                                for (int e = 0; e < 16; ++e) v[e] = leaky_relu_(v[e]);
+                            } else if (p.act == 8) {
+#pragma unroll
+                                for (int e = 0; e < 16; ++e) v[e] = tanh_(v[e]);
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < 16; ++e) v[e] = sigmoidf_(v[e]);
+                            }
                         }
                         if (p.amaxC.slot) {
 #pragma unroll
@@ -1056,6 +1088,10 @@ __global__ __launch_bounds__(NTH_WS, 1) void gemm_ws_kernel(Params p) {
                     if (p.act == 3) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = softplus_nb(v[r]);
+                    }
+                    if constexpr (EPI == 6) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = p.act == 6 ? relu_(v[r]) : p.act == 7 ? leaky_relu_(v[r]) : p.act == 8 ? tanh_(v[r]) : sigmoidf_(v[r]);
                     }
                     const int mb = cur.m0 + wm + 16 * i + 4 * l4;
                     float* crow = C + (int64_t)mb * p.ldc + n;
@@ -1307,7 +1343,7 @@ int gemm_bf3_launch(const GemmCall& c, int split, const GemmFused& fused) {
     if (split == 2 && (!c.amax_a || !c.amax_b)) return RESEL_EINVAL;
     const int M = c.M, N = c.N, K = c.K, act = c.act;
     Plan pl = make_plan<BM, BN, GRID>(M, N, K, c.batch);
-    if (act >= 4) {                                  // every tile whole: the epilogue reductions are written per (tile, wave), no K slices
+    if (act == 4 || act == 5) {                      // every tile whole: the epilogue reductions are written per (tile, wave), no K slices
         if (split != 2 || !gemm_bf3_fused_ok(M, N, K) || !fused.aux) return RESEL_EINVAL;
         if (act == 4 && (M % BM || N % BN)) return RESEL_EINVAL;          // the act 4 epilogue has no edge form (resel_gemm_f32_dact splits the rows)
         if (!c.a_kcontig) return RESEL_EINVAL;                            // the layouts the trainer uses: A [rows][K]; B either way
@@ -1323,9 +1359,9 @@ int gemm_bf3_launch(const GemmCall& c, int split, const GemmFused& fused) {
     const int rc = with_layout(c.a_kcontig, c.b_kcontig, [&](auto akc, auto bkc) {
         constexpr bool AKC = akc.value, BKC = bkc.value;
         if constexpr (AKC) {
-            if (act >= 4) return act == 4 ? launch_ws<true, BKC, 4>(p, grid, c.s) : launch_ws<true, BKC, 5>(p, grid, c.s);
+            if (act == 4 || act == 5) return act == 4 ? launch_ws<true, BKC, 4>(p, grid, c.s) : launch_ws<true, BKC, 5>(p, grid, c.s);
         }
-        if (third) return launch_ws<AKC, BKC>(p, grid, c.s);
+        if (third) return act >= 6 ? launch_ws<AKC, BKC, 6>(p, grid, c.s) : launch_ws<AKC, BKC>(p, grid, c.s);
         if (split == 3) return launch_one<AKC, BKC, 3>(p, grid, c.s);
         if (split == 2) return launch_one<AKC, BKC, 2>(p, grid, c.s);
         return launch_one<AKC, BKC, 6>(p, grid, c.s);

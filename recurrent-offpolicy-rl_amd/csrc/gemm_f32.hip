@@ -52,7 +52,7 @@ struct GemmParams {
     float *C, *slab;
     int64_t lda, ldb, ldc, sA, sB, sC, sBias;    // leading dimensions (floats) and per-batch strides
     int M, N, K;
-    int act;                                      // 0 none, 1 ELU, 2 C += product, 3 softplus
+    int act;                                      // 0 none, 1 ELU, 2 C += product, 3 softplus, 6 relu, 7 leaky_relu, 8 tanh, 9 sigmoid
     int mt, nt;                                   // tiles along m and n
     int nfull;                                    // items [0, nfull): whole tiles; then nsplit tiles x nsl K slices of kslice
     int nsplit, nsl, kslice;
@@ -465,6 +465,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
 #pragma unroll
                         for (int e = 0; e < 16; ++e) v[e] = softplus_nb(v[e]);
                     }
+                    if (p.act >= 6) {                                // relu, leaky_relu, tanh, sigmoid (the dense stacks' other activations)
+                        if (p.act == 6) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = relu_(v[e]);
+                        } else if (p.act == 7) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = leaky_relu_(v[e]);
+                        } else if (p.act == 8) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = tanh_(v[e]);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) v[e] = sigmoidf_(v[e]);
+                        }
+                    }
                     const int mb = cur.m0 + wm + 32 * a + 4 * lh;
                     float* crow = C + (int64_t)mb * p.ldc + n;
                     if (p.act == 2) {                                // C += product (the accumulating form of an input gradient)
@@ -549,7 +564,7 @@ int gemm_first_launch(const GemmCall& c, int split) {
 }
 // validate, route, launch: resel_gemm_f32x, and the tail rows of resel_gemm_f32_dact
 int gemm_run(const GemmCall& c, int split) {
-    if (!call_valid(c) || c.act < 0 || c.act > 3) return RESEL_EINVAL;
+    if (!call_valid(c) || c.act < 0 || (c.act > 3 && c.act < 6) || c.act > 9) return RESEL_EINVAL;       // 4 / 5 are the fused entries' own
     const Route r = gemm_route(c, split);
     switch (r.family) {
         case Family::rows: case Family::tiles: return gemm_any_launch(c, 0);

@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void gemm_fixup_kernel(P p) {
             float x = o[j] + (p.bias ? p.bias[(int64_t)z * p.sBias + n + j] : 0.f);
             if (p.act == 1) x = elu1(x);
             if (p.act == 3) x = softplus_nb(x);
+            if (p.act >= 6) x = p.act == 6 ? relu_(x) : p.act == 7 ? leaky_relu_(x) : p.act == 8 ? tanh_(x) : sigmoidf_(x);
             if (p.act == 2) x += c[j];
             c[j] = x;
             cmax = fmaxf(cmax, __builtin_fabsf(x));

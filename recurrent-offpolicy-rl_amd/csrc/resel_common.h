@@ -23,6 +23,20 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return fast_rcp(1.0f + fast_exp(-x)); }
+// Activation codes 6 .. 9 of the plain GEMM epilogues and of bias_act (include/resel_hip.h): relu, leaky_relu (torch's default
+// slope, an fp32 product: torch's bits), tanh, sigmoid (sigmoidf_: exp(-x) overflows to inf at x < -88.7 and v_rcp_f32 gives 0).
+__device__ __forceinline__ float relu_(float x) { return fmaxf(x, 0.0f); }
+__device__ __forceinline__ float leaky_relu_(float x) { return x > 0.0f ? x : x * 0.01f; }
+// tanh |x| = (1 - e) / (1 + e), e = exp(-2 |x|): e underflows to 0 past |x| = 44 (exactly 1).  Below 0.02 the difference 1 - e keeps
+// only e's absolute error (6e-8 against 0.04), so the series x - x^3 / 3 stands in (next term 2 x^4 / 15 < 2.2e-8 relative) and
+// tanh(+-0) = +-0, tanh(1e-30) = 1e-30.  Branch-free like softplus_nb: both sides are computed.
+__device__ __forceinline__ float tanh_(float x) {
+    const float ax = __builtin_fabsf(x);
+    const float e = __builtin_amdgcn_exp2f(-2.0f * RESEL_LOG2E * ax);
+    const float t = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
+    const float s = __builtin_fmaf(ax * ax, ax * (-1.0f / 3.0f), ax);
+    return __builtin_copysignf(ax < 0.02f ? s : t, x);
+}
 __device__ __forceinline__ float siluf_(float x) { return x * fast_rcp(1.0f + fast_exp(-x)); }
 // d/dx [x * sigmoid(x)] = s * (1 + x * (1 - s))
 __device__ __forceinline__ float dsiluf_(float x) {

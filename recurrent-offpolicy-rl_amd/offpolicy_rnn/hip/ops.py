@@ -1368,10 +1368,33 @@ def guard_apply_slots(slots, world, guard):
 
 
 # ---------------------------------------------------------------------------------------------- bias + activation tail
-ACT_IDS = {None: 0, 'linear': 0, 'elu': 1}
+# codes 6 .. 9: the dense stacks' other activations (leaky_relu: torch's default slope 0.01); 4 / 5 are the fused critic forms' own entries
+ACT_IDS = {None: 0, 'linear': 0, 'elu': 1, 'relu': 6, 'leaky_relu': 7, 'tanh': 8, 'sigmoid': 9}
 GEMM_SOFTPLUS = 'softplus'           # resel_gemm_f32x only: softplus(product + bias) (epilogue code 3)
 GEMM_ACCUMULATE = 'accumulate'       # resel_gemm_f32 only: C += product (epilogue code 2)
-GEMM_EPILOGUES = {None: 0, 'linear': 0, 'elu': 1, GEMM_ACCUMULATE: 2, GEMM_SOFTPLUS: 3}      # `act` of resel_gemm_f32x (ACT_IDS: the two bias_act knows)
+GEMM_EPILOGUES = {None: 0, 'linear': 0, 'elu': 1, GEMM_ACCUMULATE: 2, GEMM_SOFTPLUS: 3,       # `act` of resel_gemm_f32x (ACT_IDS: the ones bias_act knows)
+                  'relu': 6, 'leaky_relu': 7, 'tanh': 8, 'sigmoid': 9}
+
+
+def act_fused_on():
+    """RESEL_ACT_FUSED (read per call so that one process can run both routes): relu, leaky_relu, tanh and sigmoid behind an fc / efc-E
+    layer ride in the layer's GEMM epilogue like ELU (default); 0 = the torch modules of before.  ELU is not affected."""
+    v = os.environ.get('RESEL_ACT_FUSED', '1')
+    if v not in ('0', '1'):
+        raise ValueError(f'RESEL_ACT_FUSED={v!r}: 0 or 1')
+    return v == '1'
+
+
+def dense_act_name(act_mod, x):
+    """The epilogue name of the activation module behind an fc / efc-E layer whose input is x, or None when the module stays a module:
+    a plain ELU always (as before); nn.ReLU, nn.LeakyReLU at torch's default slope, nn.Tanh, nn.Sigmoid on an fp32 GPU pass while
+    RESEL_ACT_FUSED is on.  (gelu is not derivable from its output; another slope has no code.)"""
+    if isinstance(act_mod, torch.nn.ELU):
+        return 'elu' if act_mod.alpha == 1.0 else None
+    name = {torch.nn.ReLU: 'relu', torch.nn.LeakyReLU: 'leaky_relu', torch.nn.Tanh: 'tanh', torch.nn.Sigmoid: 'sigmoid'}.get(type(act_mod))
+    if name is None or (name == 'leaky_relu' and act_mod.negative_slope != 0.01):
+        return None
+    return name if (x.is_cuda and x.dtype == torch.float32 and act_fused_on()) else None
 
 
 @torch.no_grad()

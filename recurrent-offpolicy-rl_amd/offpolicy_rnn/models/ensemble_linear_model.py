@@ -289,7 +289,8 @@ class EnsembleLinear(nn.Module):
         return self.weight.index_select(0, self.member_index), None if b is None else b.index_select(0, self.member_index)
 
     def forward(self, x: torch.Tensor, act: str = None, grad_part=None) -> torch.Tensor:
-        """act: None, or 'elu' to fuse the layer's activation module into the bias pass (RNNBase.forward does so).
+        """act: None, or 'elu' / 'relu' / 'leaky_relu' / 'tanh' / 'sigmoid' (`ops.ACT_IDS`) to fuse the layer's activation module into the
+        GEMM epilogue (RNNBase.forward does so).
         grad_part = (x_part, col0): x carries no graph of its own; only its column block x_part is differentiated."""
         W, b = self.active_params()
         E, n_in, n_out = W.shape

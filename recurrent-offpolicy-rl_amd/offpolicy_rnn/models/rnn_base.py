@@ -324,16 +324,17 @@ class RNNBase(torch.nn.Module):
         if ind + 2 == n_layers and head_fusable(layer, act, self.layer_list[ind + 1], self.activation_list[ind + 1], x):
             x = ensemble_head(layer, self.layer_list[ind + 1], x)
             return x, 1, True
-        # plain ELU behind fc / efc-E: fused into the layer's bias pass (one in-place kernel; backward from the output)
-        if isinstance(act, torch.nn.ELU) and act.alpha == 1.0 and isinstance(layer, (EnsembleLinear, torch.nn.Linear)) \
-                and x.dtype == torch.float32:
+        # a fusable activation behind fc / efc-E - a plain ELU; on fp32 GPU passes also relu, leaky_relu (slope 0.01), tanh, sigmoid
+        # (`ops.dense_act_name`, RESEL_ACT_FUSED) - rides in the layer's GEMM epilogue; the backward runs from the output
+        name = ops.dense_act_name(act, x) if isinstance(layer, (EnsembleLinear, torch.nn.Linear)) and x.dtype == torch.float32 else None
+        if name is not None:
             if isinstance(layer, EnsembleLinear):
-                x = layer(x, act='elu', grad_part=first_grad_part if ind == 0 else None)
+                x = layer(x, act=name, grad_part=first_grad_part if ind == 0 else None)
             else:
                 assert not (ind == 0 and first_grad_part is not None)
-                x = ops.linear_act(x, layer.weight, layer.bias, 'elu', dest=out_dest if ind == n_layers - 1 else None)
+                x = ops.linear_act(x, layer.weight, layer.bias, name, dest=out_dest if ind == n_layers - 1 else None)
             return x, 0, True
-        assert not (ind == 0 and first_grad_part is not None), 'first_grad_part needs an efc first layer with ELU'
+        assert not (ind == 0 and first_grad_part is not None), 'first_grad_part needs an efc first layer with a fusable activation'
 
         if isinstance(layer, torch.nn.Linear):                    # the bias rides in the GEMM epilogue (every pass: whole trajectories and rollout steps)
             x = ops.linear_act(x, layer.weight, layer.bias, None, dest=out_dest if ind == n_layers - 1 else None)

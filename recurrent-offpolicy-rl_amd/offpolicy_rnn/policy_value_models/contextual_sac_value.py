@@ -82,7 +82,14 @@ class ContextualSACValue(ContextualModel):
         return (self.separate_encoder and isinstance(self.state_input_encoder, torch.nn.Linear)
                 and not self.state_input_encoder.weight.requires_grad and not self.action_input_encoder.weight.requires_grad
                 and isinstance(first, EnsembleLinear) and not first.weight.requires_grad
-                and isinstance(self.uni_network.activation_list[0], torch.nn.ELU) and len(self.uni_network.layer_list) > 1)
+                and self._first_act_fusable(first) and len(self.uni_network.layer_list) > 1)
+
+    def _first_act_fusable(self, first) -> bool:
+        """The head's first activation rides in its GEMM epilogue (`RNNBase._dense_step`): ELU as before, relu / leaky_relu / tanh / sigmoid
+        on the GPU while RESEL_ACT_FUSED is on."""
+        from ..hip import ops
+        act = self.uni_network.activation_list[0]
+        return isinstance(act, torch.nn.ELU) or ops.dense_act_name(act, first.weight) is not None
 
     def forward_embedding(self, state, lst_state, lst_action, rnn_memory, reward):
         return self.get_embedding(self.get_embedding_input(state, lst_state, lst_action, reward), rnn_memory)

@@ -8,8 +8,9 @@ import re, sys
 s = open(sys.argv[1]).read()
 bad = 0
 KERNEL = r'^(_ZN12_GLOBAL__N_114gemm_ws_kernelILb([01])ELb([01])ELi(\d+)EE\w+):'
-# (A [rows][K], B [rows][K], epilogue): the four layouts of the plain epilogue, dact (4) and head (5) with A [rows][K] and B either way
-EXPECTED = sorted([(a, b, 0) for a in (0, 1) for b in (0, 1)] + [(1, b, e) for e in (4, 5) for b in (0, 1)])
+# (A [rows][K], B [rows][K], epilogue): the four layouts of the plain epilogue (0; 6: the same with the activation codes 6 .. 9), dact (4) and
+# head (5) with A [rows][K] and B either way
+EXPECTED = sorted([(a, b, e) for e in (0, 6) for a in (0, 1) for b in (0, 1)] + [(1, b, e) for e in (4, 5) for b in (0, 1)])
 producers, consumers = [], []
 for m in re.finditer(KERNEL, s, re.M):
     label = 'gemm_ws_kernel<%s, %s, %s>' % m.group(2, 3, 4)
