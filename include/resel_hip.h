@@ -245,7 +245,7 @@ int resel_gru_multi_form(int n_net, int B, int H);
  * :107-112).  *** flash_attn is an un-vendored dependency: semantics restated (softmax(q k^T * scale - slope_h (i - j)), j <= i),
  * parity unpinned ***
  * qkv: [T, 3, H, hd] bf16 packed tokens (q | k | v); cu_seqlens: int32 [S + 1] device; slopes: [H] fp32 or NULL;
- * out: [T, H, hd] bf16; lse: [H, T] fp32 (base-2 log-sum-exp, saved for the backward).  hd in {32, 64}; max_seqlen bounds
+ * out: [T, H, hd] bf16; lse: [H, T] fp32 (base-2 log-sum-exp, saved for the backward).  hd in {32, 64, 128}; max_seqlen bounds
  * the grid.  Backward: dqkv [T, 3, H, hd] bf16 (fully overwritten); workspace resel_attn_varlen_bwd_workspace_bytes().
  * Forward workspace (resel_attn_varlen_fwd_workspace_bytes(), may be NULL): holds the device-built work list - the real
  * (sequence, 128-token block) items of the ragged batch, longest first - that the kernels' workgroups take their work from;
@@ -290,6 +290,16 @@ int resel_pack_rows(const float* src, int64_t ld_src, const int64_t* idx, const 
                     int T, int C, resel_stream_t stream);
 int resel_unpack_rows(const float* packed, int64_t ld, const int64_t* idx, const int32_t* n_dev, float* dst, int64_t ld_dst,
                       int M, int T, int C, resel_stream_t stream);
+
+/* Head-width padding around the attention entries.  The kernels above and resel_attn_decode exist for hd in {32, 64, 128}; every other
+ * multiple of 8 up to 120 runs on the next of these widths hdp (8..24 -> 32, 40..56 -> 64, 72..120 -> 128): zero columns of q and k add
+ * nothing to a score and zero columns of v give zero output columns, so the result is exact as long as `scale` is that of the TRUE
+ * width.  bf16 rows of hd resp. hdp elements, both multiples of 8, hdp >= hd, 16-byte aligned bases, dense tensors.
+ *   pad:   src [T, n, H, hd] -> dst [T, n, H, hdp], columns [hd, hdp) written as zero   (qkv: n = 3; dout: n = 1)
+ *   unpad: src [T, n, H, hdp] -> dst [T, n, H, hd], the first hd columns of every row   (out: n = 1; dqkv: n = 3)
+ * Every element of dst is written exactly once.  No host read, no allocation: capturable.  hdp == hd is a plain copy. */
+int resel_head_pad(const uint16_t* src, uint16_t* dst, int T, int n, int H, int hd, int hdp, resel_stream_t stream);
+int resel_head_unpad(const uint16_t* src, uint16_t* dst, int T, int n, int H, int hd, int hdp, resel_stream_t stream);
 
 /* Element-wise dropout y = keep(i) ? x / (1 - p) : 0 with the keep mask a counter function of (seed, offset, element index)
  * (16-bit threshold round((1 - p) * 65536); oracle/kernels.py `dropout_keep`).  Replaces the `nn.Dropout`s of the cgpt
@@ -614,7 +624,7 @@ int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const i
  *   x_db [B, R + 2N] = (dt low-rank | Bm | Cm) (row stride ld_xdb), w_dt [Di, R], state [B, Di, N], z [B, Di] (row stride ldz).
  * resel_attn_decode: appends this token's k, v to kv_cache [Bmax, max_seqlen, 2, H, hd] (bf16) at position `pos` and
  *   returns softmax_j<=pos(scale q.k_j - slope_h (pos - j)) v_j as out [B, H, hd] bf16.  qkv [B, 3, H, hd] bf16 (row stride
- *   ld_qkv).  pos = *pos_dev when pos_dev != NULL (device step counter: graph replay), else pos_host.  hd in {32, 64}.
+ *   ld_qkv).  pos = *pos_dev when pos_dev != NULL (device step counter: graph replay), else pos_host.  hd in {32, 64, 128} (other widths: resel_head_pad).
  *   pos >= max_seqlen: RESEL_EINVAL for a host position; with a device counter the output row is NaN (the reference's
  *   flash-attn asserts on a full cache).
  * resel_attn_decode_rows: resel_attn_decode with ONE POSITION PER ROW - pos_rows [B] int32 on the device replaces pos_dev / pos_host.

@@ -18,6 +18,7 @@
 // things that did not help (key-split wave pairs, a third LDS buffer, 5 waves per SIMD with spills, fp32-MFMA bias start).
 // Arithmetic intensity is low for hd = 32 (4 MFMAs per 32x32 tile against ~16 exp2 per lane), so these kernels are
 // VALU-issue-bound rather than MFMA-bound (PMC: VALU 58 % busy, MFMA 21 %); the whole attention share of a cgpt update is ~1 TFLOP.
+// Head widths 32, 64, 128 (others: zero-padded by resel_head_pad, true-width scale; profiles/r31_attention_head_dims.md).
 // Semantics restated from flash-attn's MHA(causal, alibi) - see oracle/kernels.py attention_alibi_varlen_ref: PARITY UNPINNED.
 //
 // Attention-probability dropout (MHA(dropout=p), reference TransformerFlashAttention.py:67-70): the keep mask is a pure
@@ -29,6 +30,7 @@
 //     is restated in oracle/kernels.py `attn_dropout_keep`).  Softmax statistics (running max, sum, lse, delta) are those
 //     of the un-dropped probabilities; only the P V, dV and dP products see the mask.
 #include "resel_common.h"
+#include "attn_image.h"
 
 namespace {
 using namespace resel;
@@ -241,7 +243,9 @@ __device__ __forceinline__ bool attn_block(const AttnParams& p, int& s, int& h, 
 //     - the A operand of O^T = V^T P^T and dQ^T = K^T dS^T in the accumulator's k-order 16 s + 8 (j >> 2) + 4 h + (j & 3).
 // chunk ch of row `row` lives at chunk position ch ^ swz(row); with swz below both read forms are bank-conflict free
 // (64-byte rows: 4 rows span the 64 banks, the 16-lane groups of ds_read_b128 hold 4 rows of each residue mod 4 whose
-// (row >> 2) & 3 differ; 128-byte rows: 2 rows span the banks and the row bits 1..3 separate the 8 rows of a group).
+// (row >> 2) & 3 differ; 128-byte rows: 2 rows span the banks and the row bits 1..3 separate the 8 rows of a group; 256-byte
+// rows (hd 128): all four row bits go into the chunk position, bits 0..1 on top so that the 4 rows of a transposed block part).
+// The arithmetic is in attn_image.h, where a host program can check it (tools/attn_image_check.cpp).
 #define LDS_AS __attribute__((address_space(3)))
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -249,18 +253,13 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 template <int HD>
 struct Img {
     static constexpr int ROWB = HD * 2;
-    static __device__ __forceinline__ int swz(int row) {
-        return HD == 32 ? ((row >> 2) & 3) : ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-    }
-    static __device__ __forceinline__ int off(int row, int ch) { return row * ROWB + ((ch ^ swz(row)) << 4); }
+    static_assert(HD == 32 || HD == 64 || HD == 128, "swizzles exist for 64-, 128- and 256-byte rows");
+    static __device__ __forceinline__ int swz(int row) { return resel_attn_image::swz(HD, row); }
+    static __device__ __forceinline__ int off(int row, int ch) { return resel_attn_image::off(HD, row, ch); }
     // lane-constant part of the row-read address of k-step ks (tile rows start at a multiple of 32: swz does not see them)
     static __device__ __forceinline__ int row_off(int r, int hh, int ks) { return off(r, 2 * ks + hh); }
     // lane-constant part of the transposed-read address: k-step s2, first / second block of the step (sec), column tile t
-    static __device__ __forceinline__ int tr_off(int lane, int s2, int sec, int t) {
-        const int li = lane & 15, dh = (lane >> 4) & 1, hh = lane >> 5;
-        const int row = 16 * s2 + 8 * sec + 4 * hh + (li >> 2);
-        return off(row, 4 * t + 2 * dh + ((li & 3) >> 1)) + 8 * (li & 1);
-    }
+    static __device__ __forceinline__ int tr_off(int lane, int s2, int sec, int t) { return resel_attn_image::tr_off(HD, lane, s2, sec, t); }
 };
 __device__ __forceinline__ bf16x8 lds_row(LDS_AS const char* a) { return *reinterpret_cast<LDS_AS const bf16x8*>(a); }
 __device__ __forceinline__ bf16x8 lds_tr(LDS_AS const char* lo, LDS_AS const char* hi) {      // EXEC must be all ones
@@ -337,6 +336,7 @@ __global__ __launch_bounds__(256 * KSPL, KSPL == 2 && HD == 32 ? 4 : 1) void att
 #else
     constexpr int NBUF = 2;
 #endif
+    static_assert(NBUF * 2 * IMG <= 160 * 1024, "LDS");              // hd 128: 2 buffers x (K | V) x 32 KB = 128 KB, one workgroup per CU
     __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * IMG];   // [buffer][K image | V image]
     LDS_AS char* const lds = (LDS_AS char*)smem;
 
@@ -694,8 +694,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(AttnParams p) {
     constexpr int KS = HD / 16, ND = HD / 32, NTHR = 256;
     constexpr int ROWB = HD * 2, IMG = KTB * ROWB;
     constexpr int NI = KTB * HD / 8 / NTHR;                      // 16-byte pieces of Q (and of dO) per thread and query block
-    constexpr int BUF = 2 * IMG + 2 * KTB * 4;                   // Q image | dO image | comb[128] | -delta[128]
-    __shared__ __attribute__((aligned(16))) char smem[3 * BUF];  // three buffers: one barrier per query block
+    constexpr int BUF = 2 * IMG + 2 * KTB * 4, NBUF = HD == 128 ? 2 : 3;     // Q image | dO image | comb[128] | -delta[128]; hd 128: 65 KB each
+    __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF];   // three buffers: one barrier per query block; hd 128: two, and a second barrier
     LDS_AS char* const lds = (LDS_AS char*)smem;
 
     int s, h, level;
@@ -785,8 +785,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(AttnParams p) {
         // every wave is done with block ib - 1, whose buffer the copies of block ib + 2 now overwrite
         if (ib + 1 < nblk) vm_wait<NVM>(); else vm_wait<0>();
         __syncthreads();
-        if (ib + 2 < nblk) issue_q(qb + 2 * KTB, (ib + 2) % 3);
-        LDS_AS const char* const qimg = lds + (ib % 3) * BUF;
+        if (NBUF == 3 && ib + 2 < nblk) issue_q(qb + 2 * KTB, (ib + 2) % 3);
+        LDS_AS const char* const qimg = lds + (ib % NBUF) * BUF;
         LDS_AS const char* const oimg = qimg + IMG;
         LDS_AS const float* const comb = reinterpret_cast<LDS_AS const float*>(qimg + 2 * IMG);
         LDS_AS const float* const sdl = comb + KTB;
@@ -865,6 +865,7 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(AttnParams p) {
                 }
             }
         }
+        if (NBUF == 2) { __syncthreads(); if (ib + 2 < nblk) issue_q(qb + 2 * KTB, ib & 1); }      // every wave is done with this block's buffer
     }
     // epilogue: dkt / dvt [t][reg] = X^T[d = 32 t + row(reg)][key]
     if (k_ok) {
@@ -882,10 +883,11 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(AttnParams p) {
                 }
         }
     }
+    static_assert(NI >= 1 && NBUF * BUF <= 160 * 1024, "staging split / LDS (hd 128: 2 x 66560 B; three buffers would be 199680 B)");
 }
 
 inline bool attn_ok(int T, int S, int H, int hd, int max_seqlen, float p_drop) {
-    return T > 0 && S > 0 && H > 0 && (hd == 32 || hd == 64) && max_seqlen > 0 && p_drop >= 0.f && p_drop < 1.f;
+    return T > 0 && S > 0 && H > 0 && (hd == 32 || hd == 64 || hd == 128) && max_seqlen > 0 && p_drop >= 0.f && p_drop < 1.f;
 }
 inline void set_dropout(AttnParams& p, float p_drop, uint64_t seed, uint64_t offset) {
     p.thr = (uint32_t)floorf((1.f - p_drop) * 255.f) + 1u;       // flash-attn's 8-bit keep threshold
@@ -949,8 +951,9 @@ extern "C" int resel_attn_varlen_fwd(const uint16_t* qkv, const int32_t* cu_seql
         p.wl = (const uint32_t*)workspace;
     }
     const bool drop = p_drop > 0.f;
-    if (hd == 32) { if (drop) launch_fwd<32, true>(p, grid, s); else launch_fwd<32, false>(p, grid, s); }
-    else          { if (drop) launch_fwd<64, true>(p, grid, s); else launch_fwd<64, false>(p, grid, s); }
+    if (hd == 32)      { if (drop) launch_fwd<32, true>(p, grid, s); else launch_fwd<32, false>(p, grid, s); }
+    else if (hd == 64) { if (drop) launch_fwd<64, true>(p, grid, s); else launch_fwd<64, false>(p, grid, s); }
+    else               { if (drop) launch_fwd<128, true>(p, grid, s); else launch_fwd<128, false>(p, grid, s); }
     return launch_status();
 }
 
@@ -980,8 +983,9 @@ extern "C" int resel_attn_varlen_bwd(const uint16_t* qkv, const int32_t* cu_seql
         p.wl = wl;
     }
     const bool drop = p_drop > 0.f;
-    if (hd == 32) { if (drop) launch_bwd<32, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<32, false>(p, (const bf16_t*)out, gq, gk, s); }
-    else          { if (drop) launch_bwd<64, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<64, false>(p, (const bf16_t*)out, gq, gk, s); }
+    if (hd == 32)      { if (drop) launch_bwd<32, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<32, false>(p, (const bf16_t*)out, gq, gk, s); }
+    else if (hd == 64) { if (drop) launch_bwd<64, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<64, false>(p, (const bf16_t*)out, gq, gk, s); }
+    else               { if (drop) launch_bwd<128, true>(p, (const bf16_t*)out, gq, gk, s); else launch_bwd<128, false>(p, (const bf16_t*)out, gq, gk, s); }
     return launch_status();
 }
 

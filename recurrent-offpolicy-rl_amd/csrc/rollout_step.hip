@@ -243,6 +243,7 @@ static int attn_decode_launch(const uint16_t* qkv, int64_t ld_qkv, uint16_t* kv_
     switch (head_dim) {
         case 32: if (rows) RESEL_DECODE(32, true); else RESEL_DECODE(32, false); break;
         case 64: if (rows) RESEL_DECODE(64, true); else RESEL_DECODE(64, false); break;
+        case 128: if (rows) RESEL_DECODE(128, true); else RESEL_DECODE(128, false); break;
         default: return RESEL_EINVAL;
     }
 #undef RESEL_DECODE

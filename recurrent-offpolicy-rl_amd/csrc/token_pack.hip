@@ -54,7 +54,29 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const float* __restric
     }
 }
 
-inline int group_shift(int C4) {                                 // smallest 2^k >= C4, at most a wave
+// Head-width padding of the cgpt attention operands: [rows][hd] bf16 <-> [rows][hdp] bf16 with a zero tail, rows = T * n * H, hd and
+// hdp multiples of 8 (a row is a whole number of 16-byte pieces on both sides).  One thread per 16-byte piece of the DESTINATION,
+// which is written exactly once; at most 2048 workgroups striding over the pieces.  No device-side count: the token tail of a
+// padded problem is zero on the way in (pack_rows) and is written as zero by the attention entries on the way out.
+__global__ __launch_bounds__(256) void head_pad_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t rows, int c_src, int c_dst) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = rows * c_dst;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t row = i / c_dst;
+        const int c = (int)(i - row * c_dst);
+        dst[i] = c < c_src ? src[row * c_src + c] : make_uint4(0u, 0u, 0u, 0u);       // unpad: c_dst < c_src, every piece is a copy
+    }
+}
+inline int head_pad_launch(const void* src, void* dst, int64_t rows, int c_src, int c_dst, resel_stream_t stream) {
+    const int64_t blocks = (rows * c_dst + 255) / 256;
+    hipLaunchKernelGGL(head_pad_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4*)src, (uint4*)dst, rows, c_src, c_dst);
+    return launch_status();
+}
+inline bool head_pad_ok(const void* a, const void* b, int T, int n, int H, int hd, int hdp) {
+    return a && b && aligned16(a) && aligned16(b) && T >= 0 && n > 0 && H > 0 && hd > 0 && (hd & 7) == 0 && hdp >= hd && (hdp & 7) == 0;
+}
+
+inline int group_shift(int C4) {                                // smallest 2^k >= C4, at most a wave
     int k = 0;
     while ((1 << k) < C4 && k < 6) ++k;
     return k;
@@ -83,4 +105,16 @@ extern "C" int resel_unpack_rows(const float* packed, int64_t ld, const int64_t*
     const int gs = group_shift(C / 4);
     hipLaunchKernelGGL(unpack_rows_kernel, dim3(grid_for(M, gs)), dim3(256), 0, (hipStream_t)stream, packed, ld, idx, n_dev, dst, ld_dst, M, T, C / 4, gs);
     return launch_status();
+}
+
+extern "C" int resel_head_pad(const uint16_t* src, uint16_t* dst, int T, int n, int H, int hd, int hdp, resel_stream_t stream) {
+    if (!head_pad_ok(src, dst, T, n, H, hd, hdp)) return RESEL_EINVAL;
+    if (T == 0) return RESEL_OK;
+    return head_pad_launch(src, dst, (int64_t)T * n * H, hd / 8, hdp / 8, stream);
+}
+
+extern "C" int resel_head_unpad(const uint16_t* src, uint16_t* dst, int T, int n, int H, int hd, int hdp, resel_stream_t stream) {
+    if (!head_pad_ok(src, dst, T, n, H, hd, hdp)) return RESEL_EINVAL;
+    if (T == 0) return RESEL_OK;
+    return head_pad_launch(src, dst, (int64_t)T * n * H, hdp / 8, hd / 8, stream);
 }

@@ -106,6 +106,8 @@ SIGNATURES = {
     'resel_attn_varlen_bwd_padded': (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, U, U, S]),
     'resel_pack_rows': (c_int, [P, L, P, P, P, L, I, I, S]),
     'resel_unpack_rows': (c_int, [P, L, P, P, P, L, I, I, I, S]),
+    'resel_head_pad': (c_int, [P, P, I, I, I, I, I, S]),
+    'resel_head_unpad': (c_int, [P, P, I, I, I, I, I, S]),
     'resel_dropout': (c_int, [P, P, L, F, U, U, S]),
     'resel_dropout_offset_base': (c_int, [P]),
     'resel_gelu_dropout_fwd': (c_int, [P, P, L, F, U, U, P, E, S]),

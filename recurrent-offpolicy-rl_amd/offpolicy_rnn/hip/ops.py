@@ -872,12 +872,48 @@ def gru_seq_multi(jobs):
 
 
 # ---------------------------------------------------------------------------------------------- attention (cgpt)
+ATTN_KERNEL_WIDTHS = (32, 64, 128)           # head widths the attention and decode kernels are built for (csrc/attention.hip, rollout_step.hip)
+
+
+def attn_head_pad(hd: int) -> int:
+    """The kernel width a head width runs on: 32, 64 and 128 themselves, every other multiple of 8 up to 120 the next of them (zero
+    columns: exact).  Anything else raises - flash-attn's 136..256 included, which this build does not cover."""
+    hd = int(hd)
+    if hd <= 0 or hd % 8 != 0 or hd > ATTN_KERNEL_WIDTHS[-1]:
+        raise ValueError(f'cgpt attention: head width {hd} (embedding width / heads) is not supported: accepted are the multiples of 8 from 8 '
+                         f'to 128 (32, 64 and 128 native, the others zero-padded to the next of these); flash-attn\'s 136 to 256 are out of scope')
+    return next(w for w in ATTN_KERNEL_WIDTHS if w >= hd)
+
+
+def _head_pad(x, hdp):
+    """[T, n, H, hd] bf16 -> [T, n, H, hdp] with a zero tail (`resel_head_pad`)."""
+    T, n, H, hd = x.shape
+    out = torch.empty(T, n, H, hdp, dtype=torch.bfloat16, device=x.device)
+    check(lib().resel_head_pad(_p(x), _p(out), T, n, H, hd, hdp, _stream()), 'head_pad')
+    return out
+
+
+def _head_unpad(x, hd):
+    """[T, n, H, hdp] bf16 -> the first hd columns of every row, [T, n, H, hd] (`resel_head_unpad`)."""
+    T, n, H, hdp = x.shape
+    out = torch.empty(T, n, H, hd, dtype=torch.bfloat16, device=x.device)
+    check(lib().resel_head_unpad(_p(x), _p(out), T, n, H, hd, hdp, _stream()), 'head_unpad')
+    return out
+
+
 class AttnVarlenFn(torch.autograd.Function):
+    """A head width that is no kernel width runs zero-padded to the next one (`attn_head_pad`): qkv is padded once, the padded qkv / out
+    are what the backward keeps, dout is padded and dqkv unpadded there.  `scale` is the caller's - that of the TRUE width."""
+
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset, padded=False):
         _need_cuda('attn_varlen', qkv, cu_seqlens)
         assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.shape[1] == 3
+        hd_true = qkv.shape[-1]
+        hdp = attn_head_pad(hd_true)
         qkv = qkv.contiguous()
+        if hdp != hd_true:
+            qkv = _head_pad(qkv, hdp)
         T, _, H, hd = qkv.shape
         cu = cu_seqlens.to(torch.int32).contiguous()
         S = cu.numel() - 1
@@ -890,19 +926,23 @@ class AttnVarlenFn(torch.autograd.Function):
                   float(p_drop), int(seed), int(offset), _stream()), 'attn_varlen_fwd')
         ctx.save_for_backward(qkv, cu, slopes, out, lse)
         ctx.max_seqlen, ctx.scale, ctx.drop = int(max_seqlen), float(scale), (float(p_drop), int(seed), int(offset))
-        ctx.padded = bool(padded)
-        return out
+        ctx.padded, ctx.hd_true = bool(padded), hd_true
+        return out if hd == hd_true else _head_unpad(out.view(T, 1, H, hd), hd_true).view(T, H, hd_true)
 
     @staticmethod
     def backward(ctx, dout):
         qkv, cu, slopes, out, lse = ctx.saved_tensors
         T, _, H, hd = qkv.shape
         dout = dout.to(torch.bfloat16).contiguous()
+        if hd != ctx.hd_true:
+            dout = _head_pad(dout.view(T, 1, H, ctx.hd_true), hd).view(T, H, hd)
         dqkv = torch.empty_like(qkv)
         ws = _ws(lib().resel_attn_varlen_bwd_workspace_bytes(T, cu.numel() - 1, H, hd, ctx.max_seqlen), qkv.device)
         bwd = lib().resel_attn_varlen_bwd_padded if ctx.padded else lib().resel_attn_varlen_bwd
         check(bwd(_p(qkv), _p(cu), _p(slopes), _p(out), _p(lse), _p(dout), _p(dqkv), _p(ws), T, cu.numel() - 1, H, hd,
                   ctx.max_seqlen, ctx.scale, *ctx.drop, _stream()), 'attn_varlen_bwd')
+        if hd != ctx.hd_true:
+            dqkv = _head_unpad(dqkv, ctx.hd_true)
         return dqkv, None, None, None, None, None, None, None, None
 
 
@@ -944,7 +984,8 @@ def attn_varlen(qkv, cu_seqlens, max_seqlen, slopes=None, scale=None, p_drop=0.0
     """qkv [T, 3, H, hd] bf16 packed tokens -> out [T, H, hd] bf16: causal softmax(q k^T * scale - slope_h (i - j)) v per sequence.
     p_drop > 0: dropout on the attention probabilities with the keep mask keyed on (seed, offset) (see resel_hip.h).
     `padded`: the tables of a shape bucket - T may exceed cu_seqlens[-1] and sequences may be empty; the same kernels, then a pass
-    that writes the token tail of out / lse (backward: dqkv) as zero (`resel_attn_varlen_fwd_padded`)."""
+    that writes the token tail of out / lse (backward: dqkv) as zero (`resel_attn_varlen_fwd_padded`).
+    hd: a multiple of 8 up to 128 (`attn_head_pad`; ValueError otherwise); the default scale is hd ** -0.5 of the width given here."""
     scale = qkv.shape[-1] ** -0.5 if scale is None else scale
     return AttnVarlenFn.apply(qkv, cu_seqlens, max_seqlen, slopes, scale, p_drop, seed, offset, padded)
 
@@ -2318,11 +2359,22 @@ def mamba_step(hidden, xz, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, d_conv
 def attn_decode(qkv, kv_cache, pos, slopes, scale):
     """Append this token's k, v to kv_cache [Bmax, S, 2, H, hd] (bf16, in place) and attend over positions 0..pos.
     qkv [B, 3, H, hd] bf16; pos: host int, or an int32 device tensor (graph replay) - of one element: the position of all rows; of
-    B > 1 elements: one position per row (rows at different points of their episodes, `resel_attn_decode_rows`).  -> [B, H, hd] bf16."""
+    B > 1 elements: one position per row (rows at different points of their episodes, `resel_attn_decode_rows`).  -> [B, H, hd] bf16.
+    The cache is held at the kernel width hdp = attn_head_pad(hd): [Bmax, S, 2, H, hdp], its columns [hd, hdp) zero; qkv is padded to it
+    and the result unpadded.  `scale` is that of the true width hd."""
     _need_cuda('attn_decode', qkv, kv_cache)
-    B, _, H, hd = qkv.shape
+    B, _, H, hd_true = qkv.shape
+    hd = attn_head_pad(hd_true)
     assert qkv.dtype == torch.bfloat16 and kv_cache.dtype == torch.bfloat16 and qkv.is_contiguous() and kv_cache.is_contiguous()
-    assert kv_cache.shape[0] >= B and kv_cache.shape[2:] == (2, H, hd)
+    assert kv_cache.shape[0] >= B and kv_cache.shape[2:] == (2, H, hd), 'the KV cache is [Bmax, S, 2, H, attn_head_pad(hd)]'
+    if hd != hd_true:
+        out = _attn_decode_run(_head_pad(qkv, hd), kv_cache, pos, slopes, scale)
+        return _head_unpad(out.view(B, 1, H, hd), hd_true).view(B, H, hd_true)
+    return _attn_decode_run(qkv, kv_cache, pos, slopes, scale)
+
+
+def _attn_decode_run(qkv, kv_cache, pos, slopes, scale):
+    B, _, H, hd = qkv.shape
     out = torch.empty((B, H, hd), dtype=torch.bfloat16, device=qkv.device)
     dev = pos if torch.is_tensor(pos) else None
     if dev is not None and dev.numel() > 1:
