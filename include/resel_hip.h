@@ -366,6 +366,13 @@ int resel_sac_target_local(const float* q, const int32_t* subset, int m, const f
                            float* target, float* stats, float* extrema, void* workspace, int E, int M, resel_stream_t stream);
 int resel_guard_apply_slots(const float* slots, int world, float* guard, resel_stream_t stream);
 size_t resel_sac_target_workspace_bytes(int M);
+/* The target of the memoryless REDQ trainer (reference algorithm/sac_mlp_redq_ensemble_q.py:29-39): no Q-guard and no mask.
+ *   target[i] = reward[i] + (1 - done[i]) gamma (min_{e in subset} q[e][i] - exp(log_alpha) next_logp[i]),  stats[0] = max_i |target[i]|
+ * q [E][M]; subset [m] int32 on the device, entries clamped into [0, E); next_logp NULL drops the entropy term; stats NULL: the
+ * maximum is not formed.  A NaN member makes its minimum NaN.  workspace: resel_sac_target_workspace_bytes(M) bytes. */
+int resel_redq_target(const float* q, const int32_t* subset, int m, const float* next_logp, const float* log_alpha,
+                      const float* reward, const float* done, float gamma, float* target, float* stats, void* workspace,
+                      int E, int M, resel_stream_t stream);
 
 /* Masked losses of the update, one forward and one backward pass each (reference sac_full_length_rnn_ensembleQ.py:80-81 `_mask_mean`,
  * :105-114 `_Q_loss`, sac_full_length_rnn_redq.py:37-49 / td3_full_length_rnn_redq.py:39-51 `_policy_loss`, :130-132 `_alpha_loss`);
@@ -605,6 +612,14 @@ int resel_gather_trajs(const float* buffer, int W, int64_t capacity, const int* 
 int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows, int Tp,
                            int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,
                            const int* sel, int sel_words, float* out, resel_stream_t stream);
+/* Transition batches from the same ring (the memoryless trainers; reference replay_memory.py `sample_transitions`):
+ *   out[n][:] = buffer[rows[p][n]][:]  for n < batch, all W columns;  out [batch][W], rows [passes][batch] int32.
+ * p is the argument, or pass_word[0] when pass_word is not NULL (a device word: one captured launch then serves every pass of an update).
+ * c_timeout >= 0: the done column of a row whose timeout column is > 0 is written as 0 (time-limit terminations bootstrap); -1 leaves
+ * done as stored.  A row index outside [0, capacity), or a pass word outside [0, passes), yields a zero row and reads nothing of the
+ * ring.  No alignment beyond 4 bytes and no multiple is asked of W or batch.  p outside [0, passes) without a pass word is RESEL_EINVAL. */
+int resel_gather_transitions(const float* buffer, int W, int64_t capacity, const int* rows, int passes, int batch, int p,
+                             const int* pass_word, int c_done, int c_timeout, float* out, resel_stream_t stream);
 
 /* ---- one-token rollout step (T = 1): the policy forward between updates -------------------------------------------
  * Reference: the outer loop calls policy.forward once per environment step (algorithm/sac.py:319-326), which reaches

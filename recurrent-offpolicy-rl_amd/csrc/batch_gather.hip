@@ -79,7 +79,40 @@ __global__ void gather_flags_kernel(float* __restrict__ out, int rows, int Tp, i
     if (c_timeout >= 0 && p[c_timeout] > 0.f) p[c_done] = 0.f;
 }
 
+// Transition batches (the memoryless trainers): out[n, :] = buffer[rows[p, n], :].  One wave per batch row, its lanes across the W columns
+// (plain 4-byte loads and stores: W is whatever the environment makes it and rows are 4-byte aligned only); a block is four rows.  The
+// pass p comes from the device word when there is one, so that one captured launch serves every pass of an update.  A pass outside
+// [0, passes) or a row index outside [0, capacity) gives a zero row and reads nothing behind the table.
+__global__ __launch_bounds__(256) void gather_transitions_kernel(const float* __restrict__ buffer, int W, int64_t capacity,
+                                                                 const int* __restrict__ rows, int passes, int batch, int p_arg,
+                                                                 const int* __restrict__ pass_word, int c_done, int c_timeout,
+                                                                 float* __restrict__ out) {
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= batch) return;
+    const int p = pass_word ? pass_word[0] : p_arg;
+    int64_t r = -1;
+    if (p >= 0 && p < passes) r = rows[(int64_t)p * batch + n];
+    const bool ok = r >= 0 && r < capacity;
+    const float* src = buffer + (ok ? r : 0) * W;
+    float* dst = out + (int64_t)n * W;
+    const bool timed_out = ok && c_timeout >= 0 && src[c_timeout] > 0.f;      // time-limit terminations bootstrap
+    for (int col = lane; col < W; col += 64) {
+        float v = ok ? src[col] : 0.f;
+        if (col == c_done && timed_out) v = 0.f;
+        dst[col] = v;
+    }
+}
+
 }  // namespace
+
+extern "C" int resel_gather_transitions(const float* buffer, int W, int64_t capacity, const int* rows, int passes, int batch, int p,
+                                        const int* pass_word, int c_done, int c_timeout, float* out, resel_stream_t stream) {
+    if (!buffer || !rows || !out || W <= 0 || capacity <= 0 || passes <= 0 || batch <= 0) return RESEL_EINVAL;
+    if (c_done < 0 || c_done >= W || c_timeout >= W || (!pass_word && (p < 0 || p >= passes))) return RESEL_EINVAL;
+    hipLaunchKernelGGL(gather_transitions_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)stream, buffer, W, capacity,
+                       rows, passes, batch, p, pass_word, c_done, c_timeout, out);
+    return launch_status();
+}
 
 extern "C" int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const int* segments, int nseg, int max_len, int skip, int rows,
                                       int Tp, int c_mask, int c_start, int c_done, int c_timeout, const int* pre_pairs, int npairs,

@@ -233,6 +233,41 @@ __global__ __launch_bounds__(256) void guard_update_kernel(const float* __restri
     }
 }
 
+// The memoryless REDQ target (reference sac_mlp_redq_ensemble_q.py:29-39): no guard, no mask.  y = r + (1 - done) gamma (min_{e in S} q[e]
+// - alpha logp); part[4 b + 2] = the block's max |y|.  A NaN member makes the minimum NaN, as q.min(dim=0) does; subset entries are
+// clamped into [0, E).
+__global__ __launch_bounds__(256) void redq_target_kernel(const float* __restrict__ q, const int32_t* __restrict__ subset, int m,
+                                                          const float* __restrict__ next_logp, const float* __restrict__ log_alpha,
+                                                          const float* __restrict__ reward, const float* __restrict__ done, float gamma,
+                                                          float* __restrict__ target, float* __restrict__ part, int E, int M) {
+    const float alpha = next_logp ? expf(log_alpha[0]) : 0.f;
+    float ma = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
+        float val = INFINITY;
+        bool bad = false;
+        for (int k = 0; k < m; ++k) {
+            const int e = min(max(subset[k], 0), E - 1);
+            const float x = q[(int64_t)e * M + i];
+            bad |= x != x;
+            val = fminf(val, x);
+        }
+        if (next_logp) val -= alpha * next_logp[i];
+        if (bad) val = NAN;
+        const float y = reward[i] + (1.f - done[i]) * gamma * val;
+        target[i] = y;
+        ma = fmaxf(ma, fabsf(y));
+    }
+    block_reduce4(0.f, 0.f, ma, 0.f, part + 4 * blockIdx.x);
+}
+__global__ __launch_bounds__(256) void redq_stats_kernel(const float* __restrict__ part, int nblk, float* __restrict__ stats) {
+    float ma = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) ma = fmaxf(ma, part[4 * i + 2]);
+    __shared__ float res[4];
+    block_reduce4(0.f, 0.f, ma, 0.f, res);
+    __syncthreads();
+    if (threadIdx.x == 0) stats[0] = res[2];
+}
+
 // ------------------------------------------------------------------------------------ flat optimizer tail
 __global__ void soft_update_kernel(float* __restrict__ tgt, const float* __restrict__ src, float tau, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -320,6 +355,20 @@ extern "C" int resel_sac_target(const float* q, const int32_t* subset, int m, co
     hipLaunchKernelGGL(guard_init_kernel, dim3(1), dim3(256), 0, s, part1, nblk, guard);
     hipLaunchKernelGGL(target_y_kernel, dim3(nblk), dim3(256), 0, s, v, reward, done, mask, gamma, guard, target, part2, M);
     hipLaunchKernelGGL(guard_update_kernel, dim3(1), dim3(256), 0, s, part2, nblk, guard, stats);
+    return launch_status();
+}
+
+extern "C" int resel_redq_target(const float* q, const int32_t* subset, int m, const float* next_logp, const float* log_alpha,
+                                 const float* reward, const float* done, float gamma, float* target, float* stats, void* workspace,
+                                 int E, int M, resel_stream_t stream) {
+    if (!q || !subset || m <= 0 || !reward || !done || !target || !workspace || E <= 0 || M <= 0) return RESEL_EINVAL;
+    if (next_logp && !log_alpha) return RESEL_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)workspace + M;             // the layout of resel_sac_target: [M] scratch (unused here), then the block partials
+    const int nblk = (M + 255) / 256 < RED_BLOCKS ? (M + 255) / 256 : RED_BLOCKS;
+    hipLaunchKernelGGL(redq_target_kernel, dim3(nblk), dim3(256), 0, s, q, subset, m, next_logp, log_alpha, reward, done, gamma, target,
+                       part, E, M);
+    if (stats) hipLaunchKernelGGL(redq_stats_kernel, dim3(1), dim3(256), 0, s, part, nblk, stats);
     return launch_status();
 }
 

@@ -83,7 +83,8 @@ class UpdateLog:
     of its own turned once per step: with utd > RING a staging slot comes round again inside one step, and the log handed out by the
     step before is still unread then."""
 
-    def __init__(self, capacity, device):
+    def __init__(self, capacity, device, log_cls=DeferredLog):
+        self.log_cls = log_cls                        # the dict class `read_back` hands out
         self.dev = torch.zeros(capacity, dtype=torch.float32, device=device)
         self.slots = {}                               # key -> its slot in `dev`
         self._ring = [dict(log=torch.empty(capacity, dtype=torch.float32, pin_memory=True), evt=torch.cuda.Event(), handed=None)
@@ -107,5 +108,5 @@ class UpdateLog:
         n = len(self.slots)
         ring['log'][:n].copy_(self.dev[:n], non_blocking=True)
         ring['evt'].record()
-        ring['handed'] = DeferredLog(keys, ring['log'][:n], ring['evt'], items, index=[self.slots[k] for k in keys])
+        ring['handed'] = self.log_cls(keys, ring['log'][:n], ring['evt'], items, index=[self.slots[k] for k in keys])
         return ring['handed']

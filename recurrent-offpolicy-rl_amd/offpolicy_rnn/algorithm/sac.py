@@ -235,6 +235,12 @@ class SAC:
     def train_one_batch(self) -> Dict:
         return {}
 
+    def update_driver(self):
+        """A driver class of the trainer's own that replays its updates as hipGraphs for `train()` - `refusal(alg)` (None: it takes the
+        trainer), `driver(alg)` -> an object with `step()` (one `train_one_batch()`) and `close()` -, or None: `GraphedUpdate`, one graph
+        per recurring batch shape of a full-trajectory trainer (graphed_update.py)."""
+        return None
+
     def train(self):
         # RESEL_CHECKPOINT_DIR (read here; unset: nothing of this happens): the run state goes there every RESEL_CHECKPOINT_EVERY
         # iterations, and a run that finds a complete state there continues it instead of starting (algorithm/run_state.py)
@@ -257,15 +263,19 @@ class SAC:
             self.iteration, self.ep_ret, self.ep_len = 0, 0.0, 0
         update = self.train_one_batch
         graphed = None
-        if os.environ.get('RESEL_GRAPH_UPDATE', '1') != '0':  # default: the whole update as one hipGraph replay per recurring batch shape (graphed_update.py)
+        if os.environ.get('RESEL_GRAPH_UPDATE', '1') != '0':  # the update as hipGraph replays (`update_driver`)
             from .graphed_update import GraphedUpdate
-            why = GraphedUpdate.refusal(self)
+            driver = self.update_driver() or GraphedUpdate
+            why = driver.refusal(self)
             if why:
                 self.logger(f'updates are launched eagerly ({why})')
-            else:
+            elif driver is GraphedUpdate:
                 # RESEL_GRAPH_BUCKETS (variable-length episodes): 1 = batch shapes bucketed from the first update, auto = once the workload
                 # turns out ragged (fixed-length ones never switch), 0 / unset = exact shapes only
                 graphed = GraphedUpdate(self, buckets=GraphedUpdate.buckets_from_env())
+                update = graphed.step
+            else:
+                graphed = driver(self)
                 update = graphed.step
         # an environment that exists as a kernel (a discrete T-Maze, Wind-v0, Catch: env_utils/device_env.py) is collected on the device
         # (utility/device_collect.py): environment step, transition row and next inputs are the last node of the policy step's graph;

@@ -145,23 +145,6 @@ class NestedMemoryArray(MemoryArray):
         mask itself) stays on the host path."""
         return not randomize_mask or bool(equalize_data_of_each_traj)
 
-    def _mirror(self, device):
-        """Device copy of the ring, refreshed for the rows written since the last call (a rollout adds one trajectory
-        between updates; the synthetic benchmark fills the ring once)."""
-        import torch
-        st = self.__dict__.setdefault('_dev_state', {'buf': None})
-        dirty = getattr(self, '_dirty', None)
-        if st['buf'] is None or st['buf'].device != device or st['buf'].shape != self.memory_buffer.shape:
-            st['buf'] = torch.from_numpy(self.memory_buffer).to(device)
-        elif dirty is None or len(dirty) > 64:       # whole ring again, IN PLACE: captured updates hold the mirror's address
-            st['buf'].copy_(torch.from_numpy(self.memory_buffer))
-        else:
-            for s0, n in dirty:                      # through pinned memory: a pageable copy would stall the launch queue
-                rows = torch.from_numpy(self.memory_buffer[s0:s0 + n])
-                st['buf'][s0:s0 + n].copy_(rows.pin_memory() if device.type == 'cuda' else rows, non_blocking=True)
-        self._dirty = []
-        return st['buf']
-
     def plan_trajs_device(self, batch_size, max_sample_size=None, get_all=False, random_trunc_traj=False, nest_stack_trajs=True,
                           buckets=False, randomize_mask=False, valid_number_post_randomized=0):
         """Host half of `sample_trajs_device`: the same sampling decisions (and numpy RNG consumption) as `sample_trajs`.  Returns a dict

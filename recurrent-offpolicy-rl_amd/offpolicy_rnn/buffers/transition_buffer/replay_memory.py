@@ -225,6 +225,38 @@ class MemoryArray:
             rows = rows[np.random.randint(0, self.transition_count, (batch_size,))]
         return self.array_to_transition(self.memory_buffer[rows].copy())
 
+    def plan_transitions(self, batch_size: int, passes: int = 1) -> np.ndarray:
+        """Host half of a transition batch taken from the device mirror of the ring (`ops.gather_transitions`): per pass exactly the
+        draw of `sample_transitions(batch_size)` - one `randint(0, transition_count, (batch_size,))` from the global numpy stream - and
+        each drawn rank mapped to the ring row that call would copy.  -> int32 [passes, batch_size].  The rank -> row map is the
+        `np.repeat` table of `sample_transitions` read through the trajectories' cumulative lengths: no Python loop per transition."""
+        starts = np.asarray(self.trajectory_start, dtype=np.int64)
+        lens = np.asarray(self.trajectory_length, dtype=np.int64)
+        ends = np.cumsum(lens)
+        rows = np.empty((int(passes), int(batch_size)), dtype=np.int32)
+        for p in range(int(passes)):
+            rank = np.random.randint(0, self.transition_count, (batch_size,))
+            traj = np.searchsorted(ends, rank, side='right')
+            rows[p] = starts[traj] + (rank - (ends[traj] - lens[traj]))
+        return rows
+
+    def _mirror(self, device):
+        """Device copy of the ring, refreshed for the rows written since the last call (a rollout adds one trajectory
+        between updates; the synthetic benchmark fills the ring once)."""
+        import torch
+        st = self.__dict__.setdefault('_dev_state', {'buf': None})
+        dirty = getattr(self, '_dirty', None)
+        if st['buf'] is None or st['buf'].device != device or st['buf'].shape != self.memory_buffer.shape:
+            st['buf'] = torch.from_numpy(self.memory_buffer).to(device)
+        elif dirty is None or len(dirty) > 64:       # whole ring again, IN PLACE: captured updates hold the mirror's address
+            st['buf'].copy_(torch.from_numpy(self.memory_buffer))
+        else:
+            for s0, n in dirty:                      # through pinned memory: a pageable copy would stall the launch queue
+                rows = torch.from_numpy(self.memory_buffer[s0:s0 + n])
+                st['buf'][s0:s0 + n].copy_(rows.pin_memory() if device.type == 'cuda' else rows, non_blocking=True)
+        self._dirty = []
+        return st['buf']
+
     def save_to_disk(self, path):
         self._last_saving_time = time.time()
         self._last_saving_size = self.size

@@ -124,6 +124,7 @@ SIGNATURES = {
     'resel_sac_target_local': (c_int, [P, P, I, P, P, P, P, P, F, P, P, P, P, P, I, I, S]),
     'resel_guard_apply_slots': (c_int, [P, I, P, S]),
     'resel_sac_target_workspace_bytes': (c_size_t, [I]),
+    'resel_redq_target': (c_int, [P, P, I, P, P, P, P, F, P, P, P, I, I, S]),
     'resel_soft_update': (c_int, [P, P, F, L, S]),
     'resel_adamw_flat': (c_int, [P, P, P, P, L, P, P, P, I, F, F, F, I, P, S]),
     'resel_adamw_flat_bc': (c_int, [P, P, P, P, L, P, P, P, I, F, F, F, F, F, P, S]),
@@ -153,6 +154,7 @@ SIGNATURES = {
     'resel_colsum_bf16': (c_int, [P, L, I, I, P, P, S]),
     'resel_gather_trajs': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, S]),
     'resel_gather_trajs_sel': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, I, P, S]),
+    'resel_gather_transitions': (c_int, [P, I, L, P, I, I, I, P, I, I, P, S]),
     'resel_mamba_conv_step': (c_int, [P, L, P, L, P, L, L, L, I, P, P, P, I, I, I, I, S]),
     'resel_selective_state_update': (c_int, [P, L, P, L, P, P, L, P, P, P, P, P, L, P, I, I, I, I, S]),
     'resel_atb_workspace_bytes': (c_size_t, [L, I, I]),

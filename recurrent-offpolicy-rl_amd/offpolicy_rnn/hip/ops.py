@@ -1180,6 +1180,24 @@ def sac_target(q, subset, next_logp, log_alpha, reward, done, mask, gamma, guard
     return target.reshape(reward.shape)
 
 
+@torch.no_grad()
+def redq_target(q, subset, next_logp, log_alpha, reward, done, gamma, stats=None):
+    """The guard-less, mask-less target of the memoryless REDQ trainer (`resel_redq_target`): q [E, ...]; subset int32 [m] (device);
+    -> reward + (1 - done) gamma (min over the subset - exp(log_alpha) next_logp), shaped like reward; stats[0] = max |target|."""
+    _need_cuda('redq_target', q, subset, reward, done)
+    assert subset.dtype == torch.int32 and subset.is_contiguous()
+    E = q.shape[0]
+    M = reward.numel()
+    qf = q.float().reshape(E, M).contiguous()
+    target = torch.empty(M, dtype=torch.float32, device=q.device)
+    ws = _ws(lib().resel_sac_target_workspace_bytes(M), q.device)
+    f = lambda t: None if t is None else t.float().reshape(-1).contiguous()
+    nl, rw, dn = f(next_logp), f(reward), f(done)
+    check(lib().resel_redq_target(_p(qf), _p(subset), int(subset.numel()), _p(nl), _p(log_alpha), _p(rw), _p(dn), float(gamma), _p(target),
+                                  _p(stats), _p(ws), E, M, _stream()), 'redq_target')
+    return target.reshape(reward.shape)
+
+
 class MaskedQLossFn(torch.autograd.Function):
     """sum_m mask[m] sum_e (q[e, m] - y[m])^2 as ONE node (include/resel_hip.h `resel_q_loss_*`)."""
 
@@ -1739,6 +1757,23 @@ def gather_trajs(buffer, segments, max_len, skip, rows, row_len, c_mask, c_start
     check(lib().resel_gather_trajs_sel(_p(buffer), W, buffer.shape[0], _p(segments), segments.shape[0], int(max_len), int(skip), int(rows),
                                        int(row_len), int(c_mask), int(c_start), int(c_done), int(c_timeout), _p(pre_pairs), pre_pairs.shape[0],
                                        None if sel is None else _p(sel), 0 if sel is None else sel.numel(), _p(out), _stream()), 'gather_trajs')
+    return out
+
+
+@torch.no_grad()
+def gather_transitions(buffer, rows_dev, pass_word=None, p=0, c_done=0, c_timeout=-1):
+    """Transition batch [batch, W] from the device ring `buffer` [capacity, W]: row n is ring row `rows_dev[p, n]` (int32
+    [passes, batch]); the pass is `p`, or the int32 device word `pass_word` when given.  `c_timeout >= 0`: done is 0 where timeout > 0.
+    See include/resel_hip.h `resel_gather_transitions`."""
+    _need_cuda('gather_transitions', buffer, rows_dev, *(() if pass_word is None else (pass_word,)))
+    assert buffer.dtype == torch.float32 and buffer.dim() == 2 and buffer.is_contiguous()
+    assert rows_dev.dtype == torch.int32 and rows_dev.dim() == 2 and rows_dev.is_contiguous()
+    assert pass_word is None or (pass_word.dtype == torch.int32 and pass_word.numel() >= 1)
+    W = buffer.shape[1]
+    passes, batch = rows_dev.shape
+    out = torch.empty(batch, W, dtype=torch.float32, device=buffer.device)
+    check(lib().resel_gather_transitions(_p(buffer), W, buffer.shape[0], _p(rows_dev), int(passes), int(batch), int(p), _p(pass_word),
+                                         int(c_done), int(c_timeout), _p(out), _stream()), 'gather_transitions')
     return out
 
 

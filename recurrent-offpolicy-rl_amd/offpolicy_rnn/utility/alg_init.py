@@ -1,9 +1,10 @@
 """alg_name -> trainer class (reference offpolicy_rnn/utility/alg_init.py:16-47).
 
-Only the full-trajectory recurrent family is in scope of this build; the remaining reference
-names raise NotImplementedError with an explicit message instead of silently mapping to something else."""
+The full-trajectory recurrent family and the memoryless baseline it is compared against,
+`sac_mlp_redq_ensemble_q`, are in scope of this build; the remaining reference names raise NotImplementedError with an explicit
+message instead of silently mapping to something else."""
 
-_OUT_OF_SCOPE = ('sac_no_train', 'sac_mlp', 'sac_mlp_redq', 'sac_rnn_slice', 'sac_mlp_redq_ensemble_q')
+_OUT_OF_SCOPE = ('sac_no_train', 'sac_mlp', 'sac_mlp_redq', 'sac_rnn_slice')
 
 
 def alg_init(parameter):
@@ -14,7 +15,9 @@ def alg_init(parameter):
     from ..algorithm.td3_full_length_rnn_ensembleQ import TD3FullLengthRNNEnsembleQ
     from ..algorithm.td3_full_length_rnn_redq import TD3FullLengthRNNREDQ
     from ..algorithm.td3_full_length_rnn_redq_sep_optim import TD3FullLengthRNNREDQ_SEP_OPTIM
+    from ..algorithm.sac_mlp_redq_ensemble_q import SAC_MLP_REDQ_EnsembleQ
     table = {
+        'sac_mlp_redq_ensemble_q': (SAC_MLP_REDQ_EnsembleQ, 'sac'),
         'sac_rnn_full_horizon_ensembleQ': (SACFullLengthRNNEnsembleQ, 'sac'),
         'sac_rnn_full_horizon_redQ': (SACFullLengthRNNREDQ, 'sac'),
         'sac_rnn_full_horizon_redQ_sep_optim': (SACFullLengthRNNREDQ_SEP_OPTIM, 'sac'),
@@ -30,6 +33,6 @@ def alg_init(parameter):
             parameter.base_algorithm = 'td3'
         return cls(parameter)
     if name in _OUT_OF_SCOPE:
-        raise NotImplementedError(f'Algorithm {name} is a transition-level / slice trainer of the reference and is outside '
-                                  f'the MI355X full-trajectory hot path implemented here.')
+        raise NotImplementedError(f'Algorithm {name} is a transition-level / slice trainer of the reference that this build does not '
+                                  f'implement; its memoryless baseline is sac_mlp_redq_ensemble_q (one efc-<E> ensemble critic).')
     raise NotImplementedError(f'Algorithm {name} has not been implemented!')

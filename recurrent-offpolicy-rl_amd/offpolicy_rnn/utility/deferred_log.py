@@ -6,6 +6,8 @@ class DeferredLog(dict):
     pinned memory and become floats on first access (`resolve()`), so a caller that does not read them - a training loop
     logging every n-th update, bench.py - never stalls the launch queue on the update it has just enqueued."""
 
+    TUPLE_KEYS = ('actor_loss',)
+
     def __init__(self, keys, buf, event, host_items=(), index=None):
         """`buf`: host tensor the scalars named by `keys` arrive in, readable once `event` (None: at once) has passed; `index`: where in
         `buf` each key's scalar sits (None: in the order of `keys`) - a buffer with a fixed slot per key, of which this log names some."""
@@ -33,8 +35,9 @@ class DeferredLog(dict):
                 self._event.synchronize()
             got = self._buf.tolist()
             vals = dict(zip(self._keys, got if self._index is None else [got[i] for i in self._index]))
-            if 'actor_loss' in vals:
-                vals['actor_loss'] = (vals['actor_loss'],)      # a 1-tuple upstream (reference :430); kept
+            for k in self.TUPLE_KEYS:
+                if k in vals:
+                    vals[k] = (vals[k],)                        # a 1-tuple upstream (reference :430); kept
             self._keys = None
             pending = dict(self)                                # host entries override / follow, as in the reference order
             dict.clear(self)
@@ -72,3 +75,8 @@ class DeferredLog(dict):
 
     def __repr__(self):
         return dict.__repr__(self.resolve())
+
+
+class ScalarLog(DeferredLog):
+    """The log of the memoryless trainers: every entry a float, `actor_loss` included (reference sac_mlp_redq_ensemble_q.py:189-200)."""
+    TUPLE_KEYS = ()
