@@ -47,7 +47,8 @@ enum {
     RESEL_PROF_LINREC_REAL_FWD = 5, RESEL_PROF_LINREC_REAL_BWD = 6, RESEL_PROF_LINREC_COMPLEX_FWD = 7, RESEL_PROF_LINREC_COMPLEX_BWD = 8,
     RESEL_PROF_GRU_FWD = 9, RESEL_PROF_GRU_BWD = 10, RESEL_PROF_CONV_FWD = 11, RESEL_PROF_CONV_BWD = 12, RESEL_PROF_GEMM = 13,
     RESEL_PROF_SSCAN_FWD_LOCAL = 14, RESEL_PROF_SSCAN_BWD_LOCAL = 15,   /* time-parallel form: the local passes (+ carry) of a call */
-    RESEL_PROF_NSLOTS = 16
+    RESEL_PROF_SSCAN_GATE_FWD = 16, RESEL_PROF_SSCAN_GATE_BWD = 17, RESEL_PROF_SSCAN_GROUP_REDUCE = 18,   /* state groups (N > 64) */
+    RESEL_PROF_NSLOTS = 19
 };
 int resel_profile_enable(int on);
 int resel_profile_collect(int kernel_id, double* total_us, int* launches);
@@ -66,7 +67,10 @@ int resel_profile_collect(int kernel_id, double* total_us, int* launches);
  *   out_t  = (<Cm_t, h_t> + D * u_t) * silu(z_t)     (gate skipped when z == NULL, skip term when D == NULL)
  * u, delta, z, out: [B*L, Di] (ld_u, ld_delta, ld_z, ld_out; 16-byte aligned); A: [Di, N] dense;
  * Bm, Cm: [B*L, N] (ld_b, ld_c); D, delta_bias: [Di]; start: [B*L] or NULL.
- * Supported: Di % 4 == 0, N in {4, 8, 16, 32, 64}.
+ * Supported by these two entries: Di % 4 == 0, N in {4, 8, 16, 32, 64} (any other N: RESEL_EINVAL).  Every d_state from 1 to 256 runs on
+ *   them through the state plan of the Python layer (hip/ops.py `sscan_state_plan`): N <= 64 zero-padded to the next native size (zero
+ *   B / C columns: exact), 64 < N <= 256 as up to RESEL_SSCAN_MAX_GROUPS column groups, each one call here with z == NULL and D == NULL,
+ *   joined by the "state groups" entries below.
  * ckpt (optional, for the backward): state checkpoints every RESEL_SSCAN_CKPT steps,
  *   resel_selective_scan_ckpt_bytes(B, L, Di, N) bytes.  last_state (optional): [B, Di, N].
  * time_segments: 0 = the library decides (one workgroup scans a whole row when B * Di / 64 rows x tiles fill the chip; small
@@ -98,6 +102,35 @@ int resel_selective_scan_bwd(const float* u, int64_t ld_u, const float* delta, i
                              float* dA, float* dD, float* ddelta_bias, void* workspace,
                              int B, int L, int Di, int N, int delta_softplus, int time_segments,
                              void* amax_dz, void* amax_ddelta, unsigned amax_epoch, resel_stream_t stream);
+
+/* State groups (d_state > 64).  States are independent given (u, delta, B, C) and meet only in <C, h>: group g scans its own columns of
+ * (A, B, C) with z == NULL, D == NULL into parts[g], and these entries do what the groups share.  parts, du_parts, ddelta_parts: G dense
+ * [M, Di] slabs, stride_g floats apart (stride_g % 4 == 0, >= M * Di); M = B * L tokens; every other [M, Di] operand has its own token
+ * stride (% 4, >= Di) and a 16-byte aligned base; G in 1 .. RESEL_SSCAN_MAX_GROUPS.  Groups are summed in index order and dD is a
+ * two-stage column sum in a fixed order: bitwise reproducible, no atomics on floats.  One pass over HBM each.
+ *   gate_fwd:      out = (sum_g parts[g] + D u) * silu(z)      (z, D optional as in the scan; amax_out gets max |out|)
+ *   gate_bwd:      g = dout * silu(z) - the `dout` of every group's backward -, dz = dout * silu'(z) * (sum_g parts[g] + D u),
+ *                  dD = sum over tokens of g u.  z == NULL: g, dz, parts must be NULL and the groups take dout itself; D == NULL: dD
+ *                  must be NULL; both NULL is RESEL_EINVAL (nothing to form).  workspace: resel_sscan_gate_bwd_workspace_bytes(M, Di)
+ *                  bytes when D is given.  amax_dz gets max |dz|.
+ *   group_reduce:  du = sum_g du_parts[g] + D g (the skip term's share; g = the pre-gate gradient, needed with D only),
+ *                  ddelta = sum_g ddelta_parts[g], ddelta_bias = sum_g dbias_parts[g] ([G, Di] dense; both NULL or neither).
+ *                  amax_ddelta gets max |ddelta|.
+ * RESEL_EINVAL before the device is touched: a NULL / misaligned required operand, Di % 4 != 0, M < 1, G outside its range, a stride
+ * that is not a multiple of 4 or is shorter than its row, a magnitude handle that is not 8-byte aligned. */
+#define RESEL_SSCAN_MAX_GROUPS 4
+int resel_sscan_gate_fwd(const float* parts, int64_t stride_g, int G, const float* u, int64_t ld_u, const float* D,
+                         const float* z, int64_t ld_z, float* out, int64_t ld_out, int64_t M, int Di,
+                         void* amax_out, unsigned amax_epoch, resel_stream_t stream);
+size_t resel_sscan_gate_bwd_workspace_bytes(int64_t M, int Di);
+int resel_sscan_gate_bwd(const float* dout, int64_t ld_dout, const float* parts, int64_t stride_g, int G,
+                         const float* u, int64_t ld_u, const float* D, const float* z, int64_t ld_z,
+                         float* g, int64_t ld_g, float* dz, int64_t ld_dz, float* dD, void* workspace, int64_t M, int Di,
+                         void* amax_dz, unsigned amax_epoch, resel_stream_t stream);
+int resel_sscan_group_reduce(const float* du_parts, const float* ddelta_parts, int64_t stride_g, const float* dbias_parts, int G,
+                             const float* g, int64_t ld_g, const float* D, float* du, int64_t ld_du,
+                             float* ddelta, int64_t ld_ddelta, float* dbias, int64_t M, int Di,
+                             void* amax_ddelta, unsigned amax_epoch, resel_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * smamba depthwise causal conv1d + bias + SiLU on the masked input.  Replaces `causal_conv1d_cuda.causal_conv1d_fwd/bwd`

@@ -74,6 +74,10 @@ SIGNATURES = {
     'resel_selective_scan_bwd_workspace_bytes': (c_size_t, [I, I, I, I, I]),
     'resel_selective_scan_bwd': (c_int, [P, L, P, L, P, L, P, P, L, P, L, P, P, P, P, L, P,
                                          P, L, P, L, P, L, P, L, P, L, P, P, P, P, I, I, I, I, I, I, P, P, E, S]),
+    'resel_sscan_gate_fwd': (c_int, [P, L, I, P, L, P, P, L, P, L, L, I, P, E, S]),
+    'resel_sscan_gate_bwd_workspace_bytes': (c_size_t, [L, I]),
+    'resel_sscan_gate_bwd': (c_int, [P, L, P, L, I, P, L, P, P, L, P, L, P, L, P, P, L, I, P, E, S]),
+    'resel_sscan_group_reduce': (c_int, [P, P, L, P, I, P, L, P, P, L, P, L, P, L, I, P, E, S]),
     'resel_causal_conv1d_fwd': (c_int, [P, L, P, P, P, P, L, I, I, I, I, I, P, E, S]),
     'resel_causal_conv1d_bwd_workspace_bytes': (c_size_t, [I, I, I, I]),
     'resel_causal_conv1d_bwd': (c_int, [P, L, P, P, P, P, L, P, L, P, P, P, I, I, I, I, I, P, E, S]),

@@ -66,7 +66,8 @@ def _ws(nbytes: int, device) -> torch.Tensor:
 PROF_SLOTS = ('sscan_fwd_kernel', 'sscan_bwd_kernel', 'attn_fwd_kernel', 'attn_dq_kernel', 'attn_dkv_kernel', 'linrec_real_fwd_kernel',
               'linrec_real_bwd_kernel', 'linrec_complex_fwd_kernel', 'linrec_complex_bwd_kernel', 'gru_fwd_kernel', 'gru_bwd_kernel',
               'conv_fwd_kernel', 'conv_bwd_kernel', 'gemm_f32_kernel', 'sscan_fwd_local_kernel',
-              'sscan_bwd_local_kernel')                                         # RESEL_PROF_* of include/resel_hip.h, in id order
+              'sscan_bwd_local_kernel', 'sscan_gate_fwd_kernel', 'sscan_gate_bwd_kernel',
+              'sscan_group_reduce_kernel')                                      # RESEL_PROF_* of include/resel_hip.h, in id order
 GEMM_FLOPS = [0.0]            # 2 M N K of every resel_gemm_f32 call since the caller last reset it (bench.py's GEMM line)
 
 
@@ -118,6 +119,120 @@ def _sscan_bwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, dout, ck, d
         Bsz, L, Di, N, softplus, SSCAN_TIME_SEGMENTS, amax_dz, amax_ddelta, epoch, _stream()), 'selective_scan_bwd')
 
 
+# ---- every d_state from 1 to 256 on the five native kernels (include/resel_hip.h "state groups") --------------------------------------
+SSCAN_NATIVE_STATES = (4, 8, 16, 32, 64)     # the sizes resel_selective_scan_fwd / _bwd are built for
+SSCAN_MAX_GROUPS = 4                         # RESEL_SSCAN_MAX_GROUPS
+SSCAN_MAX_STATES = SSCAN_NATIVE_STATES[-1] * SSCAN_MAX_GROUPS
+
+
+def sscan_state_plan(N: int):
+    """How a scan over N states runs: [(first_state, states, kernel_N), ...], one native scan per entry.  A native N is itself; any other
+    N <= 64 is one group on the next native size (zero B / C columns: a padded state stays exactly 0 and adds exactly 0); 64 < N <= 256 is
+    N // 64 groups of 64 and the remainder on the smallest native size that holds it.  Only the last group is ever padded, so the padded
+    operands are the real columns followed by zeros.  Host-only; both training nodes consult this and nothing else."""
+    N = int(N)
+    if N < 1 or N > SSCAN_MAX_STATES:
+        raise ValueError(f'selective scan: d_state {N} is not supported: accepted are 1 to {SSCAN_MAX_STATES} ({", ".join(map(str, SSCAN_NATIVE_STATES))} '
+                         f'native, other sizes up to 64 zero-padded to the next of these, larger ones as groups of 64 plus a remainder); '
+                         f'{SSCAN_MAX_STATES} is this build\'s bound: {SSCAN_MAX_GROUPS} groups')
+    if N in SSCAN_NATIVE_STATES:
+        return [(0, N, N)]
+    top = SSCAN_NATIVE_STATES[-1]
+    plan = [(top * g, top, top) for g in range(N // top)] if N > top else []
+    rest = N - top * len(plan)
+    if rest:
+        plan.append((top * len(plan), rest, next(w for w in SSCAN_NATIVE_STATES if w >= rest)))
+    return plan
+
+
+def sscan_padded_states(plan) -> int:
+    """Columns of the B / C / A operands a plan's kernels read: the real states and the zero tail of the last group."""
+    return plan[-1][0] + plan[-1][2]
+
+
+def _group_A(A, plan):
+    """The dense [Di, kernel_N] `A` (or A_log) of every group: a native N takes the tensor itself, any other plan one `place_blocks` launch per
+    group, which copies the group's columns and zero-fills a padded tail (A_log = 0 there; any finite value would do)."""
+    Di, N = A.shape
+    if len(plan) == 1 and plan[0][2] == N:
+        return [A.float().contiguous()]
+    A = A.detach()
+    return [place_blocks(Di, k, [(0, 0)], A[:, f:f + s]) for f, s, k in plan]
+
+
+def _join_states(pieces, plan, N):
+    """Per-group [rows, kernel_N] results (dA, last state) -> [rows, N]: the real columns of every group, one launch."""
+    if len(plan) == 1 and plan[0][2] == N:
+        return pieces[0]
+    return place_blocks(pieces[0].shape[0], N, [(0, f) for f, _, _ in plan], *[t[:, :s] for t, (_, s, _) in zip(pieces, plan)])
+
+
+def _sscan_gate_fwd(parts, u, D, z, out, amax_out=None, epoch=0):
+    """parts [G, M, Di] dense; u, z, out token-major [M, Di] blocks (or [B, L, Di])."""
+    G, M, Di = parts.shape
+    check(lib().resel_sscan_gate_fwd(_p(parts), parts.stride(0), G, _p(u), u.stride(-2), _p(D), _p(z), 0 if z is None else z.stride(-2),
+                                     _p(out), out.stride(-2), M, Di, amax_out, epoch, _stream()), 'sscan_gate_fwd')
+
+
+def _sscan_gate_bwd(dout, parts, G, M, Di, u, D, z, g, dz, dD, amax_dz=None, epoch=0):
+    """parts: the forward's [G, M, Di] (None without z); g, dz: None iff z is None; dD: None iff D is None."""
+    ws = _ws(lib().resel_sscan_gate_bwd_workspace_bytes(M, Di), dout.device) if D is not None else None
+    check(lib().resel_sscan_gate_bwd(_p(dout), dout.stride(-2), _p(parts), 0 if parts is None else parts.stride(0), G, _p(u), u.stride(-2), _p(D),
+                                     _p(z), 0 if z is None else z.stride(-2), _p(g), 0 if g is None else g.stride(-2),
+                                     _p(dz), 0 if dz is None else dz.stride(-2), _p(dD), _p(ws), M, Di, amax_dz, epoch, _stream()), 'sscan_gate_bwd')
+
+
+def _sscan_group_reduce(du_parts, dd_parts, db_parts, g, D, du, ddelta, dbias, amax_ddelta=None, epoch=0):
+    G, M, Di = du_parts.shape
+    check(lib().resel_sscan_group_reduce(_p(du_parts), _p(dd_parts), du_parts.stride(0), _p(db_parts), G, _p(g), g.stride(-2), _p(D),
+                                         _p(du), du.stride(-2), _p(ddelta), ddelta.stride(-2), _p(dbias), M, Di, amax_ddelta, epoch, _stream()),
+          'sscan_group_reduce')
+
+
+def _plan_fwd(plan, A_g, Bsz, L, u, delta, z, Bm, Cm, D, delta_bias, start, out, need_grad, want_last, softplus, amax_out=None, epoch=0):
+    """The scan forward of a plan.  A_g: `_group_A`; Bm, Cm: `sscan_padded_states` columns wide.  One group: the scan itself, gate and skip
+    included.  More: every group scans its own columns in place with z = D = None into its slab of `parts`, then ONE gate pass.
+    -> (checkpoints per group, parts or None, last states per group or None)."""
+    dev, Di = u.device, A_g[0].shape[0]
+    cks = [_ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, k), dev) if need_grad else None for _, _, k in plan]
+    lasts = [torch.empty(Bsz, Di, k, dtype=torch.float32, device=dev) for _, _, k in plan] if want_last else None
+    if len(plan) == 1:
+        _sscan_fwd(Bsz, L, u, delta, z, A_g[0], Bm, Cm, D, delta_bias, start, out, cks[0], lasts[0] if want_last else None, softplus, amax_out, epoch)
+        return cks, None, lasts
+    parts = torch.empty(len(plan), Bsz * L, Di, dtype=torch.float32, device=dev)
+    for i, (f, _, k) in enumerate(plan):
+        _sscan_fwd(Bsz, L, u, delta, None, A_g[i], Bm[..., f:f + k], Cm[..., f:f + k], None, delta_bias, start, parts[i], cks[i],
+                   lasts[i] if want_last else None, softplus)
+    _sscan_gate_fwd(parts, u, D, z, out, amax_out, epoch)
+    return cks, (parts if z is not None else None), lasts                  # the backward needs the pre-gate sum for dz only
+
+
+def _plan_bwd(plan, A_g, Bsz, L, u, delta, z, Bm, Cm, D, delta_bias, start, dout, cks, parts, du, ddelta, dz, dB, dC, dD, dbias, softplus,
+              amax_dz=None, amax_ddelta=None, epoch=0):
+    """The scan backward of a plan: dB, dC as wide as Bm, Cm; -> dA per group.  More than one group: ONE gate pass forms the pre-gate gradient
+    every group takes as its dout (with dz and dD), the groups write their column blocks of dB / dC and their own du / ddelta, ONE pass sums
+    those (with the skip term's share of du and ddelta_bias)."""
+    dev, Di = u.device, A_g[0].shape[0]
+    dA_g = [torch.empty(Di, k, dtype=torch.float32, device=dev) for _, _, k in plan]
+    if len(plan) == 1:
+        _sscan_bwd(Bsz, L, u, delta, z, A_g[0], Bm, Cm, D, delta_bias, start, dout, cks[0], du, ddelta, dz, dB, dC, dA_g[0], dD, dbias, softplus,
+                   amax_dz, amax_ddelta, epoch)
+        return dA_g
+    G, M = len(plan), Bsz * L
+    g = torch.empty(M, Di, dtype=torch.float32, device=dev) if z is not None else None
+    if z is not None or D is not None:
+        _sscan_gate_bwd(dout, parts, G, M, Di, u, D, z, g, dz, dD, amax_dz, epoch)
+    gin = dout if g is None else g
+    du_p = torch.empty(G, M, Di, dtype=torch.float32, device=dev)
+    dd_p = torch.empty_like(du_p)
+    db_p = torch.empty(G, Di, dtype=torch.float32, device=dev) if dbias is not None else None
+    for i, (f, _, k) in enumerate(plan):
+        _sscan_bwd(Bsz, L, u, delta, None, A_g[i], Bm[..., f:f + k], Cm[..., f:f + k], None, delta_bias, start, gin, cks[i], du_p[i], dd_p[i], None,
+                   dB[..., f:f + k], dC[..., f:f + k], dA_g[i], None, None if db_p is None else db_p[i], softplus)
+    _sscan_group_reduce(du_p, dd_p, db_p, gin, D, du, ddelta, dbias, amax_ddelta, epoch)
+    return dA_g
+
+
 def _conv_fwd(Bsz, L, x, w, bias, mask, y, act, amax_y=None, epoch=0):
     Di, K = w.shape
     check(lib().resel_causal_conv1d_fwd(_p(x), x.stride(-2), _p(w), _p(bias), _p(mask), _p(y), y.stride(-2), Bsz, L, Di, K, act,
@@ -149,38 +264,47 @@ class SelectiveScanFn(torch.autograd.Function):
         delta_bias = None if delta_bias is None else delta_bias.float().contiguous()
         Bsz, L, Di = u.shape
         N = A.shape[1]
+        plan = sscan_state_plan(N)                                         # raises for a d_state outside 1 .. 256
+        Np = sscan_padded_states(plan)
+        A_g = _group_A(A, plan)
+        if Np != N:                                                        # [M, N] beside [M, Di] activations: padded copies, zero tail
+            Bm = place_blocks(Bsz * L, Np, [(0, 0)], Bm).view(Bsz, L, Np)
+            Cm = place_blocks(Bsz * L, Np, [(0, 0)], Cm).view(Bsz, L, Np)
         start = _flags(start, Bsz, L)
         out = torch.empty(Bsz, L, Di, dtype=torch.float32, device=u.device)
         need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
-        ck = None
-        if need_grad:
-            ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), u.device)
-        last = torch.empty(Bsz, Di, N, dtype=torch.float32, device=u.device) if return_last_state else None
-        _sscan_fwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, out, ck, last, int(bool(delta_softplus)))
-        ctx.save_for_backward(u, delta, A, Bm, Cm, D, z, delta_bias, start, ck)
+        cks, parts, lasts = _plan_fwd(plan, A_g, Bsz, L, u, delta, z, Bm, Cm, D, delta_bias, start, out, need_grad, return_last_state,
+                                      int(bool(delta_softplus)))
+        ctx.save_for_backward(u, delta, Bm, Cm, D, z, delta_bias, start, parts, *A_g, *cks)
         ctx.softplus = bool(delta_softplus)
+        ctx.plan, ctx.N = plan, N
         if return_last_state:
+            last = _join_states([t.view(Bsz * Di, -1) for t in lasts], plan, N).view(Bsz, Di, N)
             ctx.mark_non_differentiable(last)
             return out, last
         return out
 
     @staticmethod
     def backward(ctx, dout, *_):
-        u, delta, A, Bm, Cm, D, z, delta_bias, start, ck = ctx.saved_tensors
+        plan, N = ctx.plan, ctx.N
+        u, delta, Bm, Cm, D, z, delta_bias, start, parts = ctx.saved_tensors[:9]
+        A_g, cks = ctx.saved_tensors[9:9 + len(plan)], ctx.saved_tensors[9 + len(plan):]
         Bsz, L, Di = u.shape
-        N = A.shape[1]
+        Np = Bm.shape[-1]
         dout = _tok_major(dout)
         dev = u.device
         du = torch.empty(Bsz, L, Di, dtype=torch.float32, device=dev)
         ddelta = torch.empty_like(du)
         dz = torch.empty_like(du) if z is not None else None
-        dB = torch.empty(Bsz, L, N, dtype=torch.float32, device=dev)
+        dB = torch.empty(Bsz, L, Np, dtype=torch.float32, device=dev)
         dC = torch.empty_like(dB)
-        dA = torch.empty(Di, N, dtype=torch.float32, device=dev)
         dD = torch.empty(Di, dtype=torch.float32, device=dev) if D is not None else None
         dbias = torch.empty(Di, dtype=torch.float32, device=dev) if delta_bias is not None else None
-        _sscan_bwd(Bsz, L, u, delta, z, A, Bm, Cm, D, delta_bias, start, dout, ck, du, ddelta, dz, dB, dC, dA, dD, dbias, int(ctx.softplus))
-        return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None, None, None
+        dA_g = _plan_bwd(plan, A_g, Bsz, L, u, delta, z, Bm, Cm, D, delta_bias, start, dout, cks, parts, du, ddelta, dz, dB, dC, dD, dbias,
+                         int(ctx.softplus))
+        if Np != N:                                                        # whatever the backward computed for padded states is dropped
+            dB, dC = dB[..., :N], dC[..., :N]
+        return du, ddelta, _join_states(dA_g, plan, N), dB, dC, dD, dz, dbias, None, None, None, None
 
 
 def selective_scan_tm(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, start=None, delta_softplus=True,
@@ -221,6 +345,8 @@ class MambaInnerFn(torch.autograd.Function):
         R = dt_w.shape[1]
         K = conv_w.shape[-1]
         M = Bsz * L
+        plan = sscan_state_plan(N)                                         # raises for a d_state outside 1 .. 256
+        Np = sscan_padded_states(plan)
         x2 = x.reshape(M, Dm)
         maskf, startf = _flags(mask, Bsz, L), _flags(start, Bsz, L)
         xz = mm_nt(x2, in_w)                                               # [M, 2Di] = (x | z)
@@ -231,7 +357,10 @@ class MambaInnerFn(torch.autograd.Function):
         h_xc, p_xc, e_xc = _slot_args(track, x.device)
         _conv_fwd(Bsz, L, xz, cw, conv_b, maskf, xc, 1, p_xc, e_xc)          # reads the x half: the first Di columns of xz's rows
         tag_amax(xc, h_xc)
-        x_dbl = mm_nt(xc, xproj_w)                                         # [M, R + 2N] = (delta_r | B | C)
+        # a padded d_state: x_proj's weight gets zero rows behind its B rows and behind its C rows (one launch, as w32 below), so x_dbl and
+        # dx_dbl simply are Np states wide and no [M, .] activation is ever re-laid-out
+        xw = xproj_w if Np == N else place_blocks(R + 2 * Np, Di, [(0, 0), (R + Np, 0)], xproj_w.detach()[:R + N], xproj_w.detach()[R + N:])
+        x_dbl = mm_nt(xc, xw)                                              # [M, R + 2Np] = (delta_r | B | C)
         # delta = softplus(dt_proj(.) + bias) leaves the GEMM epilogue: the scan kernels spend no vector issue on it
         if narrow_on() and narrow_k_ok(x_dbl[:, :R], dt_w):
             # K = dt_rank = 16 against 137 MB of output: the streaming kernel with the weight resident in registers (no padded weight, no
@@ -246,23 +375,27 @@ class MambaInnerFn(torch.autograd.Function):
         else:
             dt = gemm_f32(x_dbl[:, :R], dt_w, True, True, dt_b, GEMM_SOFTPLUS)
         # delta_softplus code 6 = 4 (the kernels form A = -exp(A_log) themselves) + 2 (delta arrives finished: no delta_bias)
-        A = A_log.float().contiguous()
+        A_g = _group_A(A_log, plan)
         need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
-        ck = _ws(lib().resel_selective_scan_ckpt_bytes(Bsz, L, Di, N), x.device) if need_grad else None
         y = torch.empty(M, Di, dtype=torch.float32, device=x.device)
         h_y, p_y, e_y = _slot_args(track, x.device)
-        _sscan_fwd(Bsz, L, xc, dt, xz[:, Di:], A, x_dbl[:, R:R + N], x_dbl[:, R + N:], D, None, startf, y, ck, None, 6, p_y, e_y)
+        cks, parts, _ = _plan_fwd(plan, A_g, Bsz, L, xc, dt, xz[:, Di:], x_dbl[:, R:R + Np], x_dbl[:, R + Np:], D, None, startf, y, need_grad, False,
+                                  6, p_y, e_y)
         tag_amax(y, h_y)
         out = mm_nt(y, out_w)
         ctx.handles = keep_handles(ctx.ax, h_xc, h_y)                      # saved tensors come back untagged
-        ctx.save_for_backward(x2, in_w, cw, conv_b, xproj_w, dt_w, dt_b, A, D, out_w, maskf, startf, xz, xc, x_dbl, dt, y, ck)
+        ctx.save_for_backward(x2, in_w, cw, conv_b, xw, dt_w, dt_b, D, out_w, maskf, startf, xz, xc, x_dbl, dt, y, parts, *A_g, *cks)
         ctx.dims = (Bsz, L, Dm, Di, N, R, K, conv_w.shape)
+        ctx.plan = plan
         return out.view(Bsz, L, -1)
 
     @staticmethod
     def backward(ctx, dout):
-        (x2, in_w, cw, conv_b, xproj_w, dt_w, dt_b, A, D, out_w, maskf, startf, xz, xc, x_dbl, dt, y, ck) = ctx.saved_tensors
+        plan = ctx.plan
+        (x2, in_w, cw, conv_b, xw, dt_w, dt_b, D, out_w, maskf, startf, xz, xc, x_dbl, dt, y, parts) = ctx.saved_tensors[:17]
+        A_g, cks = ctx.saved_tensors[17:17 + len(plan)], ctx.saved_tensors[17 + len(plan):]
         Bsz, L, Dm, Di, N, R, K, cw_shape = ctx.dims
+        Np = sscan_padded_states(plan)
         M = Bsz * L
         dev = x2.device
         do2 = dout.reshape(M, -1)
@@ -272,17 +405,17 @@ class MambaInnerFn(torch.autograd.Function):
         d_out_w = wgrad(do2, y, amax_x=h_y)
         dy = mm_nn(do2, out_w)                                             # [M, Di]
         dxz = torch.empty(M, 2 * Di, dtype=torch.float32, device=dev)      # fully written: conv bwd -> [:, :Di], scan bwd -> [:, Di:]
-        dx_dbl = torch.empty(M, R + 2 * N, dtype=torch.float32, device=dev)
+        dx_dbl = torch.empty(M, R + 2 * Np, dtype=torch.float32, device=dev)
         dxc = torch.empty(M, Di, dtype=torch.float32, device=dev)
         ddt = torch.empty(M, Di, dtype=torch.float32, device=dev)
-        dA = torch.empty(Di, N, dtype=torch.float32, device=dev)
         dD = torch.empty(Di, dtype=torch.float32, device=dev)
         ddt_b = torch.empty(Di, dtype=torch.float32, device=dev)
         track = amax_tracking() and M * Di >= (1 << 20)
         h_dxz, p_dxz, e_b = _slot_args(track, dev)                         # ONE handle for dxz: the scan fills its z half, the conv its x half
         h_ddt, p_ddt, _ = _slot_args(track, dev)                           # (published under the same epoch e_b)
-        _sscan_bwd(Bsz, L, xc, dt, xz[:, Di:], A, x_dbl[:, R:R + N], x_dbl[:, R + N:], D, None, startf, dy, ck,
-                   dxc, ddt, dxz[:, Di:], dx_dbl[:, R:R + N], dx_dbl[:, R + N:], dA, dD, ddt_b, 6, p_dxz, p_ddt, e_b)
+        dA_g = _plan_bwd(plan, A_g, Bsz, L, xc, dt, xz[:, Di:], x_dbl[:, R:R + Np], x_dbl[:, R + Np:], D, None, startf, dy, cks, parts,
+                         dxc, ddt, dxz[:, Di:], dx_dbl[:, R:R + Np], dx_dbl[:, R + Np:], dD, ddt_b, 6, p_dxz, p_ddt, e_b)
+        dA = _join_states(dA_g, plan, N)                                   # the real columns (a padded state's are dropped)
         tag_amax(ddt, h_ddt)
         # [Di, R] with a 66 752-long reduction: hand-written MFMA kernel (the library reaches 7 TFLOP/s on this shape)
         if narrow_on() and narrow_n_pair_ok(ddt, dt_w, x_dbl[:, :R]):
@@ -293,9 +426,11 @@ class MambaInnerFn(torch.autograd.Function):
                 else gemm_f32(ddt, x_dbl[:, :R], False, False)
             mm_nn(ddt, dt_w, out=dx_dbl[:, :R])                              # straight into its column block of dx_dbl
         d_xproj_w = wgrad(dx_dbl, xc, amax_x=h_xc)
+        if Np != N:                                                        # the real rows; a padded state's dB / dC columns are exactly 0 (its C is)
+            d_xproj_w = place_blocks(R + 2 * N, Di, [(0, 0), (R + N, 0)], d_xproj_w[:R + N], d_xproj_w[R + Np:R + Np + N])
         # the conv output's gradient = the scan's du (in dxc) + the x_proj input gradient: handed to the conv backward as TWO tensors
         # (summed on load) - the accumulating GEMM epilogue cost 150-214 us per call against 67 for the plain product
-        gx = mm_nn(dx_dbl, xproj_w)
+        gx = mm_nn(dx_dbl, xw)
         dcw = torch.empty(Di, K, dtype=torch.float32, device=dev)
         dcb = torch.empty(Di, dtype=torch.float32, device=dev) if conv_b is not None else None
         _conv_bwd(Bsz, L, xz, cw, conv_b, maskf, dxc, gx, dxz, dcw, dcb, 1, p_dxz, e_b)       # x halves of xz and dxz: their rows' first Di columns
