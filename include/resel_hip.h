@@ -240,7 +240,9 @@ int resel_lru_params_bwd(const float* params_log, const float* dout, float* dpar
  * gi = x W_ih^T + b_ih: [B, L, 3H] dense (r, z, n blocks); w_hh: [3H, H]; b_hh: [3H]; h0: [B, H] or NULL.
  *   r = sig(gi_r + W_hr h + b_hr) ; z = sig(gi_z + W_hz h + b_hz) ; n = tanh(gi_n + r * (W_hn h + b_hn))
  *   h' = (1 - z) n + z h ;  h_all: [B, L, H].  gates (optional, training): [B, L, 4H] saves r, z, n and
- *   (W_hn h + b_hn) for the backward.  Supported: H % 16 == 0 and H <= 256, or H in {320, 384, 448, 512}.
+ *   (W_hn h + b_hn) for the backward.  Supported: H % 16 == 0 and H <= 256, or H in {288, 320, 336, 352, 384, 416, 448, 480, 512,
+ *   640, 768, 896, 1024};
+ *   every other width from 1 to 1024 runs zero-padded on the next of these (resel_gru_pad_* below; the padding is exact).
  * The recurrence is T-sequential; each step is one launch (grid = H/16 unit slices x ceil(B/16) row groups)
  * enqueued back-to-back from C.  workspace: resel_gru_workspace_bytes() (re-laid-out W_hh slices, carry).
  * Backward returns the pre-activation gradients of BOTH projections: dgi [B, L, 3H] (w.r.t. gi) and
@@ -270,6 +272,24 @@ int resel_gru_multi_fwd(int n_net, const float* const* gi, const float* const* w
                         const float* const* h0, float* const* h_all, float* const* gates, void* workspace,
                         int B, int L, int H, resel_stream_t stream);
 int resel_gru_multi_form(int n_net, int B, int H);
+
+/* Zero padding of a GRU of true width H onto a kernel width Hk the entries above accept (1 <= H < Hk).  Padding is PER GATE BLOCK:
+ * row g * Hk + j of a padded tensor is row g * H + j of the true one (j < H) and zero otherwise; W_hh is padded in its columns too.
+ * A padded unit stays exactly 0 through the forward and receives exactly 0 in the backward, so the true units compute what they
+ * would at width H on this kernel.  Every entry is ONE launch, reads nothing on the host and is capturable.
+ *   resel_gru_pad_params:   w_ih [3H, n_in], b_ih [3H], w_hh [3H, H], b_hh [3H] -> [3Hk, n_in], [3Hk], [3Hk, Hk], [3Hk].
+ *                           w_ih / b_ih and their outputs may all four be NULL (n_in is then ignored): recurrent parameters only.
+ *   resel_gru_unpad_params: the inverse slice, for the four gradients (same NULL rule).
+ *   resel_gru_pad_rows:     src [rows, G, H] -> dst [rows, G, Hk], zero-filled (G = 3: gi; G = 1: h0, dh_all).  1 <= G <= 4.
+ *   resel_gru_unpad_rows:   src [rows, G, Hk] -> dst [rows, G, H] (h_all, dgi).
+ * RESEL_EINVAL: a NULL or not 4-byte aligned pointer, Hk not a supported kernel width, H outside 1 .. Hk - 1, n_in < 1, rows < 1,
+ * G outside 1 .. 4, or a tensor of 2^31 elements or more. */
+int resel_gru_pad_params(const float* w_ih, const float* b_ih, const float* w_hh, const float* b_hh,
+                         float* w_ih_k, float* b_ih_k, float* w_hh_k, float* b_hh_k, int n_in, int H, int Hk, resel_stream_t stream);
+int resel_gru_unpad_params(const float* dw_ih_k, const float* db_ih_k, const float* dw_hh_k, const float* db_hh_k,
+                           float* dw_ih, float* db_ih, float* dw_hh, float* db_hh, int n_in, int H, int Hk, resel_stream_t stream);
+int resel_gru_pad_rows(const float* src, float* dst, long long rows, int G, int H, int Hk, resel_stream_t stream);
+int resel_gru_unpad_rows(const float* src, float* dst, long long rows, int G, int H, int Hk, resel_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * cgpt attention core: packed var-len causal attention with ALiBi, bf16 MFMA (v_mfma_f32_32x32x16_bf16), fp32 softmax.

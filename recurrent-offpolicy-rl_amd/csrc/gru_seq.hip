@@ -9,7 +9,7 @@
 // LATENCY of one step is what matters, so the step is spread over the whole chip and keeps its operands close:
 //   grid = (H/16 hidden-unit slices) x (B/4 row groups)  [16 x 16 = 256 workgroups at H = 256, B = 64: one per CU];
 //   thread (j, kq) of a workgroup owns output unit j of the slice and the kq-th 1/16 of the reduction axis, and holds
-//   that piece of W_hh for all three gates IN REGISTERS (3H/16 <= 96 floats, fetched with fully coalesced float4 loads
+//   that piece of W_hh for all three gates IN REGISTERS (3H/16 <= 192 floats, fetched with fully coalesced float4 loads
 //   from a copy laid out once per call as [slice][float4 chunk][thread]); the 4 rows of h_{t-1} (forward) / of the gate
 //   gradients (backward) sit in LDS and are read as broadcast float4s; the 16 partial sums of an output meet in LDS.
 // A third entry, resel_gru_multi_fwd, runs up to four INDEPENDENT recurrences of equal shape through the same two drivers in one launch
@@ -36,7 +36,7 @@ __device__ __forceinline__ float gru_tanh(float x) {
 constexpr int US = 16;    // hidden units per block
 constexpr int RG = 4;     // batch rows per block
 constexpr int KQMAX = 16; // reduction-axis pieces: H = KC * KQ with KQ <= 16; a block has 16 * KQ threads
-constexpr int HMAX = 512;
+constexpr int HMAX = 1024;
 
 // forward copy: thread (kq, j) of slice s needs W_hh[g*H + s*16 + j][kq*KC + i], g < 3, i < KC = H/16, as 3*KC/4 float4s
 //   wf[((s * NC + c) * NT + tid) * 4 + e]   with chunk c = g * (KC/4) + i/4, e = i % 4, tid = kq * 16 + j, NT = 16 KQ
@@ -534,14 +534,16 @@ __global__ __launch_bounds__(256) void gru_bwd_persistent_kernel(GruBwd p, u64* 
 }
 
 // H = KC * KQ with KC in {4, 8, 12, 16, 24, 32} (templated) and 4 <= KQ <= 16: every multiple of 16 up to 256, and
-// 320 / 384 / 448 / 512 above
+// 288 / 320 / 336 / 352 / 384 / 416 / 448 / 480 / 512 above.  640 / 768 / 896 / 1024 are named one by one (KQ = 16, KC = 40 / 48 / 56 / 64): the accepted set is a
+// list, not whatever factors (a KC of 40 in the candidates would let 200 = 40 x 5 in).
 inline int pick_kc(int H) {
     const int cand[6] = {4, 8, 12, 16, 24, 32};
     for (int kc : cand)
         if (H % kc == 0 && H / kc <= KQMAX && H / kc >= 4) return kc;
+    if (H == 640 || H == 768 || H == 896 || H == 1024) return H / KQMAX;
     return 0;
 }
-// The run-time KC as a template argument: f(std::integral_constant<int, KC>) for the six instantiations, RESEL_EINVAL for any other KC.
+// The run-time KC as a template argument: f(std::integral_constant<int, KC>) for the ten instantiations, RESEL_EINVAL for any other KC.
 template <typename F>
 inline int with_kc(int KC, F&& f) {
     switch (KC) {
@@ -551,6 +553,10 @@ inline int with_kc(int KC, F&& f) {
         case 16: return f(std::integral_constant<int, 16>{});
         case 24: return f(std::integral_constant<int, 24>{});
         case 32: return f(std::integral_constant<int, 32>{});
+        case 40: return f(std::integral_constant<int, 40>{});
+        case 48: return f(std::integral_constant<int, 48>{});
+        case 56: return f(std::integral_constant<int, 56>{});
+        case 64: return f(std::integral_constant<int, 64>{});
     }
     return RESEL_EINVAL;
 }
@@ -585,6 +591,14 @@ inline bool gru_persistent_allowed() {
 // problems keep the launch-per-step form.
 // (the multi-network forward below has its own residency rule: its grid is up to four times as large)
 inline bool persistent_ok(int B, int H) { return gru_persistent_allowed() && gru_workgroups(B, H) <= 256; }
+// gfx950 build of the widths above 512 (KC 40 / 48 / 56 / 64; 256 threads, so one workgroup per CU needs <= 512 registers per lane):
+//   forward persistent 216 / 245 / 277 / 311 registers, 23-29 KB of LDS, no scratch: resident at one per CU, rule above holds;
+//   backward persistent 430 / 512 / 512 / 512 registers, 35-53 KB of LDS, and 352 / 676 bytes of scratch per lane at KC 56 / 64
+//   (the carry-independent operands of a step, 8 registers per (row, unit) item and RG * KC / 16 items, on top of 3 KC of W_hh).
+// A step that spills cannot keep the 3.9 us the persistent form is there for, so those two widths take the per-step backward
+// (200 / 224 registers, no scratch) whatever the grid; everything else is routed as before.
+constexpr int BWD_PERSISTENT_KC_MAX = 48;
+inline bool bwd_persistent_ok(int B, int H) { return persistent_ok(B, H) && pick_kc(H) <= BWD_PERSISTENT_KC_MAX; }
 
 }  // namespace
 
@@ -635,7 +649,7 @@ extern "C" size_t resel_gru_multi_workspace_bytes(int n_net, int B, int L, int H
 // and at most 8 waves; a workgroup here has at most 4 waves, one per SIMD, so workgroups per CU = waves per SIMD, further bounded
 // by 160 KB of LDS and by 7 (the SGPR rule for 82-96 SGPRs).  gfx950 build of this file: KC 4 / 8 / 12 / 16 / 24 / 32 use
 // 60 / 78 / 98 / 124 / 154 / 184 VGPRs, 73-84 SGPRs, no scratch, 14-21 KB of LDS -> 7 / 6 / 4 / 4 / 3 / 2 workgroups per CU (H = 256: 4,
-// H = 384: 3, H = 512: 2; the compiler's own `Occupancy [waves/SIMD]` remark says 8 / 6 / 4 / 4 / 3 / 2).
+// H = 384: 3, H = 512: 2; the compiler's own `Occupancy [waves/SIMD]` remark says 8 / 6 / 4 / 4 / 3 / 2).  KC 40 / 48 / 56 / 64: below.
 // Cached per instantiation; 0 when no device answers (the per-step form needs no residency).
 template <int KC>
 inline int multi_resident_cap() {
@@ -653,6 +667,10 @@ inline int multi_resident_cap() {
         const int lds = (int)fa.sharedSizeBytes > 0 ? (160 * 1024) / (int)fa.sharedSizeBytes : 8;
         if (per_cu > lds) per_cu = lds;
         if (per_cu > 7) per_cu = 7;
+        // KC 40 / 48 / 56 / 64 (H = 640 .. 1024): 214 / 243 / 274 / 309 registers (the last two 256 + 18 / 53 accumulation registers) -> 2 / 2 /
+        // 1 / 1 per CU.  Held to the compiler's figure whatever the runtime reports for a kernel that uses both register files.
+        constexpr int known = KC >= 56 ? 1 : (KC >= 40 ? 2 : 7);
+        if (per_cu > known) per_cu = known;
         return per_cu * prop.multiProcessorCount;
     }();
     return cap;
@@ -725,13 +743,17 @@ extern "C" int resel_gru_seq_bwd(const float* w_hh, const float* h0, const float
     hipLaunchKernelGGL(gru_layout_bwd_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w_hh, ws.wcopy(), H, KQ);
     if (hipMemsetAsync(carry, 0, ws.carry_bytes, s) != hipSuccess) return RESEL_ELAUNCH;
     GruBwd p{ws.wcopy(), h0, h_all, gates, dh_all, nullptr, nullptr, dgi, dgh, B, L, H, 0};
-    if (persistent_ok(B, H)) {
+    if (bwd_persistent_ok(B, H)) {
         if (hipMemsetAsync(ws.sync(), 0, ws.sync_bytes(), s) != hipSuccess) return RESEL_ELAUNCH;
         p.carry_out = carry;
         const dim3 pgrid(gru_workgroups(B, H));
         return with_kc(KC, [&](auto kc) {
-            launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<decltype(kc)::value>, pgrid, dim3(16 * KQ), 0, s, p, ws.xchg(), ws.err());
-            return launch_status();
+            if constexpr (decltype(kc)::value <= BWD_PERSISTENT_KC_MAX) {        // the spilling instantiations are not even built
+                launch_timed(RESEL_PROF_GRU_BWD, gru_bwd_persistent_kernel<decltype(kc)::value>, pgrid, dim3(16 * KQ), 0, s, p, ws.xchg(), ws.err());
+                return launch_status();
+            } else {
+                return (int)RESEL_EINVAL;
+            }
         });
     }
     dim3 grid(H / US, (B + RG - 1) / RG);
@@ -744,4 +766,89 @@ extern "C" int resel_gru_seq_bwd(const float* w_hh, const float* h0, const float
         }
         return launch_status();
     });
+}
+
+// ---- widths that are not native: zero padding per gate block ----------------------------------------------------------
+// One launch moves up to four tensors (segment in grid.y).  A segment is seen as [outer][G][width][inner]: the padded side has
+// width Hk and inner `inner_k`, the true side width H and inner `inner_t` (W_hh: inner H / Hk, everything else equal inners).
+namespace {
+struct GruPadSeg {
+    const float* src;
+    float* dst;
+    int outer, G, inner_t, inner_k;
+    int n;                                           // elements of dst
+};
+struct GruPadArgs {
+    GruPadSeg seg[4];
+    int H, Hk;
+};
+template <bool WIDEN>
+__global__ __launch_bounds__(256) void gru_pad_kernel(GruPadArgs a) {
+    const GruPadSeg sg = a.seg[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= sg.n) return;
+    const int wd = WIDEN ? a.Hk : a.H, inn = WIDEN ? sg.inner_k : sg.inner_t;      // dst geometry
+    const int c = i % inn;
+    int r = i / inn;
+    const int j = r % wd; r /= wd;                   // r = outer * G + g
+    if (WIDEN) sg.dst[i] = (j < a.H && c < sg.inner_t) ? sg.src[((int64_t)r * a.H + j) * sg.inner_t + c] : 0.f;
+    else sg.dst[i] = sg.src[((int64_t)r * a.Hk + j) * sg.inner_k + c];
+}
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool pad_widths_ok(int H, int Hk) { return gru_ok(1, 1, Hk) && H >= 1 && H < Hk; }
+
+template <bool WIDEN>
+inline int gru_pad_launch(GruPadArgs& a, int nseg, hipStream_t s) {
+    int nmax = 0;
+    for (int k = 0; k < nseg; ++k) {
+        GruPadSeg& sg = a.seg[k];
+        const int64_t n = (int64_t)sg.outer * sg.G * (WIDEN ? a.Hk : a.H) * (WIDEN ? sg.inner_k : sg.inner_t);
+        const int64_t nk = (int64_t)sg.outer * sg.G * a.Hk * sg.inner_k;
+        if (!sg.src || !sg.dst || !aligned4(sg.src) || !aligned4(sg.dst) || n < 1 || nk >= ((int64_t)1 << 31) - 256) return RESEL_EINVAL;
+        sg.n = (int)n;
+        if (sg.n > nmax) nmax = sg.n;
+    }
+    hipLaunchKernelGGL(gru_pad_kernel<WIDEN>, dim3((unsigned)((nmax + 255) / 256), nseg), dim3(256), 0, s, a);
+    return launch_status();
+}
+template <bool WIDEN>
+inline int gru_pad_params(const float* w_ih, const float* b_ih, const float* w_hh, const float* b_hh,
+                          float* o_w_ih, float* o_b_ih, float* o_w_hh, float* o_b_hh, int n_in, int H, int Hk, hipStream_t s) {
+    if (!pad_widths_ok(H, Hk)) return RESEL_EINVAL;
+    const bool none_ih = !w_ih && !b_ih && !o_w_ih && !o_b_ih;
+    if (!none_ih && n_in < 1) return RESEL_EINVAL;
+    GruPadArgs a{};
+    a.H = H; a.Hk = Hk;
+    int k = 0;
+    a.seg[k++] = GruPadSeg{w_hh, o_w_hh, 1, 3, H, Hk, 0};
+    a.seg[k++] = GruPadSeg{b_hh, o_b_hh, 1, 3, 1, 1, 0};
+    if (!none_ih) {                                  // a partly given pair fails the NULL check of the launch
+        a.seg[k++] = GruPadSeg{w_ih, o_w_ih, 1, 3, n_in, n_in, 0};
+        a.seg[k++] = GruPadSeg{b_ih, o_b_ih, 1, 3, 1, 1, 0};
+    }
+    return gru_pad_launch<WIDEN>(a, k, s);
+}
+template <bool WIDEN>
+inline int gru_pad_rows(const float* src, float* dst, long long rows, int G, int H, int Hk, hipStream_t s) {
+    if (!pad_widths_ok(H, Hk) || rows < 1 || G < 1 || G > 4 || rows >= (1ll << 31) || rows * G * (long long)Hk >= (1ll << 31) - 256) return RESEL_EINVAL;
+    GruPadArgs a{};
+    a.H = H; a.Hk = Hk;
+    a.seg[0] = GruPadSeg{src, dst, (int)rows, G, 1, 1, 0};
+    return gru_pad_launch<WIDEN>(a, 1, s);
+}
+}  // namespace
+
+extern "C" int resel_gru_pad_params(const float* w_ih, const float* b_ih, const float* w_hh, const float* b_hh,
+                                    float* w_ih_k, float* b_ih_k, float* w_hh_k, float* b_hh_k, int n_in, int H, int Hk, resel_stream_t stream) {
+    return gru_pad_params<true>(w_ih, b_ih, w_hh, b_hh, w_ih_k, b_ih_k, w_hh_k, b_hh_k, n_in, H, Hk, (hipStream_t)stream);
+}
+extern "C" int resel_gru_unpad_params(const float* dw_ih_k, const float* db_ih_k, const float* dw_hh_k, const float* db_hh_k,
+                                      float* dw_ih, float* db_ih, float* dw_hh, float* db_hh, int n_in, int H, int Hk, resel_stream_t stream) {
+    return gru_pad_params<false>(dw_ih_k, db_ih_k, dw_hh_k, db_hh_k, dw_ih, db_ih, dw_hh, db_hh, n_in, H, Hk, (hipStream_t)stream);
+}
+extern "C" int resel_gru_pad_rows(const float* src, float* dst, long long rows, int G, int H, int Hk, resel_stream_t stream) {
+    return gru_pad_rows<true>(src, dst, rows, G, H, Hk, (hipStream_t)stream);
+}
+extern "C" int resel_gru_unpad_rows(const float* src, float* dst, long long rows, int G, int H, int Hk, resel_stream_t stream) {
+    return gru_pad_rows<false>(src, dst, rows, G, H, Hk, (hipStream_t)stream);
 }

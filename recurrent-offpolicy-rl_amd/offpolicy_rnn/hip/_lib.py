@@ -102,6 +102,10 @@ SIGNATURES = {
     'resel_gru_multi_workspace_bytes': (c_size_t, [I, I, I, I]),
     'resel_gru_multi_fwd': (c_int, [I, P, P, P, P, P, P, P, I, I, I, S]),
     'resel_gru_multi_form': (c_int, [I, I, I]),
+    'resel_gru_pad_params': (c_int, [P, P, P, P, P, P, P, P, I, I, I, S]),
+    'resel_gru_unpad_params': (c_int, [P, P, P, P, P, P, P, P, I, I, I, S]),
+    'resel_gru_pad_rows': (c_int, [P, P, L, I, I, I, S]),
+    'resel_gru_unpad_rows': (c_int, [P, P, L, I, I, I, S]),
     'resel_attn_varlen_fwd_workspace_bytes': (c_size_t, [I, I]),
     'resel_attn_varlen_fwd': (c_int, [P, P, P, P, P, P, I, I, I, I, I, F, F, U, U, S]),
     'resel_attn_varlen_bwd_workspace_bytes': (c_size_t, [I, I, I, I, I]),

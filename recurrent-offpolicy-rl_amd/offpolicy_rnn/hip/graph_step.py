@@ -27,6 +27,7 @@ call and `replay_device()` replays it with no copy and no synchronise.  Without 
 
 Parameters are read through their storage, so in-place optimiser steps are seen by the next replay; call
 `invalidate()` after anything that re-allocates them (`load`, `.to`)."""
+import gc
 from typing import Callable, Optional
 
 import numpy as np
@@ -133,8 +134,18 @@ class GraphedPolicyStep:
                 self._forward()
         torch.cuda.current_stream(self.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
-            self._forward()
+        # No cyclic garbage collection while the stream captures (as `GraphedUpdate._record`): a dead captured graph that only the collector
+        # can free - a dropped trainer or evaluator is a cycle through its step object and the `after_step` hook - synchronises the device
+        # in its destructor, which a capturing stream refuses, and the process aborts.  When the collector runs is the allocator's choice.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.no_grad(), torch.cuda.graph(graph):
+                self._forward()
+        finally:
+            if gc_was_on:
+                gc.enable()
         # the warm-up really ran (and capture advanced the host counters): put the episode state back
         for h, k in zip(self._hidden._data, keep):
             if k is not None:

@@ -7,6 +7,7 @@ current stream and autograd bookkeeping.
 Layout: activations are token-major `[B, L, C]` (channel stride 1).  Column slices of a wider row-major
 tensor (e.g. the `x` / `z` halves of `in_proj`'s output) are passed by stride, never copied.
 """
+import collections
 import ctypes
 import os
 from typing import Optional
@@ -939,9 +940,115 @@ class GruSeqFn(torch.autograd.Function):
         return dgi, dw_hh, db_hh, None
 
 
+GRU_MAX_HIDDEN = 1024
+# widths csrc/gru_seq.hip accepts (`pick_kc`): every multiple of 16 up to 256; the multiples of 16 up to 512 that split into 4 to 16
+# pieces of 24 or 32; and 640, 768, 896, 1024, named one by one
+GRU_NATIVE_WIDTHS = tuple(range(16, 257, 16)) + (288, 320, 336, 352, 384, 416, 448, 480, 512) + (640, 768, 896, 1024)
+GruWidthPlan = collections.namedtuple('GruWidthPlan', 'Hk native')
+
+
+def gru_width_plan(H: int) -> GruWidthPlan:
+    """The kernel width a GRU of hidden width H runs at: (Hk, native).  A native width is itself; every other width from 1 to 1024 is
+    zero-padded per gate block onto the smallest native width above it (a padded unit has zero parameters and a zero initial state: it
+    stays exactly 0 and adds exactly 0 to the real units, forward and backward).  Host-only; the module, `gru_seq` and `gru_seq_multi`
+    consult this and nothing else."""
+    H = int(H)
+    if H < 1 or H > GRU_MAX_HIDDEN:
+        raise ValueError(f'gru: hidden width {H} is not supported: accepted are 1 to {GRU_MAX_HIDDEN} (native widths: the multiples of 16 up to 256 and '
+                         f'{", ".join(map(str, GRU_NATIVE_WIDTHS[16:]))}; every other width zero-padded to the next of these); '
+                         f'{GRU_MAX_HIDDEN} is this build\'s bound')
+    Hk = next(w for w in GRU_NATIVE_WIDTHS if w >= H)
+    return GruWidthPlan(Hk, Hk == H)
+
+
+def gru_pad_rows(x, G, H, Hk):
+    """x [..., G * H] -> [..., G * Hk], each of the G blocks zero-filled from H to Hk (`resel_gru_pad_rows`; no autograd)."""
+    x = x.float().contiguous()
+    out = torch.empty(x.shape[:-1] + (G * Hk,), dtype=torch.float32, device=x.device)
+    check(lib().resel_gru_pad_rows(_p(x), _p(out), x.numel() // (G * H), G, H, Hk, _stream()), 'gru_pad_rows')
+    return out
+
+
+def gru_unpad_rows(x, G, H, Hk):
+    """x [..., G * Hk] -> [..., G * H]: the first H of each block (`resel_gru_unpad_rows`; no autograd)."""
+    x = x.float().contiguous()
+    out = torch.empty(x.shape[:-1] + (G * H,), dtype=torch.float32, device=x.device)
+    check(lib().resel_gru_unpad_rows(_p(x), _p(out), x.numel() // (G * Hk), G, H, Hk, _stream()), 'gru_unpad_rows')
+    return out
+
+
+class GruPadRowsFn(torch.autograd.Function):
+    """Widen (`widen`) or narrow the G blocks of the last axis between H and Hk; the backward is the other pass."""
+
+    @staticmethod
+    def forward(ctx, x, G, H, Hk, widen):
+        ctx.geom = (G, H, Hk, widen)
+        return (gru_pad_rows if widen else gru_unpad_rows)(x, G, H, Hk)
+
+    @staticmethod
+    def backward(ctx, g):
+        G, H, Hk, widen = ctx.geom
+        return (gru_unpad_rows if widen else gru_pad_rows)(g, G, H, Hk), None, None, None, None
+
+
+class GruPadParamsFn(torch.autograd.Function):
+    """nn.GRU's parameters at the true width -> the same at the kernel width Hk, padded per gate block: (W_ih [3Hk, in], b_ih [3Hk],
+    W_hh [3Hk, Hk], b_hh [3Hk]).  ONE node per forward, one launch each way (`resel_gru_pad_params` / `resel_gru_unpad_params`); the
+    backward slices the four gradients back.  w_ih and b_ih may both be None (the recurrent parameters alone)."""
+
+    @staticmethod
+    def forward(ctx, w_ih, b_ih, w_hh, b_hh, Hk):
+        _need_cuda('gru_pad_params', w_ih, b_ih, w_hh, b_hh)
+        H = w_hh.shape[1]
+        srcs = [None if t is None else t.float().contiguous() for t in (w_ih, b_ih, w_hh, b_hh)]
+        n_in = 0 if w_ih is None else w_ih.shape[1]
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=w_hh.device)
+        outs = [None if w_ih is None else new(3 * Hk, n_in), None if b_ih is None else new(3 * Hk), new(3 * Hk, Hk), new(3 * Hk)]
+        check(lib().resel_gru_pad_params(*[_p(t) for t in srcs], *[_p(t) for t in outs], n_in, H, Hk, _stream()), 'gru_pad_params')
+        ctx.geom = (n_in, H, Hk)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        n_in, H, Hk = ctx.geom
+        grads = [None if g is None else g.float().contiguous() for g in grads]
+        dev = grads[2].device
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        outs = [None if grads[0] is None else new(3 * H, n_in), None if grads[1] is None else new(3 * H), new(3 * H, H), new(3 * H)]
+        check(lib().resel_gru_unpad_params(*[_p(t) for t in grads], *[_p(t) for t in outs], n_in, H, Hk, _stream()), 'gru_unpad_params')
+        return tuple(outs) + (None,)
+
+
+def gru_pad_params(w_ih, b_ih, w_hh, b_hh, Hk):
+    return GruPadParamsFn.apply(w_ih, b_ih, w_hh, b_hh, Hk)
+
+
+def gru_pad_state(h0, H, Hk):
+    """Initial state [.., B, H] (or None) -> [B, Hk] with a zero tail: the state of a padded unit."""
+    return None if h0 is None else gru_pad_rows(h0.detach().reshape(-1, H), 1, H, Hk)
+
+
+def gru_narrow(y, H, Hk):
+    """Hidden states at the kernel width [B, L, Hk] -> the true units [B, L, H]; the backward widens the gradient with zeros."""
+    return GruPadRowsFn.apply(y, 1, H, Hk, False)
+
+
+def _gru_widen_job(gi, w_hh, b_hh, h0, H, Hk):
+    """A job at a true width that is not native -> the same job at Hk.  (The module pads its PARAMETERS and projects straight to
+    [B, L, 3Hk]; a caller that arrives here with gi at the true width pays one pass over gi instead.)"""
+    _need_cuda('gru_seq', gi, w_hh, b_hh, h0)
+    _, _, w_hh_k, b_hh_k = gru_pad_params(None, None, w_hh, b_hh, Hk)
+    return GruPadRowsFn.apply(gi, 3, H, Hk, True), w_hh_k, b_hh_k, gru_pad_state(h0, H, Hk)
+
+
 def gru_seq(gi, w_hh, b_hh, h0=None):
-    """gi = x W_ih^T + b_ih [B, L, 3H] -> all hidden states [B, L, H] (torch.nn.GRU gate order / formula)."""
-    return GruSeqFn.apply(gi, w_hh, b_hh, h0)
+    """gi = x W_ih^T + b_ih [B, L, 3H] -> all hidden states [B, L, H] (torch.nn.GRU gate order / formula).  Any H from 1 to 1024
+    (`gru_width_plan`); a native width takes the kernels as it is."""
+    H = gi.shape[-1] // 3
+    Hk, native = gru_width_plan(H)
+    if native:
+        return GruSeqFn.apply(gi, w_hh, b_hh, h0)
+    return gru_narrow(GruSeqFn.apply(*_gru_widen_job(gi, w_hh, b_hh, h0, H, Hk)), H, Hk)
 
 
 GRU_MULTI_MAX = 4             # networks one `resel_gru_multi_fwd` launch takes
@@ -974,10 +1081,21 @@ def gru_seq_multi(jobs):
     """jobs = [(gi, w_hh, b_hh, h0, need_grad), ...] (1 to 4 of them, equal [B, L, 3H]) -> [h_all, ...]: independent GRU recurrences
     that share ONE launch (`resel_gru_multi_fwd`) instead of one stream each.  Every output is bit for bit what `gru_seq` returns for
     that job alone.  A job with need_grad saves its gates and takes part in autograd; the others are constants whatever their
-    tensors' `requires_grad` says (target networks, no-grad passes)."""
+    tensors' `requires_grad` says (target networks, no-grad passes).  Jobs at a width that is not native are widened as `gru_seq`
+    widens them (they share H, so they share the kernel width) and their outputs narrowed."""
     n = len(jobs)
     if not 1 <= n <= GRU_MULTI_MAX:
         raise ValueError(f'gru_seq_multi takes 1 to {GRU_MULTI_MAX} jobs, got {n}')
+    H_true = jobs[0][0].shape[-1] // 3
+    Hk, native = gru_width_plan(H_true)
+    if not native:
+        if any(tuple(j[0].shape) != tuple(jobs[0][0].shape) for j in jobs):
+            raise ValueError('gru_seq_multi: the jobs of one launch share (B, L, H)')
+        wide = []
+        for gi, w_hh, b_hh, h0, need_grad in jobs:
+            with torch.set_grad_enabled(bool(need_grad) and torch.is_grad_enabled()):
+                wide.append(_gru_widen_job(gi, w_hh, b_hh, h0, H_true, Hk) + (need_grad,))
+        return [gru_narrow(y, H_true, Hk) for y in gru_seq_multi(wide)]
     prep = []
     for gi, w_hh, b_hh, h0, need_grad in jobs:
         _need_cuda('gru_seq_multi', gi, w_hh, b_hh, h0)

@@ -24,12 +24,21 @@ class GRU(nn.Module):
     def recurrence_job(self, x, hidden=None):
         """The hoisted input projection and what the recurrence needs besides: (gi, W_hh, b_hh, h0), the arguments of `ops.gru_seq`
         and the head of an `ops.gru_seq_multi` job (RNNBase's lockstep walk runs several networks' recurrences in one launch)."""
-        gi = ops.linear(x, self.weight_ih_l0, self.bias_ih_l0)
+        H = self.hidden_size
+        Hk, native = ops.gru_width_plan(H) if x.is_cuda else (H, True)       # the kernels' widths bind GPU passes only
         h0 = None if hidden is None else hidden[0]
-        return gi, self.weight_hh_l0, self.bias_hh_l0, h0
+        if native:
+            return ops.linear(x, self.weight_ih_l0, self.bias_ih_l0), self.weight_hh_l0, self.bias_hh_l0, h0
+        # a width the kernels have no instantiation for: the job runs at Hk on zero-padded PARAMETERS (one node, one launch each way),
+        # so the projection writes gi [B, T, 3Hk] directly and only `finish` touches an activation.  The parameters themselves - what the
+        # flat store, the optimizer and the checkpoints see - keep nn.GRU's shapes.
+        w_ih, b_ih, w_hh, b_hh = ops.gru_pad_params(self.weight_ih_l0, self.bias_ih_l0, self.weight_hh_l0, self.bias_hh_l0, Hk)
+        return ops.linear(x, w_ih, b_ih), w_hh, b_hh, ops.gru_pad_state(h0, H, Hk)
 
-    @staticmethod
-    def finish(y):
+    def finish(self, y):
+        """y: the recurrence's output for `recurrence_job` - at the kernel width, narrowed here to the true units."""
+        if y.shape[-1] != self.hidden_size:
+            y = ops.gru_narrow(y, self.hidden_size, y.shape[-1])
         return y, y[:, -1:, :].transpose(0, 1)
 
     def forward(self, x, hidden=None):
