@@ -156,6 +156,22 @@ int resel_causal_conv1d_bwd2(const float* x, int64_t ld_x, const float* w, const
                              float* dw, float* dbias, void* workspace, int B, int L, int Di, int K, int silu,
                              void* amax_dx, unsigned amax_epoch, resel_stream_t stream);
 
+/* Member edition for `econv1d[_<K>]-<E>` (reference offpolicy_rnn/models/conv1d/econv1d.py: one nn.Conv1d over E * Di grouped channels,
+ * channel e * Di + d = member e): the same kernels over member-major rows.  y, dy, dx: [E, rows_per_member, L, Di], row e * rpm + b
+ * belongs to member e; x the same or, with x_shared = 1, [rows_per_member, L, Di] read by every member; w [E, Di, K], bias [E, Di] or NULL;
+ * mask [rows_per_member * L], shared by the members, or NULL.  No activation.  E * rows_per_member <= 65535; everything else as above.
+ * Backward: dw [E, Di, K], dbias [E, Di] per member (fixed summation order).  dx_sum (x_shared only, may be NULL): dense
+ * [rows_per_member, L, Di] = sum over the members of dx, member 0 first; it needs dense dx (ld_dx == Di) and rows_per_member * L * Di < 2^31.
+ * amax_dx: max |dx| over the per-member gradients (no bound on dx_sum).  (Added without an ABI bump: no existing signature changed.) */
+int resel_member_conv1d_fwd(const float* x, int64_t ld_x, int x_shared, const float* w, const float* bias, const float* mask,
+                            float* y, int64_t ld_y, int E, int rows_per_member, int L, int Di, int K,
+                            void* amax_y, unsigned amax_epoch, resel_stream_t stream);
+size_t resel_member_conv1d_bwd_workspace_bytes(int E, int rows_per_member, int L, int Di, int K);
+int resel_member_conv1d_bwd(const float* x, int64_t ld_x, int x_shared, const float* w, const float* bias, const float* mask,
+                            const float* dy, int64_t ld_dy, float* dx, int64_t ld_dx, float* dx_sum, float* dw, float* dbias,
+                            void* workspace, int E, int rows_per_member, int L, int Di, int K,
+                            void* amax_dx, unsigned amax_epoch, resel_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused residual add + LayerNorm / RMSNorm.  Replaces the Triton kernels `_layer_norm_fwd_1pass_kernel` /
  * `_layer_norm_bwd_kernel` (offpolicy_rnn/models/smamba/mamba_ssm/ops/triton/layernorm.py:65,196; CPU spec
@@ -197,6 +213,13 @@ int resel_member_layernorm_bwd(const float* dy, int64_t ldg_e, int64_t ldg_m, co
                                const float* w, const float* b, const float* stats, float* dx, int64_t ldd_e, int64_t ldd_m,
                                float* dw, float* db, void* workspace, int M, int E, int C, int act,
                                void* amax_dx, unsigned amax_epoch, resel_stream_t stream);
+/* Residual form: y = act(LN(x + res)), the closing add + joint member LayerNorm of the ensemble feed-forward block of `elru-<E>`
+ * (reference offpolicy_rnn/models/lru/elru.py:226-229) in one pass.  x, res and xsum (out: x + res, what the backward reads as its `x`)
+ * share the stride pair (ldx_e, ldx_m); everything else as resel_member_layernorm_fwd, which this is bit for bit when the sum is formed
+ * beforehand.  Backward: resel_member_layernorm_bwd on xsum - its dx is the gradient of x and of res.  (Added without an ABI bump: no existing signature changed.) */
+int resel_member_add_layernorm_fwd(const float* x, const float* res, float* xsum, int64_t ldx_e, int64_t ldx_m,
+                                   const float* w, const float* b, float* y, int64_t ldy_e, int64_t ldy_m, float* stats,
+                                   int M, int E, int C, float eps, int act, void* amax_y, unsigned amax_epoch, resel_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Linear-recurrence scans (gilr, lru).  Replace the Triton kernels
@@ -227,6 +250,21 @@ int resel_linrec_complex_bwd(const float* vr, const float* vi, int64_t ld_u, con
                              const float* hr, const float* hi, const float* dhr, const float* dhi,
                              float* dvr, float* dvi, int64_t ld_du, float* dlam_re, float* dlam_im, float* dgamma,
                              void* workspace, int B, int L, int C, resel_stream_t stream);
+/* Member edition of the complex scan for `elru-<E>` (reference offpolicy_rnn/models/lru/elru.py:103-188 expands lambda / gamma to
+ * [E * B, L, C] and scans E * B rows): the E * rows_per_member rows are member-major, rows e * rpm .. (e + 1) * rpm - 1 take row e of the
+ * [E, C] tables lam_re / lam_im / gamma; start [rows_per_member * L] is shared by the members, h0r / h0i [E * rpm, C] are per row.
+ * Backward: dlam_re, dlam_im, dgamma [E, C], reduced per member over its rows and L in a fixed order.  E * rows_per_member <= 65535.
+ * E = 1 is resel_linrec_complex_fwd / _bwd bit for bit.  (Added without an ABI bump: no existing signature changed.) */
+int resel_linrec_complex_members_fwd(const float* vr, const float* vi, int64_t ld_u, const float* lam_re, const float* lam_im,
+                                     const float* gamma, const float* start, const float* h0r, const float* h0i,
+                                     float* hr, float* hi, int E, int rows_per_member, int L, int C,
+                                     void* amax_h, unsigned amax_epoch, resel_stream_t stream);
+size_t resel_linrec_complex_members_bwd_workspace_bytes(int E, int rows_per_member, int L, int C);
+int resel_linrec_complex_members_bwd(const float* vr, const float* vi, int64_t ld_u, const float* lam_re, const float* lam_im,
+                                     const float* gamma, const float* start, const float* h0r, const float* h0i,
+                                     const float* hr, const float* hi, const float* dhr, const float* dhi,
+                                     float* dvr, float* dvi, int64_t ld_du, float* dlam_re, float* dlam_im, float* dgamma,
+                                     void* workspace, int E, int rows_per_member, int L, int C, resel_stream_t stream);
 
 /* lru's per-channel parameters in one launch each way (reference offpolicy_rnn/models/lru/lru.py:104-110: exp / cos / sin / mul on [C]
  * tensors).  params_log [3, C] = (nu_log | theta_log | gamma_log) -> out [3, C] = (lam_re | lam_im | gamma) with

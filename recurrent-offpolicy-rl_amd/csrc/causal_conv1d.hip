@@ -20,7 +20,20 @@ struct ConvParams {
     AmaxOut amax;                    // optional: publish max |y| (forward) / max |dx| (backward)
     const float* dy2 = nullptr;      // backward: optional second gradient of the output, summed with dy on load (the Mamba mixer's conv output
     int64_t ld_dy2 = 0;              // receives the scan's du AND the x_proj input gradient: no accumulating GEMM, no add pass)
+    // member edition (econv1d-<E>): the B rows are member-major, rows e rpm .. (e + 1) rpm - 1 belong to member e and take block e of
+    // w [E, Di, K] / bias [E, Di]; mask [rpm, L] is shared by the members; x_shared: x is [rpm, L, Di], read by every member.
+    int rpm = 0x7fffffff;            // rows per member (the default: one member owns every row)
+    int x_shared = 0;
 };
+
+// the parameters as row b's member sees them: its block of w / bias; -> (row of x, row of the mask)
+struct MemberRow { int xb, mb; };
+__device__ __forceinline__ MemberRow member_view(ConvParams& p, int b) {
+    const int e = b / p.rpm, bs = b - e * p.rpm;
+    p.w += (int64_t)e * p.Di * p.K;
+    if (p.bias) p.bias += (int64_t)e * p.Di;
+    return MemberRow{p.x_shared ? bs : b, bs};
+}
 
 template <int KT>
 __device__ __forceinline__ void load_taps(const ConvParams& p, int c, bool ok, float4 (&wr)[KT]) {
@@ -41,7 +54,7 @@ __device__ __forceinline__ void load_taps(const ConvParams& p, int c, bool ok, f
 
 // rows [t0 - (KT-1), t0 + nrows - (KT-1)) of the masked input -> s_x[0..nrows)
 template <int ROWS>
-__device__ __forceinline__ void stage_x(const ConvParams& p, float (*s_x)[TILE_C], int64_t tok0, int t_first, int nrows,
+__device__ __forceinline__ void stage_x(const ConvParams& p, float (*s_x)[TILE_C], int64_t tok0, int64_t mtok0, int t_first, int nrows,
                                         int d0, int tid, int nthreads) {
     const int tc4 = (tid & 15) * 4;
     const bool c_ok = (d0 + tc4) < p.Di;
@@ -51,7 +64,7 @@ __device__ __forceinline__ void stage_x(const ConvParams& p, float (*s_x)[TILE_C
         if (t >= 0 && t < p.L && c_ok) {
             v = ld4(p.x + (tok0 + t) * p.ld_x + d0 + tc4);
             if (p.mask) {
-                const float m = p.mask[tok0 + t];
+                const float m = p.mask[mtok0 + t];
                 v.x *= m; v.y *= m; v.z *= m; v.w *= m;
             }
         }
@@ -104,13 +117,14 @@ __global__ __launch_bounds__(128) void conv_fwd_kernel(ConvParams p) {
     constexpr int P = KT < 16 ? KT : 16;
     const int lane = threadIdx.x & 63;
     if ((blockIdx.x * 128 + (threadIdx.x & 64)) * 2 >= p.Di) return;      // whole wave past the last channel (no barriers below)
+    const MemberRow mr = member_view(p, blockIdx.z);
     // lanes past the last channel of a partly filled wave shadow the last pair (same loads, same stores, same values):
     // every lane stays active, which the v_readlane mask fetches and the exact vmcnt accounting rely on
     const int c = min((int)(blockIdx.x * 128 + threadIdx.x) * 2, p.Di - 2);
     const int b = blockIdx.z, t0 = blockIdx.y * CONV_TT;
     const int t_end = min(p.L, t0 + CONV_TT);
-    const int64_t tok0 = (int64_t)b * p.L;
-    const float* xrow = p.x + tok0 * p.ld_x + c;
+    const int64_t tok0 = (int64_t)b * p.L, xtok0 = (int64_t)mr.xb * p.L, mtok0 = (int64_t)mr.mb * p.L;
+    const float* xrow = p.x + xtok0 * p.ld_x + c;
     float* yrow = p.y + tok0 * p.ld_y + c;
     f2 wr[KT], win[KT];
 #pragma unroll
@@ -128,8 +142,8 @@ __global__ __launch_bounds__(128) void conv_fwd_kernel(ConvParams p) {
     {
         const int ta = ts + lane, tb = ts + 64 + lane;
         const bool oka = ta >= 0 && ta < t_end, okb = tb >= 0 && tb < t_end;
-        const float va = p.mask ? p.mask[tok0 + min(max(ta, 0), t_end - 1)] : 1.f;
-        const float vb = p.mask ? p.mask[tok0 + min(max(tb, 0), t_end - 1)] : 1.f;
+        const float va = p.mask ? p.mask[mtok0 + min(max(ta, 0), t_end - 1)] : 1.f;
+        const float vb = p.mask ? p.mask[mtok0 + min(max(tb, 0), t_end - 1)] : 1.f;
         mlo = oka ? va : 0.f;
         mhi = okb ? vb : 0.f;
     }
@@ -223,10 +237,11 @@ __global__ __launch_bounds__(128) void conv_bwd_win_kernel(ConvParams p, int nch
     const int c_raw = (int)(blockIdx.x * 128 + threadIdx.x) * 2;
     const int c = min(c_raw, p.Di - 2);             // shadow lanes (see the forward kernel)
     const int b = blockIdx.z, chunk = blockIdx.y;
+    const MemberRow mr = member_view(p, b);
     const int t_own0 = chunk * CB_TT;               // first step this chunk accounts for in dw / db
     const int t0 = min(t_own0, p.L - CB_TT);        // the last chunk is shifted back to end at the row end
-    const int64_t tok0 = (int64_t)b * p.L;
-    const float* xrow = p.x + tok0 * p.ld_x + c;
+    const int64_t tok0 = (int64_t)b * p.L, xtok0 = (int64_t)mr.xb * p.L, mtok0 = (int64_t)mr.mb * p.L;
+    const float* xrow = p.x + xtok0 * p.ld_x + c;
     const float* dyrow = p.dy + tok0 * p.ld_dy + c;
     const float* dy2row = TWO ? p.dy2 + tok0 * p.ld_dy2 + c : nullptr;
     float* dxrow = p.dx + tok0 * p.ld_dx + c;
@@ -245,7 +260,7 @@ __global__ __launch_bounds__(128) void conv_bwd_win_kernel(ConvParams p, int nch
 #pragma unroll
     for (int q = 0; q < CB_NM; ++q) {
         const int ta = ts + 64 * q + lane;
-        const float va = p.mask ? p.mask[tok0 + min(max(ta, 0), p.L - 1)] : 1.f;
+        const float va = p.mask ? p.mask[mtok0 + min(max(ta, 0), p.L - 1)] : 1.f;
         mk[q] = (ta >= 0 && ta < p.L) ? va : 0.f;
     }
     f2 prex[P], predy[P], predy2[P];
@@ -285,7 +300,8 @@ __global__ __launch_bounds__(256) void conv_bwd_kernel(ConvParams p) {
     __shared__ __attribute__((aligned(16))) float s_g[TT + KT - 1][TILE_C];         // g rows [t0, t0+TT+KT-1)
     const int tid = threadIdx.x;
     const int b = blockIdx.x, d0 = blockIdx.y * TILE_C;
-    const int64_t tok0 = (int64_t)b * p.L;
+    const MemberRow mr = member_view(p, b);
+    const int64_t tok0 = (int64_t)b * p.L, xtok0 = (int64_t)mr.xb * p.L, mtok0 = (int64_t)mr.mb * p.L;
     const int tc4 = (tid & 15) * 4, tr = tid >> 4;
     const bool c_ok = (d0 + tc4) < p.Di;
     float4 wr[KT], dwr[KT];
@@ -297,7 +313,7 @@ __global__ __launch_bounds__(256) void conv_bwd_kernel(ConvParams p) {
 
     for (int t0 = 0; t0 < p.L; t0 += TT) {
         __syncthreads();
-        stage_x<TT + 2 * (KT - 1)>(p, s_x, tok0, t0 - (KT - 1), TT + 2 * (KT - 1), d0, tid, 256);
+        stage_x<TT + 2 * (KT - 1)>(p, s_x, xtok0, mtok0, t0 - (KT - 1), TT + 2 * (KT - 1), d0, tid, 256);
         __syncthreads();
         // g for rows [t0, t0 + TT + KT - 1); rows >= t0 + TT are halo recomputed for dx only
         for (int r = tr; r < TT + KT - 1; r += 16) {
@@ -342,7 +358,7 @@ __global__ __launch_bounds__(256) void conv_bwd_kernel(ConvParams p) {
                     acc.z = __builtin_fmaf(wr[kk].z, gv.z, acc.z); acc.w = __builtin_fmaf(wr[kk].w, gv.w, acc.w);
                 }
                 if (p.mask) {
-                    const float m = p.mask[tok0 + t];
+                    const float m = p.mask[mtok0 + t];
                     acc.x *= m; acc.y *= m; acc.z *= m; acc.w *= m;
                 }
                 st4(p.dx + (tok0 + t) * p.ld_dx + d0 + tc4, acc);
@@ -378,13 +394,15 @@ inline bool conv_args_ok(const float* x, int64_t ld_x, const float* o, int64_t l
 
 }  // namespace
 
-extern "C" int resel_causal_conv1d_fwd(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
-                                       float* y, int64_t ld_y, int B, int L, int Di, int K, int silu,
-                                       void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
+// B rows in all; E members of B / E rows each (E = 1: the plain form)
+static int conv_fwd_run(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
+                        float* y, int64_t ld_y, int B, int L, int Di, int K, int silu,
+                        void* amax_y, unsigned amax_epoch, resel_stream_t stream, int E, int x_shared) {
     if (amax_y && (reinterpret_cast<uintptr_t>(amax_y) & 7u)) return RESEL_EINVAL;
     if (!conv_args_ok(x, ld_x, y, ld_y, B, L, Di, K) || !w || (bias && !aligned16(bias))) return RESEL_EINVAL;
     ConvParams p{x, w, bias, mask, nullptr, y, nullptr, nullptr, nullptr, ld_x, ld_y, 0, 0, B, L, Di, K, silu,
                  AmaxOut{(unsigned long long*)amax_y, amax_epoch}};
+    if (E > 1 || x_shared) { p.rpm = B / E; p.x_shared = x_shared; }
     const int KT = pad_taps(K);
     dim3 grid((Di + 255) / 256, (L + CONV_TT - 1) / CONV_TT, B);
     hipStream_t s = (hipStream_t)stream;
@@ -395,6 +413,23 @@ extern "C" int resel_causal_conv1d_fwd(const float* x, int64_t ld_x, const float
         default: launch_timed(RESEL_PROF_CONV_FWD, conv_fwd_kernel<32>, grid, dim3(128), 0, s, p); break;
     }
     return launch_status();
+}
+
+extern "C" int resel_causal_conv1d_fwd(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
+                                       float* y, int64_t ld_y, int B, int L, int Di, int K, int silu,
+                                       void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
+    return conv_fwd_run(x, ld_x, w, bias, mask, y, ld_y, B, L, Di, K, silu, amax_y, amax_epoch, stream, 1, 0);
+}
+
+// Member edition (econv1d-<E>): y [E, rpm, L, Di] member-major rows; x the same, or [rpm, L, Di] read by every member (x_shared);
+// w [E, Di, K], bias [E, Di] (16-byte aligned blocks: Di % 4 == 0), mask [rpm * L] shared.  No activation.
+inline bool member_args_ok(int E, int rpm) { return E > 0 && rpm > 0 && (int64_t)E * rpm <= 65535; }
+
+extern "C" int resel_member_conv1d_fwd(const float* x, int64_t ld_x, int x_shared, const float* w, const float* bias, const float* mask,
+                                       float* y, int64_t ld_y, int E, int rows_per_member, int L, int Di, int K,
+                                       void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
+    if (!member_args_ok(E, rows_per_member) || (x_shared != 0 && x_shared != 1)) return RESEL_EINVAL;
+    return conv_fwd_run(x, ld_x, w, bias, mask, y, ld_y, E * rows_per_member, L, Di, K, 0, amax_y, amax_epoch, stream, E, x_shared);
 }
 
 // chunk length of the windowed backward for rows of L steps: the candidate that walks the fewest steps (ties: the shorter); 0: not windowed
@@ -426,10 +461,10 @@ extern "C" int resel_causal_conv1d_bwd(const float* x, int64_t ld_x, const float
                                     amax_epoch, stream);
 }
 
-extern "C" int resel_causal_conv1d_bwd2(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
-                                        const float* dy, int64_t ld_dy, const float* dy2, int64_t ld_dy2, float* dx, int64_t ld_dx,
-                                        float* dw, float* dbias, void* workspace, int B, int L, int Di, int K, int silu,
-                                        void* amax_dx, unsigned amax_epoch, resel_stream_t stream) {
+static int conv_bwd_run(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
+                        const float* dy, int64_t ld_dy, const float* dy2, int64_t ld_dy2, float* dx, int64_t ld_dx,
+                        float* dw, float* dbias, void* workspace, int B, int L, int Di, int K, int silu,
+                        void* amax_dx, unsigned amax_epoch, resel_stream_t stream, int E, int x_shared, float* dx_sum) {
     if (amax_dx && (reinterpret_cast<uintptr_t>(amax_dx) & 7u)) return RESEL_EINVAL;
     if (dy2 && (ld_dy2 % 4 || !aligned16(dy2))) return RESEL_EINVAL;
     if (!conv_args_ok(x, ld_x, dx, ld_dx, B, L, Di, K) || !w || !dy || !dw || !workspace || ld_dy % 4 || !aligned16(dy) ||
@@ -441,6 +476,7 @@ extern "C" int resel_causal_conv1d_bwd2(const float* x, int64_t ld_x, const floa
     float* db_part = dw_part + (size_t)rows * Di * KT;
     ConvParams p{x, w, bias, mask, dy, nullptr, dx, dw_part, db_part, ld_x, 0, ld_dy, ld_dx, B, L, Di, K, silu,
                  AmaxOut{(unsigned long long*)amax_dx, amax_epoch}, dy2, ld_dy2};
+    if (E > 1 || x_shared) { p.rpm = B / E; p.x_shared = x_shared; }
     hipStream_t s = (hipStream_t)stream;
     if (const int tt = bwd_chunk(L, KT)) {
         const int nchunk = (L + tt - 1) / tt;
@@ -464,7 +500,34 @@ extern "C" int resel_causal_conv1d_bwd2(const float* x, int64_t ld_x, const floa
             default: launch_timed(RESEL_PROF_CONV_BWD, conv_bwd_kernel<32>, grid, dim3(256), 0, s, p); break;
         }
     }
-    launch_colsum(dw_part, (int64_t)Di * KT, rows, Di * KT, dw, s, KT, K);   // dw[d, k] = sum_rows dw_part[row, d, KT - K + k]
-    if (dbias) launch_colsum(db_part, Di, rows, Di, dbias, s);
+    // dw[d, k] = sum_rows dw_part[row, d, KT - K + k]; the rows of a member are one slab of rows / E partial rows (E = 1: all of them)
+    launch_colsum(dw_part, (int64_t)Di * KT, rows / E, Di * KT, dw, s, KT, K, E);
+    if (dbias) launch_colsum(db_part, Di, rows / E, Di, dbias, s, 1, 0, E);
+    // shared input: dx_sum [rpm, L, Di] = sum over the members of dx [E, rpm, L, Di], member 0 first (fixed order)
+    if (dx_sum) launch_colsum(dx, (int64_t)(B / E) * L * Di, E, (int)((int64_t)(B / E) * L * Di), dx_sum, s);
     return launch_status();
+}
+
+extern "C" int resel_causal_conv1d_bwd2(const float* x, int64_t ld_x, const float* w, const float* bias, const float* mask,
+                                        const float* dy, int64_t ld_dy, const float* dy2, int64_t ld_dy2, float* dx, int64_t ld_dx,
+                                        float* dw, float* dbias, void* workspace, int B, int L, int Di, int K, int silu,
+                                        void* amax_dx, unsigned amax_epoch, resel_stream_t stream) {
+    return conv_bwd_run(x, ld_x, w, bias, mask, dy, ld_dy, dy2, ld_dy2, dx, ld_dx, dw, dbias, workspace, B, L, Di, K, silu, amax_dx, amax_epoch,
+                        stream, 1, 0, nullptr);
+}
+
+extern "C" size_t resel_member_conv1d_bwd_workspace_bytes(int E, int rows_per_member, int L, int Di, int K) {
+    return resel_causal_conv1d_bwd_workspace_bytes(E * rows_per_member, L, Di, K);
+}
+
+// dx [E, rpm, L, Di] per member (ld_dx); with x_shared also dx_sum [rpm, L, Di] dense = the sum over the members (then dx must be dense,
+// ld_dx == Di, and rpm * L * Di < 2^31).  dw [E, Di, K], dbias [E, Di] (or NULL) per member.
+extern "C" int resel_member_conv1d_bwd(const float* x, int64_t ld_x, int x_shared, const float* w, const float* bias, const float* mask,
+                                       const float* dy, int64_t ld_dy, float* dx, int64_t ld_dx, float* dx_sum, float* dw, float* dbias,
+                                       void* workspace, int E, int rows_per_member, int L, int Di, int K,
+                                       void* amax_dx, unsigned amax_epoch, resel_stream_t stream) {
+    if (!member_args_ok(E, rows_per_member) || (x_shared != 0 && x_shared != 1) || (dx_sum && !x_shared)) return RESEL_EINVAL;
+    if (dx_sum && (ld_dx != Di || (int64_t)rows_per_member * L * Di >= ((int64_t)1 << 31))) return RESEL_EINVAL;
+    return conv_bwd_run(x, ld_x, w, bias, mask, dy, ld_dy, nullptr, 0, dx, ld_dx, dw, dbias, workspace, E * rows_per_member, L, Di, K, 0,
+                        amax_dx, amax_epoch, stream, E, x_shared, dx_sum);
 }

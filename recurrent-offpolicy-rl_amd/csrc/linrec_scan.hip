@@ -166,17 +166,20 @@ __global__ __launch_bounds__(NSEG * 64) void linrec_complex_fwd_kernel(const flo
                                                                        const float* __restrict__ gamma, const float* __restrict__ start,
                                                                        const float* __restrict__ h0r, const float* __restrict__ h0i,
                                                                        float* __restrict__ hr, float* __restrict__ hi, int B, int L, int C,
-                                                                       int64_t ld_u, AmaxOut amax_h) {
+                                                                       int64_t ld_u, AmaxOut amax_h, int rpm) {
     constexpr int NST = NSEG * 64 / CL;
     __shared__ float s_ar[NST][CL], s_ai[NST][CL], s_cr[NST][CL], s_ci[NST][CL];
     extern __shared__ float s_keep[];
     const int lane = threadIdx.x & (CL - 1), w = (threadIdx.x >> 6) * (64 / CL) + ((threadIdx.x & 63) / CL);   // channel, time segment
     const int b = blockIdx.y, c = blockIdx.x * CL + lane;
-    stage_keep(s_keep, start, b, L);
+    // member edition: rows e rpm .. (e + 1) rpm - 1 take row e of the [E, C] tables and share the rpm rows of `start` (rpm = B: one member)
+    const int e = b / rpm;
+    stage_keep(s_keep, start, b - e * rpm, L);
     const bool ok = c < C;
     const int64_t base = (int64_t)b * L * C + c, ubase = (int64_t)b * L * ld_u + c;
     const Seg sg = segment<NST>(w, L);
-    const float lr = ok ? lam_re[c] : 0.f, li = ok ? lam_im[c] : 0.f, gm = (ok && gamma) ? gamma[c] : 1.f;
+    const int pc = e * C + c;
+    const float lr = ok ? lam_re[pc] : 0.f, li = ok ? lam_im[pc] : 0.f, gm = (ok && gamma) ? gamma[pc] : 1.f;
     float ar = 1.f, ai = 0.f, cr = 0.f, ci = 0.f;
     if (ok) {
 #pragma unroll 8
@@ -225,17 +228,20 @@ __global__ __launch_bounds__(NSEG * 64) void linrec_complex_bwd_kernel(const flo
                                                                        const float* __restrict__ hr, const float* __restrict__ hi,
                                                                        const float* __restrict__ dhr, const float* __restrict__ dhi,
                                                                        float* __restrict__ dvr, float* __restrict__ dvi,
-                                                                       float* __restrict__ part, int B, int L, int C, int64_t ld_u, int64_t ld_du) {
+                                                                       float* __restrict__ part, int B, int L, int C, int64_t ld_u, int64_t ld_du,
+                                                                       int rpm) {
     constexpr int NST = NSEG * 64 / CL;
     __shared__ float s_ar[NST][CL], s_ai[NST][CL], s_cr[NST][CL], s_ci[NST][CL];
     extern __shared__ float s_keep[];
     const int lane = threadIdx.x & (CL - 1), w = (threadIdx.x >> 6) * (64 / CL) + ((threadIdx.x & 63) / CL);   // channel, time segment
     const int b = blockIdx.y, c = blockIdx.x * CL + lane;
-    stage_keep(s_keep, start, b, L);
+    const int e = b / rpm;                                             // member of this row (see the forward)
+    stage_keep(s_keep, start, b - e * rpm, L);
     const bool ok = c < C;
     const int64_t base = (int64_t)b * L * C + c, ubase = (int64_t)b * L * ld_u + c, dbase = (int64_t)b * L * ld_du + c;
     const Seg sg = segment<NST>(w, L);
-    const float lr = ok ? lam_re[c] : 0.f, li = ok ? lam_im[c] : 0.f, gm = (ok && gamma) ? gamma[c] : 1.f;
+    const int pc = e * C + c;
+    const float lr = ok ? lam_re[pc] : 0.f, li = ok ? lam_im[pc] : 0.f, gm = (ok && gamma) ? gamma[pc] : 1.f;
     auto keep_at = [&](int t) -> float { return s_keep[t]; };          // sentinel slot L holds 0
     float ar = 1.f, ai = 0.f, gr = 0.f, gi = 0.f;
     if (ok && sg.t1 > sg.t0) {
@@ -359,7 +365,7 @@ extern "C" int resel_linrec_complex_fwd(const float* vr, const float* vi, int64_
     const int cl = pick_cl(B, C);
     const AmaxOut ao{(unsigned long long*)amax_h, amax_epoch};
     LINREC_DISPATCH(cl, (launch_timed(RESEL_PROF_LINREC_COMPLEX_FWD, linrec_complex_fwd_kernel<CL>, dim3((C + cl - 1) / cl, B), dim3(NSEG * 64),
-                                      (size_t)(L + 1) * sizeof(float), (hipStream_t)stream, vr, vi, lam_re, lam_im, gamma, start, h0r, h0i, hr, hi, B, L, C, ld_u, ao)));
+                                      (size_t)(L + 1) * sizeof(float), (hipStream_t)stream, vr, vi, lam_re, lam_im, gamma, start, h0r, h0i, hr, hi, B, L, C, ld_u, ao, B)));
     return launch_status();
 }
 
@@ -380,12 +386,57 @@ extern "C" int resel_linrec_complex_bwd(const float* vr, const float* vi, int64_
     const int cl = pick_cl(B, C), nst = NSEG * 64 / cl;
     LINREC_DISPATCH(cl, (launch_timed(RESEL_PROF_LINREC_COMPLEX_BWD, linrec_complex_bwd_kernel<CL>, dim3((C + cl - 1) / cl, B), dim3(NSEG * 64),
                                       (size_t)(L + 1) * sizeof(float), s, vr, vi, lam_re, lam_im, gamma, start, h0r, h0i, hr, hi, dhr, dhi, dvr, dvi,
-                                      (float*)workspace, B, L, C, ld_u, ld_du)));
+                                      (float*)workspace, B, L, C, ld_u, ld_du, B)));
     // per-(row, segment) partials [B * nst][3][C] -> d lambda_re, d lambda_im, d gamma (fixed summation order)
     const float* part = (const float*)workspace;
     launch_colsum(part, 3 * (int64_t)C, B * nst, C, dlam_re, s);
     launch_colsum(part + C, 3 * (int64_t)C, B * nst, C, dlam_im, s);
     if (dgamma) launch_colsum(part + 2 * (int64_t)C, 3 * (int64_t)C, B * nst, C, dgamma, s);
+    return launch_status();
+}
+
+// Member edition (elru-<E>): the E * rows_per_member scanned rows are member-major, rows e rpm .. (e + 1) rpm - 1 belong to member e and take
+// row e of the [E, C] tables lam_re / lam_im / gamma; start [rows_per_member * L] is shared by the members; h0r / h0i are per row.  The
+// backward leaves dlam_re / dlam_im / dgamma per member, [E, C]: member e's partial rows form one slab, summed in a fixed order.
+extern "C" int resel_linrec_complex_members_fwd(const float* vr, const float* vi, int64_t ld_u, const float* lam_re, const float* lam_im,
+                                                const float* gamma, const float* start, const float* h0r, const float* h0i,
+                                                float* hr, float* hi, int E, int rows_per_member, int L, int C,
+                                                void* amax_h, unsigned amax_epoch, resel_stream_t stream) {
+    if (!vr || !vi || !lam_re || !lam_im || !hr || !hi || E <= 0 || rows_per_member <= 0 || L <= 0 || C <= 0 || ld_u < C || !amax_arg_ok(amax_h) ||
+        (int64_t)E * rows_per_member > 65535 || (int64_t)E * C >= ((int64_t)1 << 31))
+        return RESEL_EINVAL;
+    const int B = E * rows_per_member, cl = pick_cl(B, C);
+    const AmaxOut ao{(unsigned long long*)amax_h, amax_epoch};
+    LINREC_DISPATCH(cl, (launch_timed(RESEL_PROF_LINREC_COMPLEX_FWD, linrec_complex_fwd_kernel<CL>, dim3((C + cl - 1) / cl, B), dim3(NSEG * 64),
+                                      (size_t)(L + 1) * sizeof(float), (hipStream_t)stream, vr, vi, lam_re, lam_im, gamma, start, h0r, h0i, hr, hi, B, L, C, ld_u, ao,
+                                      rows_per_member)));
+    return launch_status();
+}
+
+extern "C" size_t resel_linrec_complex_members_bwd_workspace_bytes(int E, int rows_per_member, int L, int C) {
+    return resel_linrec_complex_bwd_workspace_bytes(E * rows_per_member, L, C);
+}
+
+extern "C" int resel_linrec_complex_members_bwd(const float* vr, const float* vi, int64_t ld_u, const float* lam_re, const float* lam_im,
+                                                const float* gamma, const float* start, const float* h0r, const float* h0i,
+                                                const float* hr, const float* hi, const float* dhr, const float* dhi,
+                                                float* dvr, float* dvi, int64_t ld_du, float* dlam_re, float* dlam_im, float* dgamma,
+                                                void* workspace, int E, int rows_per_member, int L, int C, resel_stream_t stream) {
+    if (!vr || !vi || !lam_re || !lam_im || !hr || !hi || !dhr || !dhi || !dvr || !dvi || !dlam_re || !dlam_im || !workspace ||
+        E <= 0 || rows_per_member <= 0 || L <= 0 || C <= 0 || ld_u < C || ld_du < C || (int64_t)E * rows_per_member > 65535 ||
+        (int64_t)E * C >= ((int64_t)1 << 31))
+        return RESEL_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = E * rows_per_member, cl = pick_cl(B, C), nst = NSEG * 64 / cl;
+    LINREC_DISPATCH(cl, (launch_timed(RESEL_PROF_LINREC_COMPLEX_BWD, linrec_complex_bwd_kernel<CL>, dim3((C + cl - 1) / cl, B), dim3(NSEG * 64),
+                                      (size_t)(L + 1) * sizeof(float), s, vr, vi, lam_re, lam_im, gamma, start, h0r, h0i, hr, hi, dhr, dhi, dvr, dvi,
+                                      (float*)workspace, B, L, C, ld_u, ld_du, rows_per_member)));
+    // partials [E][rows_per_member * nst][3][C]: one slab per member -> [E, C] each (colsum's batched form, fixed summation order)
+    const float* part = (const float*)workspace;
+    const int K = rows_per_member * nst;
+    launch_colsum(part, 3 * (int64_t)C, K, C, dlam_re, s, 1, 0, E);
+    launch_colsum(part + C, 3 * (int64_t)C, K, C, dlam_im, s, 1, 0, E);
+    if (dgamma) launch_colsum(part + 2 * (int64_t)C, 3 * (int64_t)C, K, C, dgamma, s, 1, 0, E);
     return launch_status();
 }
 

@@ -34,7 +34,8 @@ template <int VPL>                  // float4 per lane: E * C <= VPL * 256; one 
 __global__ __launch_bounds__(WAVES * 64) void mln_fwd_kernel(const float* __restrict__ x, int64_t ldx_e, int64_t ldx_m,
                                                              const float* __restrict__ w, const float* __restrict__ b,
                                                              float* __restrict__ y, int64_t ldy_e, int64_t ldy_m,
-                                                             float* __restrict__ stats, int M, int E, int C, float eps, int act, AmaxOut amax) {
+                                                             float* __restrict__ stats, int M, int E, int C, float eps, int act, AmaxOut amax,
+                                                             const float* __restrict__ res, float* __restrict__ xsum) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -42,7 +43,10 @@ __global__ __launch_bounds__(WAVES * 64) void mln_fwd_kernel(const float* __rest
     const float inv_n = 1.f / (float)(E * C);
     const float* xr = x + (int64_t)row * ldx_m;
     float* yr = y + (int64_t)row * ldy_m;
-    const float x0 = xr[0];                             // wave-uniform: the shift of the mean
+    // residual form (res != nullptr): the token normalised is x + res, both in x's layout; the sum is left in xsum (same layout) for the backward
+    const float* rr = res ? res + (int64_t)row * ldx_m : nullptr;
+    float* sr = res ? xsum + (int64_t)row * ldx_m : nullptr;
+    const float x0 = rr ? xr[0] + rr[0] : xr[0];        // wave-uniform: the shift of the mean
     float4 v[VPL];
     float s = 0.f;
 #pragma unroll
@@ -50,7 +54,12 @@ __global__ __launch_bounds__(WAVES * 64) void mln_fwd_kernel(const float* __rest
         const int j = i * 64 + lane;
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (j < n4) {
-            const float4 t = ld4(xr + seg_off(j, c4, ldx_e));
+            float4 t = ld4(xr + seg_off(j, c4, ldx_e));
+            if (rr) {
+                const float4 r = ld4(rr + seg_off(j, c4, ldx_e));
+                t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w;
+                st4(sr + seg_off(j, c4, ldx_e), t);
+            }
             v[i] = make_float4(t.x - x0, t.y - x0, t.z - x0, t.w - x0);
         }
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -186,7 +195,8 @@ template <int VW>                   // float4 per thread: E * C <= VW * 1024; on
 __global__ __launch_bounds__(WAVES * 64) void mln_fwd_wide_kernel(const float* __restrict__ x, int64_t ldx_e, int64_t ldx_m,
                                                                   const float* __restrict__ w, const float* __restrict__ b,
                                                                   float* __restrict__ y, int64_t ldy_e, int64_t ldy_m,
-                                                                  float* __restrict__ stats, int M, int E, int C, float eps, int act, AmaxOut amax) {
+                                                                  float* __restrict__ stats, int M, int E, int C, float eps, int act, AmaxOut amax,
+                                                                  const float* __restrict__ res, float* __restrict__ xsum) {
     __shared__ float s_red[4][WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int row = blockIdx.x;                         // grid = M
@@ -194,7 +204,9 @@ __global__ __launch_bounds__(WAVES * 64) void mln_fwd_wide_kernel(const float* _
     const float inv_n = 1.f / (float)(E * C);
     const float* xr = x + (int64_t)row * ldx_m;
     float* yr = y + (int64_t)row * ldy_m;
-    const float x0 = xr[0];
+    const float* rr = res ? res + (int64_t)row * ldx_m : nullptr;      // residual form, see mln_fwd_kernel
+    float* sr = res ? xsum + (int64_t)row * ldx_m : nullptr;
+    const float x0 = rr ? xr[0] + rr[0] : xr[0];
     float4 v[VW];
     float s = 0.f;
 #pragma unroll
@@ -202,7 +214,12 @@ __global__ __launch_bounds__(WAVES * 64) void mln_fwd_wide_kernel(const float* _
         const int j = i * (WAVES * 64) + tid;
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (j < n4) {
-            const float4 t = ld4(xr + seg_off(j, c4, ldx_e));
+            float4 t = ld4(xr + seg_off(j, c4, ldx_e));
+            if (rr) {
+                const float4 r = ld4(rr + seg_off(j, c4, ldx_e));
+                t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w;
+                st4(sr + seg_off(j, c4, ldx_e), t);
+            }
             v[i] = make_float4(t.x - x0, t.y - x0, t.z - x0, t.w - x0);
         }
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -347,9 +364,9 @@ inline bool ld_ok(int64_t ld_e, int64_t ld_m, int E, int M) {
 
 }  // namespace
 
-extern "C" int resel_member_layernorm_fwd(const float* x, int64_t ldx_e, int64_t ldx_m, const float* w, const float* b,
-                                          float* y, int64_t ldy_e, int64_t ldy_m, float* stats, int M, int E, int C, float eps, int act,
-                                          void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
+static int mln_fwd_run(const float* x, const float* res, float* xsum, int64_t ldx_e, int64_t ldx_m, const float* w, const float* b,
+                       float* y, int64_t ldy_e, int64_t ldy_m, float* stats, int M, int E, int C, float eps, int act,
+                       void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
     if (!x || !w || !y || !stats || !shape_ok(M, E, C) || (act != 0 && act != 1) || (reinterpret_cast<uintptr_t>(amax_y) & 7u)) return RESEL_EINVAL;
     if (!ld_ok(ldx_e, ldx_m, E, M) || !ld_ok(ldy_e, ldy_m, E, M)) return RESEL_EINVAL;
     if (!aligned16(x) || !aligned16(y) || !aligned16(w) || (b && !aligned16(b))) return RESEL_EINVAL;
@@ -357,13 +374,30 @@ extern "C" int resel_member_layernorm_fwd(const float* x, int64_t ldx_e, int64_t
     hipStream_t s = (hipStream_t)stream;
     const int N = E * C;
     dim3 grid(wide(E, C) ? M : (M + WAVES - 1) / WAVES), blk(WAVES * 64);
-#define MLN_FWD(K) hipLaunchKernelGGL(K, grid, blk, 0, s, x, ldx_e, ldx_m, w, b, y, ldy_e, ldy_m, stats, M, E, C, eps, act, ao)
+#define MLN_FWD(K) hipLaunchKernelGGL(K, grid, blk, 0, s, x, ldx_e, ldx_m, w, b, y, ldy_e, ldy_m, stats, M, E, C, eps, act, ao, res, xsum)
     if (N <= 256) MLN_FWD(mln_fwd_kernel<1>);
     else if (N <= WAVE_ROW) MLN_FWD(mln_fwd_kernel<2>);
     else if (N <= 1024) MLN_FWD(mln_fwd_wide_kernel<1>);
     else MLN_FWD(mln_fwd_wide_kernel<2>);
 #undef MLN_FWD
     return launch_status();
+}
+
+extern "C" int resel_member_layernorm_fwd(const float* x, int64_t ldx_e, int64_t ldx_m, const float* w, const float* b,
+                                          float* y, int64_t ldy_e, int64_t ldy_m, float* stats, int M, int E, int C, float eps, int act,
+                                          void* amax_y, unsigned amax_epoch, resel_stream_t stream) {
+    return mln_fwd_run(x, nullptr, nullptr, ldx_e, ldx_m, w, b, y, ldy_e, ldy_m, stats, M, E, C, eps, act, amax_y, amax_epoch, stream);
+}
+
+// y = act(LN_[E, C](x + res)), xsum = x + res: the closing residual add + joint member LayerNorm of the ensemble feed-forward block
+// (elru-<E>) in one pass.  x, res, xsum share one stride pair.  The backward is resel_member_layernorm_bwd on xsum: its dx is the
+// gradient of both addends.
+extern "C" int resel_member_add_layernorm_fwd(const float* x, const float* res, float* xsum, int64_t ldx_e, int64_t ldx_m,
+                                              const float* w, const float* b, float* y, int64_t ldy_e, int64_t ldy_m, float* stats,
+                                              int M, int E, int C, float eps, int act, void* amax_y, unsigned amax_epoch,
+                                              resel_stream_t stream) {
+    if (!res || !xsum || !aligned16(res) || !aligned16(xsum)) return RESEL_EINVAL;
+    return mln_fwd_run(x, res, xsum, ldx_e, ldx_m, w, b, y, ldy_e, ldy_m, stats, M, E, C, eps, act, amax_y, amax_epoch, stream);
 }
 
 extern "C" size_t resel_member_layernorm_bwd_workspace_bytes(int M, int E, int C) {

@@ -89,14 +89,14 @@ inline int row_lanes(int A) {
 // Column sums of row-major partial slabs in a fixed order (bitwise reproducible): out[o(c)] = sum_{k<K} part[k * ld + c],
 // c < C.  With taps == 0 the output index is c; otherwise the columns are [ch][padded taps KT] and only the last `taps`
 // of every KT go out, as out[ch * taps + tap].  256 threads = 16 columns x 16 row groups; grid = ceil(C / 16) blocks.
-// blockIdx.y = batch: slab b starts at part + b * K * ld, its sums go to out + b * C (batched form: taps == 0 only).
+// blockIdx.y = batch: slab b starts at part + b * K * ld, its sums go to out + b * C (with taps: out + b * (C / KT) * taps).
 static __global__ void colsum_kernel(const float* __restrict__ part, int64_t ld, int K, int C, float* __restrict__ out,
                                      int KT, int taps) {
     __shared__ float s_acc[16][17];
     const int cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + cl;
     part += (int64_t)blockIdx.y * K * ld;
-    out += (int64_t)blockIdx.y * C;
+    out += (int64_t)blockIdx.y * (taps == 0 ? C : (C / KT) * taps);
     float acc = 0.f;
     if (c < C) {                                   // four loads in flight per thread, fixed summation order
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;

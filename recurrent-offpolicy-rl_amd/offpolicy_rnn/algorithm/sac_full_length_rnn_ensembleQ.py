@@ -290,8 +290,10 @@ class SACFullLengthRNNEnsembleQ(SAC):
         `index` (`_target_subset`) names the drawn ones."""
         tv = self.target_values[0]
         subset, index = self._target_subset(tv.uni_network.layer_list[-1].num_ensemble)
-        # (an `eln-E` norm couples the members: every one of them is evaluated, the drawn ones are picked from q as in the reference)
-        if subset.size < tv.uni_network.layer_list[-1].num_ensemble and not tv.uni_network.members_coupled():
+        # (an `eln-E` norm or an ensemble sequence layer, in the head or in the context encoder, couples the members: every one of them is
+        # evaluated, the drawn ones are picked from q as in the reference)
+        coupled = tv.uni_network.members_coupled() or tv.embedding_network.emits_member_axis()
+        if subset.size < tv.uni_network.layer_list[-1].num_ensemble and not coupled:
             with _ensemble_subset(tv, index(as_long=True)):
                 return tv.forward(b['next_state'], b['state'], action, sample, hidden, b['reward'])[0], None
         return tv.forward(b['next_state'], b['state'], action, sample, hidden, b['reward'])[0], index

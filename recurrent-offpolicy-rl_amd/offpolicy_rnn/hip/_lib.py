@@ -82,16 +82,23 @@ SIGNATURES = {
     'resel_causal_conv1d_bwd_workspace_bytes': (c_size_t, [I, I, I, I]),
     'resel_causal_conv1d_bwd': (c_int, [P, L, P, P, P, P, L, P, L, P, P, P, I, I, I, I, I, P, E, S]),
     'resel_causal_conv1d_bwd2': (c_int, [P, L, P, P, P, P, L, P, L, P, L, P, P, P, I, I, I, I, I, P, E, S]),
+    'resel_member_conv1d_fwd': (c_int, [P, L, I, P, P, P, P, L, I, I, I, I, I, P, E, S]),
+    'resel_member_conv1d_bwd_workspace_bytes': (c_size_t, [I, I, I, I, I]),
+    'resel_member_conv1d_bwd': (c_int, [P, L, I, P, P, P, P, L, P, L, P, P, P, P, I, I, I, I, I, P, E, S]),
     'resel_add_layernorm_fwd': (c_int, [P, P, P, P, P, P, P, I, I, F, I, I, P, E, S]),
     'resel_add_layernorm_bwd_workspace_bytes': (c_size_t, [I, I]),
     'resel_add_layernorm_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, E, S]),
     'resel_member_layernorm_fwd': (c_int, [P, L, L, P, P, P, L, L, P, I, I, I, F, I, P, E, S]),
     'resel_member_layernorm_bwd_workspace_bytes': (c_size_t, [I, I, I]),
     'resel_member_layernorm_bwd': (c_int, [P, L, L, P, L, L, P, P, P, P, L, L, P, P, P, I, I, I, I, P, E, S]),
+    'resel_member_add_layernorm_fwd': (c_int, [P, P, P, L, L, P, P, P, L, L, P, I, I, I, F, I, P, E, S]),
     'resel_linrec_real_fwd': (c_int, [P, P, L, P, P, P, I, I, I, I, P, E, S]),
     'resel_linrec_real_bwd': (c_int, [P, P, L, P, P, P, P, P, P, L, I, I, I, I, P, E, S]),
     'resel_linrec_complex_fwd': (c_int, [P, P, L, P, P, P, P, P, P, P, P, I, I, I, P, E, S]),
     'resel_linrec_complex_bwd_workspace_bytes': (c_size_t, [I, I, I]),
+    'resel_linrec_complex_members_fwd': (c_int, [P, P, L, P, P, P, P, P, P, P, P, I, I, I, I, P, E, S]),
+    'resel_linrec_complex_members_bwd_workspace_bytes': (c_size_t, [I, I, I, I]),
+    'resel_linrec_complex_members_bwd': (c_int, [P, P, L, P, P, P, P, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, S]),
     'resel_place_blocks': (c_int, [P, L, I, I, I, P, P, P, P, P, P, S]),
     'resel_lru_params_fwd': (c_int, [P, P, I, S]),
     'resel_lru_params_bwd': (c_int, [P, P, P, I, S]),

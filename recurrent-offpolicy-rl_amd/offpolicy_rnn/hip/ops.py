@@ -482,6 +482,66 @@ def causal_conv1d_fn(x, weight, bias=None, mask=None, activation=True):
     return CausalConv1dFn.apply(x, weight, bias, mask, activation)
 
 
+# ---------------------------------------------------------------------------------------------- ensemble sequence layers: the switch
+MEMBER_SEQ_DEFAULT = '1'        # what an unset RESEL_MEMBER_SEQ means (README; measured in profiles/r35_ensemble_encoders.md)
+
+
+def member_seq_on() -> bool:
+    """RESEL_MEMBER_SEQ, read per call.  1: the `elru-<E>` / `econv1d[_<K>]-<E>` layers run the member editions of the scan, the causal
+    convolution and the add + LayerNorm (one launch over all members); 0: E launches of the single-member entries on each member's rows
+    plus the separate add.  Anything else is an error."""
+    v = os.environ.get('RESEL_MEMBER_SEQ', MEMBER_SEQ_DEFAULT)
+    if v not in ('0', '1'):
+        raise ValueError(f'RESEL_MEMBER_SEQ={v!r}: expected 0 or 1')
+    return v == '1'
+
+
+class MemberConv1dFn(torch.autograd.Function):
+    """Depthwise causal convolution of E members in one launch each way (include/resel_hip.h `resel_member_conv1d_*`): x [E, B, L, D]
+    member-major, or [B, L, D] read by every member (its gradient is then the sum over the members, formed in a fixed order); weight
+    [E, D, K], bias [E, D] or None, mask [B, L(, 1)] shared -> y [E, B, L, D].  No activation."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mask):
+        _need_cuda('member_conv1d', x, weight)
+        E, D, K = weight.shape
+        shared = x.dim() == 3
+        assert x.shape[-1] == D and (shared or (x.dim() == 4 and x.shape[0] == E)), (tuple(x.shape), tuple(weight.shape))
+        Bsz, L = x.shape[-3], x.shape[-2]
+        x3 = _tok_major(x if shared else x.reshape(E * Bsz, L, D))
+        w = weight.float().contiguous()
+        bias = None if bias is None else _aligned_param(bias)
+        mask = _flags(mask, Bsz, L)
+        y = torch.empty(E, Bsz, L, D, dtype=torch.float32, device=x.device)
+        slot, slot_p, epoch = _slot_args(amax_tracking() and y.numel() >= (1 << 20), x.device)
+        check(lib().resel_member_conv1d_fwd(_p(x3), x3.stride(-2), int(shared), _p(w), _p(bias), _p(mask), _p(y), D, E, Bsz, L, D, K,
+                                            slot_p, epoch, _stream()), 'member_conv1d_fwd')
+        publish_amax(slot)
+        ctx.save_for_backward(x3, w, bias, mask)
+        ctx.cfg = (E, Bsz, L, D, K, shared, tuple(x.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x3, w, bias, mask = ctx.saved_tensors
+        E, Bsz, L, D, K, shared, xshape = ctx.cfg
+        dy = _tok_major(dy.reshape(E * Bsz, L, D))
+        dx = torch.empty(E, Bsz, L, D, dtype=torch.float32, device=dy.device)
+        dx_sum = torch.empty(Bsz, L, D, dtype=torch.float32, device=dy.device) if shared else None
+        dw = torch.empty(E, D, K, dtype=torch.float32, device=dy.device)
+        db = torch.empty(E, D, dtype=torch.float32, device=dy.device) if bias is not None else None
+        ws = _ws(lib().resel_member_conv1d_bwd_workspace_bytes(E, Bsz, L, D, K), dy.device)
+        slot, slot_p, epoch = _slot_args(not shared and amax_tracking() and dx.numel() >= (1 << 20), dy.device)
+        check(lib().resel_member_conv1d_bwd(_p(x3), x3.stride(-2), int(shared), _p(w), _p(bias), _p(mask), _p(dy), dy.stride(-2), _p(dx), D,
+                                            _p(dx_sum), _p(dw), _p(db), _p(ws), E, Bsz, L, D, K, slot_p, epoch, _stream()), 'member_conv1d_bwd')
+        return (dx_sum if shared else tag_amax(dx.view(xshape), slot)), dw, db, None
+
+
+def member_conv1d(x, weight, bias=None, mask=None):
+    """The `econv1d[_<K>]-<E>` convolution: see `MemberConv1dFn`."""
+    return apply_tagged(MemberConv1dFn.apply, False, x, weight, bias, mask)
+
+
 # ---------------------------------------------------------------------------------------------- add + norm
 class AddNormFn(torch.autograd.Function):
     @staticmethod
@@ -642,6 +702,42 @@ def member_layer_norm(x, weight, bias, eps=1e-5, act=None):
     the reference spells `LayerNorm([E, C])(x.transpose(-2, 0)).transpose(-2, 0)` - or [..., C] with weight / bias [C].  The output
     carries the magnitude bound the kernel published, for the GEMM behind it."""
     return apply_tagged(MemberLayerNormFn.apply, True, x, weight, bias, eps, act)
+
+
+class MemberAddLayerNormFn(torch.autograd.Function):
+    """y = act(LN_[E, C](a + r)) for member-major a, r [E, ..., C]: the closing residual add + joint member LayerNorm of the ensemble
+    feed-forward block in one pass (`resel_member_add_layernorm_fwd`); the backward is `resel_member_layernorm_bwd` on the saved sum,
+    whose dx is the gradient of both addends."""
+
+    @staticmethod
+    def forward(ctx, a, r, weight, bias, eps, act):
+        _need_cuda('member_add_layer_norm', a, r, weight, bias)
+        assert act in (None, 'elu') and a.shape == r.shape and weight.dim() == 2
+        E, C = weight.shape
+        assert a.shape[0] == E and a.shape[-1] == C, (tuple(a.shape), tuple(weight.shape))
+        a3, r3 = a.float().contiguous().view(E, -1, C), r.float().contiguous().view(E, -1, C)      # dense member-major: one stride pair
+        M = a3.shape[1]
+        w = _aligned_param(weight)
+        b = None if bias is None else _aligned_param(bias)
+        xsum, y3 = torch.empty_like(a3), torch.empty_like(a3)
+        stats = torch.empty(M, 2, dtype=torch.float32, device=a.device)
+        slot, slot_p, epoch = _slot_args(amax_tracking() and M * E * C >= (1 << 20), a.device)
+        check(lib().resel_member_add_layernorm_fwd(_p(a3), _p(r3), _p(xsum), M * C, C, _p(w), _p(b), _p(y3), M * C, C, _p(stats), M, E, C,
+                                                   float(eps), int(act == 'elu'), slot_p, epoch, _stream()), 'member_add_layernorm_fwd')
+        publish_amax(slot)
+        ctx.save_for_backward(xsum, w, b, stats)
+        ctx.cfg = (E, C, int(act == 'elu'), a.shape, weight.shape)
+        return y3.view(a.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dw, db, _, _ = MemberLayerNormFn.backward(ctx, dy)
+        return dx, dx, dw, db, None, None
+
+
+def member_add_layer_norm(a, r, weight, bias, eps=1e-5, act=None):
+    """`member_layer_norm(a + r, ...)` with the add inside the norm's pass; shapes outside `member_layer_norm_ok` are the caller's to route."""
+    return apply_tagged(MemberAddLayerNormFn.apply, True, a, r, weight, bias, eps, act)
 
 
 # ---------------------------------------------------------------------------------------------- linear recurrences
@@ -806,7 +902,8 @@ class LruScanFn(torch.autograd.Function):
 
 
 class LruParamsFn(torch.autograd.Function):
-    """params_log [3, C] = (nu_log | theta_log | gamma_log) -> lam3 [3, C] = (lam_re | lam_im | gamma), lambda = exp(-exp(nu_log)) e^{i exp(theta_log)},
+    """params_log [3, C] (or [3, E, C]: the kernels are element-wise over the rows' E C entries) = (nu_log | theta_log | gamma_log) -> lam3 of the
+    same shape = (lam_re | lam_im | gamma), lambda = exp(-exp(nu_log)) e^{i exp(theta_log)},
     gamma = exp(gamma_log) (reference lru.py:104-110): one launch each way instead of ~25 element-wise launches on [C] tensors per layer call."""
 
     @staticmethod
@@ -814,7 +911,7 @@ class LruParamsFn(torch.autograd.Function):
         _need_cuda('lru_params', params_log)
         p = params_log.float().contiguous()
         out = torch.empty_like(p)
-        check(lib().resel_lru_params_fwd(_p(p), _p(out), p.shape[1], _stream()), 'lru_params_fwd')
+        check(lib().resel_lru_params_fwd(_p(p), _p(out), p.numel() // 3, _stream()), 'lru_params_fwd')
         ctx.save_for_backward(p)
         return out
 
@@ -823,7 +920,7 @@ class LruParamsFn(torch.autograd.Function):
         (p,) = ctx.saved_tensors
         dout = dout.float().contiguous()
         dp = torch.empty_like(p)
-        check(lib().resel_lru_params_bwd(_p(p), _p(dout), _p(dp), p.shape[1], _stream()), 'lru_params_bwd')
+        check(lib().resel_lru_params_bwd(_p(p), _p(dout), _p(dp), p.numel() // 3, _stream()), 'lru_params_bwd')
         return dp
 
 
@@ -877,6 +974,56 @@ def complex_scan_members(u, lam3, start=None, h0r=None, h0i=None):
     """`complex_scan(u[0], u[1], lam3[0], lam3[1], lam3[2], ...)` for u [2 or 3, B, T, C] read in place and lam3 = `lru_params(params_log)`
     -> (h2 [2, B, T, C] = (Re h | Im h), u[2] or None); see `LruMembersFn`."""
     return apply_tagged(LruMembersFn.apply, False, u, lam3, start, h0r, h0i)
+
+
+class LruEnsembleFn(torch.autograd.Function):
+    """The lru recurrence of E members in one launch each way (`resel_linrec_complex_members_*`): u [3, E, B, T, C] (Re / Im of the
+    input, skip term; reference elru.py:81-90), lam3 [3, E, C] = `lru_params` of the [3, E, C] parameters, start [B, T(, 1)] shared by the
+    members, h0r / h0i [E, B, C] -> (h2 [2, E, B, T, C] = (Re h | Im h) stacked, what `middle_proj` multiplies; u[2] passed through so
+    that all of u's gradient comes back as one tensor).  The gradient of lam3 is [3, E, C], reduced per member."""
+
+    @staticmethod
+    def forward(ctx, u, lam3, start, h0r, h0i):
+        _need_cuda('linrec_complex_members', u, lam3)
+        assert u.dim() == 5 and u.shape[0] == 3 and lam3.shape == (3, u.shape[1], u.shape[4]), (tuple(u.shape), tuple(lam3.shape))
+        _, E, Bsz, L, C = u.shape
+        if not (u.dtype == torch.float32 and u.stride(4) == 1 and u.stride(2) == L * u.stride(3) and u.stride(1) == Bsz * u.stride(2)
+                and u.stride(3) >= C):
+            u = u.float().contiguous()
+        ld = u.stride(3)
+        lam3 = lam3.float().contiguous()
+        start = _flags(start, Bsz, L)
+        h0r, h0i = _h0(h0r, E * Bsz, C), _h0(h0i, E * Bsz, C)
+        h2 = torch.empty(2, E, Bsz, L, C, dtype=torch.float32, device=u.device)
+        slot, slot_p, epoch = _slot_args(amax_tracking() and h2.numel() >= (1 << 20), u.device)
+        check(lib().resel_linrec_complex_members_fwd(_p(u[0]), _p(u[1]), ld, _p(lam3[0]), _p(lam3[1]), _p(lam3[2]), _p(start), _p(h0r), _p(h0i),
+                                                     _p(h2[0]), _p(h2[1]), E, Bsz, L, C, slot_p, epoch, _stream()), 'linrec_complex_members_fwd')
+        publish_amax(slot)
+        ctx.save_for_backward(u, lam3, start, h0r, h0i, h2)
+        return h2, u[2]
+
+    @staticmethod
+    def backward(ctx, dh2, du2):
+        u, lam3, start, h0r, h0i, h2 = ctx.saved_tensors
+        _, E, Bsz, L, C = u.shape
+        dh2 = dh2.float().contiguous()
+        du = _like_members(u)
+        dlam3 = torch.empty_like(lam3)
+        ws = _ws(lib().resel_linrec_complex_members_bwd_workspace_bytes(E, Bsz, L, C), u.device)
+        check(lib().resel_linrec_complex_members_bwd(_p(u[0]), _p(u[1]), u.stride(3), _p(lam3[0]), _p(lam3[1]), _p(lam3[2]), _p(start),
+                                                     _p(h0r), _p(h0i), _p(h2[0]), _p(h2[1]), _p(dh2[0]), _p(dh2[1]), _p(du[0]), _p(du[1]),
+                                                     du.stride(3), _p(dlam3[0]), _p(dlam3[1]), _p(dlam3[2]), _p(ws), E, Bsz, L, C, _stream()),
+              'linrec_complex_members_bwd')
+        if du2 is None:
+            du[2].zero_()
+        else:
+            du[2].copy_(du2)
+        return du, dlam3, None, None, None
+
+
+def complex_scan_ensemble(u, lam3, start=None, h0r=None, h0i=None):
+    """The `elru-<E>` recurrence, every member in one launch: see `LruEnsembleFn`."""
+    return apply_tagged(LruEnsembleFn.apply, False, u, lam3, start, h0r, h0i)
 
 
 class SubAddMembers(torch.autograd.Function):

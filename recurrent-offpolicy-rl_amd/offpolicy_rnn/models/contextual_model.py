@@ -15,6 +15,8 @@ from ..hip import ops
 
 
 class ContextualModel:
+    member_sequence_layers_ok = False      # the critics set it: only their heads read the member axis an `elru-<E>` / `econv1d-<E>` layer emits
+
     def __init__(self, embedding_input_size: int, embedding_size: int, embedding_hidden: List[int], embedding_activations: List[str],
                  embedding_layer_type: List[str], uni_model_input_size: int, uni_model_output_size: int, uni_model_hidden: List[int],
                  uni_model_activations: List[str], uni_model_layer_type: List[str], fix_rnn_length: int, name: str,
@@ -30,6 +32,20 @@ class ContextualModel:
         uni_in = uni_model_input_size if uni_model_input_mapping_dim == 0 else uni_model_input_mapping_dim
         self.uni_network = RNNBase(embedding_size + uni_in, uni_model_output_size, uni_model_hidden, uni_model_activations,
                                    uni_model_layer_type)
+        if not self.member_sequence_layers_ok:
+            for which, net in (('embedding', self.embedding_network), ('universal', self.uni_network)):
+                bad = [lid for lid, kind in zip(net.layer_type, net.layer_kind) if kind is not None and kind.member_axis]
+                if bad:
+                    raise ValueError(f'{name}: ensemble sequence layer {bad[0]!r} in the {which} stack of a policy - its output carries a '
+                                     f'member axis [E, B, T, C] that the policy heads cannot read; these layers belong in value stacks')
+        else:                                  # the members of the two stacks are the same critics: their counts must agree
+            counts = {(which, lid): layer.num_ensemble for which, net in (('embedding', self.embedding_network), ('universal', self.uni_network))
+                      for lid, layer in zip(net.layer_type, net.layer_list) if hasattr(layer, 'num_ensemble')}
+            if any(net.emits_member_axis() for net in (self.embedding_network, self.uni_network)) and len(set(counts.values())) > 1:
+                (wa, la), ea = next(iter(counts.items()))
+                (wb, lb), eb = next((k, v) for k, v in counts.items() if v != ea)
+                raise ValueError(f'{name}: layer {la!r} of the {wa} stack runs {ea} members but layer {lb!r} of the {wb} stack runs {eb}: '
+                                 f'with an ensemble sequence layer the member counts must agree')
         self.contextual_modules: 'OrderedDict[str, torch.nn.Module]' = OrderedDict()
         self.contextual_register_rnn_base_module(self.embedding_network, 'embedding_model')
         self.contextual_register_rnn_base_module(self.uni_network, 'universal_model')

@@ -56,3 +56,36 @@ class GILRLayer(nn.Module):
         if self.use_ff:
             out = self.ff(out, out_act)
         return out, h[:, -1:, :].transpose(0, 1)
+
+
+class EnsemblePositionWiseFeedForward(nn.Module):
+    """The feed-forward block of the ensemble sequence layers (reference offpolicy_rnn/models/lru/elru.py:217-229): per-member w_1, GELU,
+    w_2 on member-major [E, B, T, C] activations, then ONE LayerNorm over all E x C features of a token jointly (what `eln-E` computes)
+    of w_2(.) + x.  RESEL_MEMBER_SEQ=1: the add and the norm are one pass each way (`ops.member_add_layer_norm`); 0, or a shape the
+    kernels do not take (C % 4, E * C > 2048 - said once): the torch add and LayerNorm."""
+
+    def __init__(self, d_model, n_ensemble, dropout=0.1, desire_ndim=4):
+        super().__init__()
+        self.w_1 = EnsembleLinear(d_model, d_model, n_ensemble, desire_ndim=desire_ndim)
+        self.w_2 = EnsembleLinear(d_model, d_model, n_ensemble, desire_ndim=desire_ndim)
+        self.activation = nn.GELU()
+        self.dropout = nn.Dropout(dropout)
+        self.layer_norm = nn.LayerNorm([n_ensemble, d_model])
+        self._refusal_said = False
+
+    def forward(self, x):
+        E, C = self.layer_norm.normalized_shape
+        h1 = self.w_1(x)
+        y = self.activation(h1)
+        if y.is_cuda:
+            ops.tag_amax(y, ops.amax_of(h1))          # |gelu(v)| <= |v| (see PositionWiseFeedForward)
+        z = self.dropout(self.w_2(self.dropout(y)))
+        ln = self.layer_norm
+        if ops.member_seq_on() and x.is_cuda and x.dtype == torch.float32:
+            if ops.member_layer_norm_ok(E, C):
+                return ops.member_add_layer_norm(z, x, ln.weight, ln.bias, ln.eps)
+            if not self._refusal_said:
+                self._refusal_said = True
+                print(f'[ WARNING ] ensemble feed-forward block: {E} x {C} is outside what the HIP norm kernels take '
+                      f'(width % 4 == 0, E * width <= {ops.MEMBER_NORM_MAX}); this layer keeps the torch add + LayerNorm')
+        return ln((z + x).transpose(0, -2)).transpose(0, -2)

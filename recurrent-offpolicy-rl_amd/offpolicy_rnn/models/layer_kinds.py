@@ -3,22 +3,29 @@ function that looks inside a layer-id string (`kind_of`).  RNNBase resolves the 
 its state factory and the trainers read the records and never test an id themselves.
 
 Ids (reference rnn_base.py:101-247): `gru`, `gilr`, `gilr_lstm`, `lru` by exact name; `smamba[_s<N>][_c<K>][_b<blocks>][_n<ln|...>][_ff]`,
-`mamba[_s<N>][_c<K>][_noff]`, `conv1d[_<K>]`, `cgpt[_h<H>][_l<L>][_p<drop>][_ml<M>][_rms]` by prefix.  The dense ids `fc` / `efc-<E>` have
-no record (`kind_of` returns None): RNNBase keeps a branch of its own for them.  Ids of reference layers that are outside this build
-(`lstm`, `e<rnn>-<E>`, `econv1d*`, `gpt*`, `transformer*`, `cgru`) are recognised and rejected with an explicit message."""
+`mamba[_s<N>][_c<K>][_noff]`, `conv1d[_<K>]`, `cgpt[_h<H>][_l<L>][_p<drop>][_ml<M>][_rms]` by prefix; the ensemble sequence layers
+`elru-<E>` and `econv1d[_<K>]-<E>` (E >= 1, K from 1 to 32, plain decimal digits) by a regular expression - they give every member of an
+`efc-<E>` critic its own context encoder and belong in value stacks only.  The dense ids `fc` / `efc-<E>` have no record (`kind_of`
+returns None): RNNBase keeps a branch of its own for them.  Ids of reference layers that are outside this build (`lstm`, `egilr-<E>`,
+`egilr_lstm-<E>`, `gpt*`, `transformer*`, `cgru`) are recognised and rejected with an explicit message."""
+import re
 from dataclasses import dataclass
 from typing import Callable, Optional
 
 from .conv1d.conv1d import Conv1d
+from .conv1d.econv1d import EConv1d
 from .flash_attention.TransformerFlashAttention import InferenceParams, TransformerDecoder
 from .gilr.gilr import GILRLayer
 from .gilr_lstm.gilr_lstm import GILRLSTMLayer
 from .gru import GRU
+from .lru.elru import EnsembleLRULayer
 from .lru.lru import LRULayer
 from .s6.mamba import MambaResidualBlock
 from .smamba.mamba import BlockList as MambaBlockList
 
-_UNSUPPORTED_PREFIXES = ('lstm', 'econv1d', 'gpt', 'transformer', 'cgru', 'elru', 'egilr')
+_UNSUPPORTED_PREFIXES = ('lstm', 'gpt', 'transformer', 'cgru', 'egilr')
+_E_SEQ_ID = re.compile(r'(elru|econv1d)(?:_([0-9]+))?-([0-9]+)')          # int('4_4') is 44 in Python: the digits are matched, not converted
+ECONV1D_MAX_TAPS = 32                       # what csrc/causal_conv1d.hip takes
 
 
 def parse_smamba_id(layer_id: str) -> dict:
@@ -73,6 +80,22 @@ def parse_cgpt_id(layer_id: str) -> dict:
     return cfg
 
 
+def parse_e_seq_id(layer_id: str) -> dict:
+    """`elru-<E>` / `econv1d[_<K>]-<E>` -> dict(family, num_ensemble, d_conv); anything else behind these prefixes raises."""
+    m = _E_SEQ_ID.fullmatch(layer_id)
+    bad = NotImplementedError(f'layer id {layer_id!r}: expected elru-<E> or econv1d[_<K>]-<E> with E >= 1 and K from 1 to '
+                              f'{ECONV1D_MAX_TAPS} in plain decimal digits')
+    if m is None:
+        raise bad
+    family, k, e = m.group(1), m.group(2), int(m.group(3))
+    if e < 1 or (family == 'elru' and k is not None):
+        raise bad
+    d_conv = 4 if k is None else int(k)
+    if family == 'econv1d' and not 1 <= d_conv <= ECONV1D_MAX_TAPS:
+        raise bad
+    return dict(family=family, num_ensemble=e, d_conv=d_conv)
+
+
 def _never(layer, x) -> bool:
     return False
 
@@ -95,7 +118,10 @@ class LayerKind:
         segments), so rows may pack several trajectories and a pass shifted by one slot computes the same tokens.
     context_len(layer): tokens in front of a sampled sequence that the layer reads (a causal convolution's window).
     packs_sequences: consumes the per-row sequence-length table (`attention_concat_mask`).
-    make_state(width, batch_size): the rollout state where it is no zero tensor of (1, batch, width)."""
+    make_state(width, batch_size): the rollout state where it is no zero tensor of (1, batch, width).
+    member_axis: an ensemble sequence layer - its output carries a leading member axis [E, B, T, C] (it takes member-major or shared
+        input), every member of the stack has to be evaluated (`RNNBase.members_coupled`), it cannot sit in a policy stack and is
+        never stepped one token at a time."""
     name: str
     build: Callable
     call: Optional[Callable]
@@ -105,9 +131,10 @@ class LayerKind:
     context_len: Callable = _no_context
     packs_sequences: bool = False
     make_state: Optional[Callable] = None
+    member_axis: bool = False
 
     def __reduce__(self):                   # a copied / pickled network keeps pointing at the one record of its family
-        return kind_of, (self.name,)
+        return kind_by_name, (self.name,)
 
 
 def _whole_rows(x) -> bool:
@@ -122,6 +149,17 @@ def _build_mamba(lid, n_in, n_out):
 
 def _build_conv1d(lid, n_in, n_out):
     layer = Conv1d(n_in, n_out, d_conv=int(lid.split('_')[-1]) if '_' in lid else 4)
+    return layer, layer.desired_hidden_dim
+
+
+def _build_elru(lid, n_in, n_out):
+    E = parse_e_seq_id(lid)['num_ensemble']
+    return EnsembleLRULayer(n_in, n_out, E, batch_first=True), n_out * 2 * E
+
+
+def _build_econv1d(lid, n_in, n_out):
+    cfg = parse_e_seq_id(lid)
+    layer = EConv1d(n_in, n_out, num_ensemble=cfg['num_ensemble'], d_conv=cfg['d_conv'])
     return layer, layer.desired_hidden_dim
 
 
@@ -175,8 +213,21 @@ CGPT = LayerKind(                                       # the ELU rides in the d
     'cgpt', build=_build_cgpt, call=_call_cgpt, fuses_out_act=lambda layer, x: _whole_rows(x), packs_sequences=True,
     make_state=lambda width, batch_size: InferenceParams(max_seqlen=width, max_batch_size=batch_size))
 
+ELRU = LayerKind(                                       # (no ELU rides in its closing add + norm: the activation module runs behind it)
+    'elru', build=_build_elru, call=lambda layer, x, state, side, out_act: layer(x, state, side.rnn_start, side.grad_detach),
+    member_axis=True)
+ECONV1D = LayerKind(
+    'econv1d', build=_build_econv1d, call=lambda layer, x, state, side, out_act: layer(x, state, side.mask),
+    context_len=lambda layer: layer.d_conv, member_axis=True)
+
 _EXACT = {k.name: k for k in (GRU_KIND, GILR, GILR_LSTM, LRU)}
 _PREFIXED = (SMAMBA, MAMBA, CONV1D, CGPT)
+_E_SEQ = {k.name: k for k in (ELRU, ECONV1D)}
+_BY_NAME = {k.name: k for k in (GRU_KIND, GILR, GILR_LSTM, LRU, SMAMBA, MAMBA, CONV1D, CGPT, ELRU, ECONV1D)}
+
+
+def kind_by_name(name: str) -> LayerKind:
+    return _BY_NAME[name]
 
 
 def is_rnn_layer(layer_id: str) -> bool:
@@ -193,6 +244,15 @@ def kind_of(lid: str) -> Optional[LayerKind]:
     for kind in _PREFIXED:
         if lid.startswith(kind.name):
             return kind
+    if lid.startswith(('elru', 'econv1d')):
+        return _E_SEQ[parse_e_seq_id(lid)['family']]
+    if lid.startswith('egilr'):
+        # `egilr-<E>` does not run in the reference: EnsembleGILRLayer transposes the [1, B, E C] state RNNBase hands it and then scans
+        # E B rows of width C (gilr/egilr.py:72-76), so its first forward raises, at layer level and in the trainers; `egilr_lstm-<E>`
+        # is mapped to the ensemble LRU class there (rnn_base.py:110-113) - use `elru-<E>` for that
+        raise NotImplementedError(f"layer id {lid!r}: the reference's EnsembleGILRLayer raises on its first forward (it transposes the "
+                                  f"[1, B, E*C] state and scans E*B rows of width C, gilr/egilr.py:72-76), and it maps egilr_lstm-<E> to "
+                                  f"its ensemble LRU class (rnn_base.py:110-113): use elru-<E>")
     if lid == 'lstm':
         # the reference lists `lstm` (rnn_base.py:58) but cannot run it on this path either: ContextualModel.meta_forward asks every
         # embedding network for its full hidden sequence (contextual_model.py:92-94, 113-115) and RNNHidden refuses to hold one for an
@@ -201,5 +261,5 @@ def kind_of(lid: str) -> Optional[LayerKind]:
                                   "when ContextualModel.meta_forward requests the full hidden sequence, contextual_model.py:92-94)")
     if lid.startswith(_UNSUPPORTED_PREFIXES):
         raise NotImplementedError(f'layer id {lid!r} exists in the reference but is outside the MI355X hot path of this build '
-                                  f'(supported: fc, efc-<E>, gru, gilr, lru, gilr_lstm, smamba_*, mamba_*, conv1d_*, cgpt_*)')
+                                  f'(supported: fc, efc-<E>, gru, gilr, lru, gilr_lstm, smamba_*, mamba_*, conv1d_*, cgpt_*, elru-<E>, econv1d_*-<E>)')
     raise NotImplementedError(f'unknown layer id {lid!r}')

@@ -16,9 +16,11 @@ from .RNNHidden import RNNHidden
 from .ensemble_linear_model import EnsembleLinear, critic_mlp, critic_mlp_fusable, ensemble_head, head_fusable
 from .flash_attention.TransformerFlashAttention import TransformerDecoder
 from .conv1d.conv1d import Conv1d
+from .conv1d.econv1d import EConv1d
 from .gilr.gilr import GILRLayer
 from .gilr_lstm.gilr_lstm import GILRLSTMLayer
 from .s6.mamba import MambaResidualBlock
+from .lru.elru import EnsembleLRULayer
 from .lru.lru import LRULayer
 from .smamba.mamba import BlockList as MambaBlockList
 from .layer_kinds import is_rnn_layer, kind_of, parse_cgpt_id, parse_mamba_id, parse_smamba_id  # noqa: F401  (the parsers: part of this module's surface)
@@ -81,6 +83,7 @@ class RNNBase(torch.nn.Module):
             self.activation_list.append(self._make_activation(activation[ind], width))
             width_in = width
         self.rnn_layer_kind = [kind for kind in self.layer_kind if kind is not None]           # beside rnn_layer_type
+        self._check_member_counts()
         self._norm_refused = set()              # layers whose `+` norm the HIP kernels refused (logged once each)
         self.xavier_initialize_weights()
 
@@ -92,6 +95,16 @@ class RNNBase(torch.nn.Module):
         if lid == 'fc':
             return Linear(n_in, n_out), None
         return EnsembleLinear(n_in, n_out, int(lid.split('-')[-1])), None
+
+    def _check_member_counts(self):
+        """An ensemble sequence layer (`elru-<E>`, `econv1d[_K]-<E>`) runs E members: the `efc-<E>` layers of its stack must agree."""
+        for lid, kind, layer in zip(self.layer_type, self.layer_kind, self.layer_list):
+            if kind is None or not kind.member_axis:
+                continue
+            for other, mod in zip(self.layer_type, self.layer_list):
+                if isinstance(mod, (EnsembleLinear, EnsembleLRULayer, EConv1d)) and mod.num_ensemble != layer.num_ensemble:
+                    raise ValueError(f'layer {lid!r} runs {layer.num_ensemble} members but layer {other!r} of the same stack runs '
+                                     f'{mod.num_ensemble}: the member counts of a stack must agree')
 
     @staticmethod
     def _make_activation(spec: str, width: int):
@@ -124,6 +137,14 @@ class RNNBase(torch.nn.Module):
             elif isinstance(m, LRULayer):
                 xavier_ensemble(m.in_proj)
                 xavier_ensemble(m.middle_proj)
+            elif isinstance(m, EnsembleLRULayer):           # Xavier per [i, j] slice, zero biases (reference rnn_base.py:284-290)
+                with torch.no_grad():
+                    for efc in (m.in_proj, m.middle_proj):
+                        for i in range(efc.weight.shape[0]):
+                            for j in range(efc.weight.shape[1]):
+                                torch.nn.init.xavier_uniform_(efc.weight[i, j].transpose(0, 1))
+                        if getattr(efc, 'bias', None) is not None:
+                            efc.bias.zero_()
             elif isinstance(m, GILRLayer):
                 torch.nn.init.xavier_uniform_(m.out_proj.weight)
                 torch.nn.init.constant_(m.out_proj.bias, 0)
@@ -133,7 +154,7 @@ class RNNBase(torch.nn.Module):
                 torch.nn.init.constant_(m.out_proj.bias, 0)
                 xavier_ensemble(m.in_proj)
                 xavier_ensemble(m.middle_proj)
-            elif isinstance(m, (MambaBlockList, TransformerDecoder, MambaResidualBlock, Conv1d)):
+            elif isinstance(m, (MambaBlockList, TransformerDecoder, MambaResidualBlock, Conv1d, EConv1d)):
                 pass
             else:
                 for name, param in m.named_parameters():
@@ -147,8 +168,14 @@ class RNNBase(torch.nn.Module):
         return [(kind, layer) for kind, layer in zip(self.layer_kind, self.layer_list) if kind is not None]
 
     def members_coupled(self) -> bool:
-        """An `eln-<E>` norm normalises a token over ALL members jointly: the members of this stack cannot be evaluated as a subset."""
-        return any(spec.startswith('eln') for spec in self.activation_type)
+        """An `eln-<E>` norm normalises a token over ALL members jointly: the members of this stack cannot be evaluated as a subset.  Nor
+        can those of a stack with an ensemble sequence layer: its feed-forward block holds the same joint norm, and its state and
+        activations are laid out for all E members."""
+        return any(spec.startswith('eln') for spec in self.activation_type) or self.emits_member_axis()
+
+    def emits_member_axis(self) -> bool:
+        """The stack holds an ensemble sequence layer: what it hands on carries a leading member axis [E, B, T, C]."""
+        return any(kind is not None and kind.member_axis for kind in self.layer_kind)
 
     def rnn_parameters(self, recursive=True):
         out = []

@@ -14,6 +14,8 @@ from ..models.linear import Linear
 
 
 class ContextualSACDiscreteValue(ContextualModel):
+    member_sequence_layers_ok = True
+
     def __init__(self, state_dim, action_dim, embedding_size, embedding_hidden, embedding_activations, embedding_layer_type,
                  uni_model_hidden, uni_model_activations, uni_model_layer_type, fix_rnn_length, uni_model_input_mapping_dim: int = 0,
                  reward_input=False, last_action_input=True, last_state_input=False, separate_encoder=False):

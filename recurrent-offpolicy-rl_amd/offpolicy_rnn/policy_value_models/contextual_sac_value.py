@@ -13,6 +13,8 @@ from ..models.linear import Linear
 
 
 class ContextualSACValue(ContextualModel):
+    member_sequence_layers_ok = True
+
     def __init__(self, state_dim, action_dim, embedding_size, embedding_hidden, embedding_activations, embedding_layer_type,
                  uni_model_hidden, uni_model_activations, uni_model_layer_type, fix_rnn_length, uni_model_input_mapping_dim: int = 0,
                  reward_input=False, last_action_input=True, last_state_input=False, separate_encoder=False, name='ContextualSACValue'):
@@ -56,7 +58,9 @@ class ContextualSACValue(ContextualModel):
         part = None
         # GPU passes: the head input [state-action encoding | embedding] is ONE row buffer whose column blocks the producing GEMMs write
         # in place (no cat of 205 MB per pass at config 2, one shared magnitude handle instead of a pre-pass)
-        rb = self.head_row_buffer(state.shape[:-1], state.device, state.dtype) if self.separate_encoder else None
+        # (not behind an ensemble sequence layer: its embedding is member-major [E, B, T, C] and is joined to the encoding by the plain cat)
+        rb = self.head_row_buffer(state.shape[:-1], state.device, state.dtype) \
+            if self.separate_encoder and not self.embedding_network.emits_member_axis() else None
         if detach_embedding and torch.is_grad_enabled() and action.requires_grad and self._action_only_graph():
             # actor step: frozen critic, detached embedding - the ONLY differentiable input of the head is the action encoding.
             # Encode state and action separately so that the first layer's backward forms just that column block of dX.
@@ -80,6 +84,7 @@ class ContextualSACValue(ContextualModel):
         first = self.uni_network.layer_list[0]
         from ..models.ensemble_linear_model import EnsembleLinear
         return (self.separate_encoder and isinstance(self.state_input_encoder, torch.nn.Linear)
+                and not self.embedding_network.emits_member_axis()       # member-major head input: the first layer is no shared-input layer
                 and not self.state_input_encoder.weight.requires_grad and not self.action_input_encoder.weight.requires_grad
                 and isinstance(first, EnsembleLinear) and not first.weight.requires_grad
                 and self._first_act_fusable(first) and len(self.uni_network.layer_list) > 1)
