@@ -711,6 +711,20 @@ int resel_gather_trajs_sel(const float* buffer, int W, int64_t capacity, const i
  * ring.  No alignment beyond 4 bytes and no multiple is asked of W or batch.  p outside [0, passes) without a pass word is RESEL_EINVAL. */
 int resel_gather_transitions(const float* buffer, int W, int64_t capacity, const int* rows, int passes, int batch, int p,
                              const int* pass_word, int c_done, int c_timeout, float* out, resel_stream_t stream);
+/* Slice batches from the same ring (the slice trainer; reference replay_memory_tail_padding.py `sample_fix_length_sub_trajs`), ONE launch:
+ *   plan [passes][batch][2] int32 = (row0: ring row of the slice's first transition, n: its valid rows, 1 <= n <= L);
+ *   out [batch][L + 1][W]:  slot 0      the PRE-STEP row: zero, except out[b][0][dst] = buffer[row0][src] for the npairs (dst, src) column
+ *                                       pairs of pre_pairs (the convention of resel_gather_trajs; the slice trainer passes next_state <- state,
+ *                                       state <- last_state, action <- last_action, reward <- reward_input);
+ *                           slots 1..n  buffer[row0 .. row0 + n - 1][:], done written as 0 where the row's timeout column is > 0 (c_timeout >= 0);
+ *                           slots n+1..L zero (the tail behind the trajectory's end: mask = 0).
+ * out[:, 1:] is the batch, out[:, :] read through the destination columns is the L + 1 window of the target pass.  Every element of out
+ * is written.  p is the argument, or pass_word[0] when pass_word is not NULL.  A plan entry with row0 < 0, n < 1, n > L or
+ * row0 + n > capacity, or a pass word outside [0, passes), yields an all-zero slice and reads nothing of the ring; a pair whose source
+ * column is outside [0, W) is skipped.  No alignment beyond 4 bytes and no multiple is asked of W, L or batch.  p outside [0, passes)
+ * without a pass word, or (L + 1) * W above 65535 * 256, is RESEL_EINVAL. */
+int resel_gather_slices(const float* buffer, int W, int64_t capacity, const int* plan, int passes, int batch, int L, int p,
+                        const int* pass_word, int c_done, int c_timeout, const int* pre_pairs, int npairs, float* out, resel_stream_t stream);
 
 /* ---- one-token rollout step (T = 1): the policy forward between updates -------------------------------------------
  * Reference: the outer loop calls policy.forward once per environment step (algorithm/sac.py:319-326), which reaches

@@ -103,7 +103,58 @@ __global__ __launch_bounds__(256) void gather_transitions_kernel(const float* __
     }
 }
 
+// Slice batches (the slice trainer): out[b, 0, :] = the PRE-STEP row of slice b's first transition (zero but for the column pairs),
+// out[b, 1 .. n, :] = ring rows row0 .. row0 + n - 1 with done <- 0 where the row timed out, out[b, n + 1 .. L, :] = 0; (row0, n) =
+// plan[p, b].  grid = (batch, ceil((L + 1) W / 256)): one float per thread along the contiguous (slot, column) axis of a slice - the n
+// ring rows of a slice are contiguous too, so every wave access is a fully used row segment (plain 4-byte loads and stores: W is whatever
+// the environment makes it).  EVERY element of out is written.  The pass p comes from the device word when there is one.  A pass outside
+// [0, passes), row0 < 0, n < 1, n > L or row0 + n > capacity gives an all-zero slice and reads nothing of the ring; a pair whose source
+// column is outside [0, W) is skipped.
+__global__ __launch_bounds__(256) void gather_slices_kernel(const float* __restrict__ buffer, int W, int64_t capacity,
+                                                            const int* __restrict__ plan, int passes, int batch, int L, int p_arg,
+                                                            const int* __restrict__ pass_word, int c_done, int c_timeout,
+                                                            const int* __restrict__ pre_pairs, int npairs, float* __restrict__ out) {
+    const int b = blockIdx.x;
+    const int e = blockIdx.y * blockDim.x + threadIdx.x;
+    if (b >= batch || e >= (L + 1) * W) return;
+    const int p = pass_word ? pass_word[0] : p_arg;
+    int row0 = -1, n = 0;
+    if (p >= 0 && p < passes) {
+        const int* entry = plan + ((int64_t)p * batch + b) * 2;
+        row0 = entry[0];
+        n = entry[1];
+    }
+    const bool ok = row0 >= 0 && n >= 1 && n <= L && (int64_t)row0 + n <= capacity;
+    const int slot = e / W, col = e - slot * W;
+    float v = 0.f;
+    if (ok && slot == 0) {
+        const float* first = buffer + (int64_t)row0 * W;
+        for (int k = 0; k < npairs; ++k) {
+            const int src = pre_pairs[2 * k + 1];
+            if (pre_pairs[2 * k] == col && src >= 0 && src < W) v = first[src];
+        }
+    } else if (ok && slot <= n) {
+        const float* src = buffer + ((int64_t)row0 + slot - 1) * W;
+        v = src[col];
+        if (col == c_done && c_timeout >= 0 && src[c_timeout] > 0.f) v = 0.f;      // time-limit terminations bootstrap
+    }
+    out[(int64_t)b * (L + 1) * W + e] = v;
+}
+
 }  // namespace
+
+extern "C" int resel_gather_slices(const float* buffer, int W, int64_t capacity, const int* plan, int passes, int batch, int L, int p,
+                                   const int* pass_word, int c_done, int c_timeout, const int* pre_pairs, int npairs, float* out,
+                                   resel_stream_t stream) {
+    if (!buffer || !plan || !out || W <= 0 || capacity <= 0 || passes <= 0 || batch <= 0 || L <= 0) return RESEL_EINVAL;
+    if (c_done < 0 || c_done >= W || c_timeout >= W || npairs < 0 || (npairs > 0 && !pre_pairs)) return RESEL_EINVAL;
+    if (!pass_word && (p < 0 || p >= passes)) return RESEL_EINVAL;
+    const int64_t per_slice = ((int64_t)L + 1) * W, chunks = (per_slice + 255) / 256;
+    if (chunks > 65535) return RESEL_EINVAL;          // (grid.y; per_slice then fits an int with room to spare)
+    hipLaunchKernelGGL(gather_slices_kernel, dim3((unsigned)batch, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, buffer, W, capacity,
+                       plan, passes, batch, L, p, pass_word, c_done, c_timeout, pre_pairs, npairs, out);
+    return launch_status();
+}
 
 extern "C" int resel_gather_transitions(const float* buffer, int W, int64_t capacity, const int* rows, int passes, int batch, int p,
                                         const int* pass_word, int c_done, int c_timeout, float* out, resel_stream_t stream) {

@@ -1,9 +1,10 @@
-"""One `train_one_batch()` of the memoryless REDQ trainer (algorithm/sac_mlp_redq_ensemble_q.py) as `utd` hipGraph replays.
+"""One `train_one_batch()` of a trainer whose passes are fixed-shape batches - the memoryless REDQ trainer
+(algorithm/sac_mlp_redq_ensemble_q.py), the slice trainer (algorithm/sac_rnn_slice.py) - as `utd` hipGraph replays.
 
 REDQ's usual setting is utd = 20 on a few hundred transitions: twenty launch-bound passes per environment step, each a few dozen small
 kernels.  The captured unit is ONE pass of the `utd` loop (profiles/r17_utd_replay.md), in two recordings - with and without the actor
 step - keyed on nothing else: the batch size is fixed.  A step is
-    one H2D of a pinned block  [rows int32 [utd, batch] | REDQ subsets int32 [utd, redq_m] | pass word (0) | AdamW factors fp32 [utd, 4]],
+    one H2D of a pinned block  [plans int32 [utd, words] | REDQ subsets int32 [utd, redq_m] | pass word (0) | AdamW factors fp32 [utd, 4]],
     `utd` replays, the two parameter norms of the log (launched once, behind the last pass), one D2H of the log block.
 How a replay finds its slice: the PASS WORD, a device int32 inside that block.  The gather kernel reads its rows through it
 (`ops.gather_transitions(pass_word=...)`), two `index_select`s by it fetch the pass's subset and bias corrections into the buffers the
@@ -12,7 +13,12 @@ pass advances it with an ordinary add.  The host half of a step draws from numpy
 subset - and counts the optimizer steps.  Actor noise inside a recording comes from torch's CUDA generator, which the capture registers:
 graph-safe Philox offsets, fresh numbers on every replay.  The recording policy (warm-up passes, record on the second occurrence) and the
 log's slots and read-back are those of the full-trajectory driver (graph_policy.py, graph_staging.py).  Recorded kernel nodes carry
-magnitude epochs: when `ops.amax_maintenance()` starts a new generation at a step boundary, the recordings are dropped and made again."""
+magnitude epochs: when `ops.amax_maintenance()` starts a new generation at a step boundary, the recordings are dropped and made again.
+
+What the trainer supplies: `graph_plan_words()` (int32 words of one pass's plan: `batch` rows for the REDQ trainer, `2 * batch` for
+the slice trainer's (row, valid rows) pairs), `graph_plan_pass()` (one pass's plan, drawn as the eager pass draws it), `graph_gather(ring,
+table [utd, words], pass word)`, `graph_subset_size()` (0: the trainer has no REDQ subset, and the block has no subset part) with
+`num_ensemble` when it is not 0, and `graph_optimizers()` -> (those the critic step advances, those the actor step advances)."""
 import gc
 
 import numpy as np
@@ -53,11 +59,11 @@ class GraphedTransitionUpdate:
         if par.utd < 1:
             raise ValueError(f'GraphedTransitionUpdate: utd={par.utd} (an update is at least one pass)')
         self.alg, self.device = alg, alg.device
-        self.utd, self.batch, self.m = int(par.utd), int(par.sac_batch_size), int(par.redq_m)
-        n_rows, n_sub = self.utd * self.batch, self.utd * self.m
+        self.utd, self.words, self.m = int(par.utd), int(alg.graph_plan_words()), int(alg.graph_subset_size())
+        n_rows, n_sub = self.utd * self.words, self.utd * self.m
         words = n_rows + n_sub + 1 + 4 * self.utd
         self._block = torch.zeros(words, dtype=torch.int32, device=self.device)
-        self.rows_dev = self._block[:n_rows].view(self.utd, self.batch)
+        self.rows_dev = self._block[:n_rows].view(self.utd, self.words)
         self.sub_dev = self._block[n_rows:n_rows + n_sub].view(self.utd, self.m)
         self.pass_word = self._block[n_rows + n_sub:n_rows + n_sub + 1]
         self.bc_dev = self._block[n_rows + n_sub + 1:].view(torch.float32).view(self.utd, 4)
@@ -65,7 +71,8 @@ class GraphedTransitionUpdate:
         self._turn = 0
         self.subset_i32 = torch.zeros(self.m, dtype=torch.int32, device=self.device)      # this pass's subset, as the target reads it
         self.subset_i64 = torch.zeros(self.m, dtype=torch.int64, device=self.device)      # ... and as `member_index`
-        for opt in (alg.optimizer_value, alg.optimizer_policy):
+        self.critic_opts, self.actor_opts = alg.graph_optimizers()
+        for opt in self.critic_opts + self.actor_opts:
             opt.enable_device_factors()
         self.log = UpdateLog(self.LOG_SLOTS, self.device, log_cls=ScalarLog)
         self.recording = RecordingPolicy(warmup, None, 'off', sequences=max(1, len(set(self.pass_schedule(alg)))))
@@ -87,8 +94,7 @@ class GraphedTransitionUpdate:
         return self._pass
 
     def gather(self):
-        c_done, c_timeout = self.alg._ring_columns()
-        return ops.gather_transitions(self._ring_dev, self.rows_dev, self.pass_word, 0, c_done, c_timeout)
+        return self.alg.graph_gather(self._ring_dev, self.rows_dev, self.pass_word)
 
     def target_subset(self):
         return self.subset_i32, self.subset_i64
@@ -110,34 +116,39 @@ class GraphedTransitionUpdate:
         if slot['used']:
             slot['evt'].synchronize()
         host = slot['host'].numpy()
-        n_rows, n_sub = self.utd * self.batch, self.utd * self.m
-        rows, sub = host[:n_rows].reshape(self.utd, self.batch), host[n_rows:n_rows + n_sub].reshape(self.utd, self.m)
+        n_rows, n_sub = self.utd * self.words, self.utd * self.m
+        rows, sub = host[:n_rows].reshape(self.utd, self.words), host[n_rows:n_rows + n_sub].reshape(self.utd, self.m)
         bc = host[n_rows + n_sub + 1:].view(np.float32).reshape(self.utd, 4)
         for p, actor_due in enumerate(schedule):
-            rows[p] = alg.replay_buffer.plan_transitions(self.batch, 1)[0]
-            sub[p] = np.random.permutation(alg.num_ensemble)[:self.m]
-            for i, opt in enumerate((alg.optimizer_value, alg.optimizer_policy)):
+            rows[p] = alg.graph_plan_pass()
+            if self.m:
+                sub[p] = np.random.permutation(alg.num_ensemble)[:self.m]
+            for i, opts in enumerate((self.critic_opts, self.actor_opts)):
                 if i == 0 or actor_due:
-                    opt.step_count += 1
-                    bc[p, 2 * i:2 * i + 2] = ops.adamw_bias_corrections(opt.betas[0], opt.betas[1], opt.step_count)
+                    for opt in opts:                  # (the optimizers of one step count together: one pair of factors serves them)
+                        opt.step_count += 1
+                    bc[p, 2 * i:2 * i + 2] = ops.adamw_bias_corrections(opts[0].betas[0], opts[0].betas[1], opts[0].step_count)
         host[n_rows + n_sub] = 0                      # the pass word starts every step at pass 0
         self._block.copy_(slot['host'], non_blocking=True)
 
     def _body(self):
         alg = self.alg
-        opts = (alg.optimizer_value, alg.optimizer_policy)
+        opts = self.critic_opts + self.actor_opts
         alg._graph = self
         for opt in opts:
             opt.device_factors_active = True
         try:
             ops.amax_arena_zero(self.device)          # first node: a replay publishes operand magnitudes into the slots / epochs baked into the graph
             # this pass's slice of the step's tables, through the pass word
-            self.subset_i32.copy_(self.sub_dev.index_select(0, self.pass_word).view(-1))
-            self.subset_i64.copy_(self.subset_i32)
+            if self.m:
+                self.subset_i32.copy_(self.sub_dev.index_select(0, self.pass_word).view(-1))
+                self.subset_i64.copy_(self.subset_i32)
             bc = self.bc_dev.index_select(0, self.pass_word).view(-1)
-            opts[0]._bc_dev.copy_(bc[0:2])
+            for opt in self.critic_opts:
+                opt._bc_dev.copy_(bc[0:2])
             if alg._actor_due(*self._pass):
-                opts[1]._bc_dev.copy_(bc[2:4])
+                for opt in self.actor_opts:
+                    opt._bc_dev.copy_(bc[2:4])
             with training_pass():
                 alg._train_one_batch()
             self.pass_word.add_(1)                    # last node: the next replay serves the next pass

@@ -99,6 +99,24 @@ class SAC_MLP_REDQ_EnsembleQ(SAC):
         R = self.replay_buffer.name2range
         return {name: batch[:, R[name][0]:R[name][1]] for name in FIELDS}
 
+    # ---- the driver's view of this trainer's plan (graphed_transition_update.py)
+    def graph_plan_words(self):
+        return self.parameter.sac_batch_size
+
+    def graph_subset_size(self):
+        return self.parameter.redq_m
+
+    def graph_plan_pass(self):
+        return self.replay_buffer.plan_transitions(self.parameter.sac_batch_size, 1)[0]
+
+    def graph_gather(self, ring_dev, table, pass_word):
+        c_done, c_timeout = self._ring_columns()
+        return ops.gather_transitions(ring_dev, table, pass_word, 0, c_done, c_timeout)
+
+    def graph_optimizers(self):
+        """-> (the optimizers the critic step advances, those the actor step advances)."""
+        return [self.optimizer_value], [self.optimizer_policy]
+
     def _sample(self):
         """One transition batch -> its field views on the trainer's device, `done` already 0 where the transition timed out."""
         ring, n = self.replay_buffer, self.parameter.sac_batch_size

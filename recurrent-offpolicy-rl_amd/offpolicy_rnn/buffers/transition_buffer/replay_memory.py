@@ -240,6 +240,39 @@ class MemoryArray:
             rows[p] = starts[traj] + (rank - (ends[traj] - lens[traj]))
         return rows
 
+    def plan_slices(self, batch_size: int, fix_length: int, passes: int = 1) -> np.ndarray:
+        """Host half of a slice batch taken from the device mirror of the ring (`ops.gather_slices`): per pass exactly the draw of
+        `sample_fix_length_sub_trajs(batch_size, fix_length)` - one `randint(0, transition_count, batch_size)` from the global numpy
+        stream -, each drawn rank (traj, point) mapped to (ring row of the slice's first transition, its valid rows =
+        min(fix_length, length - point)).  -> int32 [passes, batch_size, 2].  No Python loop per transition (`plan_transitions`)."""
+        starts = np.asarray(self.trajectory_start, dtype=np.int64)
+        lens = np.asarray(self.trajectory_length, dtype=np.int64)
+        ends = np.cumsum(lens)
+        plan = np.empty((int(passes), int(batch_size), 2), dtype=np.int32)
+        for p in range(int(passes)):
+            rank = np.random.randint(0, self.transition_count, batch_size)
+            traj = np.searchsorted(ends, rank, side='right')
+            point = rank - (ends[traj] - lens[traj])
+            plan[p, :, 0] = starts[traj] + point
+            plan[p, :, 1] = np.minimum(int(fix_length), lens[traj] - point)
+        return plan
+
+    def slices_from_plan(self, plan: np.ndarray, fix_length: int) -> np.ndarray:
+        """The host batch of one pass of a slice plan (int32 [batch, 2]) -> [batch, fix_length, width] in the ring's dtype.  The rows
+        behind a trajectory's end are ZERO: in this flat ring the row behind a trajectory belongs to the next one, so the tail comes from
+        the plan's valid count (the trajectory length table), never from the ring."""
+        plan = np.asarray(plan).reshape(-1, 2)
+        at = np.arange(int(fix_length))
+        valid = at[None, :] < plan[:, 1:2]
+        rows = np.where(valid, plan[:, 0:1] + at[None, :], 0)
+        return np.where(valid[..., None], self.memory_buffer[rows], 0).astype(self.STORE_DTYPE)
+
+    def sample_fix_length_sub_trajs(self, batch_size: int, fix_length: int) -> Transition:
+        """Slices of `fix_length` transitions that start at `batch_size` uniformly drawn stored transitions and are zero-padded behind
+        their trajectory's end (reference buffers/replay_memory_tail_padding.py:22-36; the one `randint` draw is the reference's).
+        -> Transition of [batch_size, fix_length, w] arrays; `mask` is 0 on the padding."""
+        return self.array_to_transition(self.slices_from_plan(self.plan_slices(batch_size, fix_length, 1)[0], fix_length))
+
     def _mirror(self, device):
         """Device copy of the ring, refreshed for the rows written since the last call (a rollout adds one trajectory
         between updates; the synthetic benchmark fills the ring once)."""

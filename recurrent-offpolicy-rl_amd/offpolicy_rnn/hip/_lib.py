@@ -170,6 +170,7 @@ SIGNATURES = {
     'resel_gather_trajs': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, S]),
     'resel_gather_trajs_sel': (c_int, [P, I, L, P, I, I, I, I, I, I, I, I, I, P, I, P, I, P, S]),
     'resel_gather_transitions': (c_int, [P, I, L, P, I, I, I, P, I, I, P, S]),
+    'resel_gather_slices': (c_int, [P, I, L, P, I, I, I, I, P, I, I, P, I, P, S]),
     'resel_mamba_conv_step': (c_int, [P, L, P, L, P, L, L, L, I, P, P, P, I, I, I, I, S]),
     'resel_selective_state_update': (c_int, [P, L, P, L, P, P, L, P, P, P, P, P, L, P, I, I, I, I, S]),
     'resel_atb_workspace_bytes': (c_size_t, [L, I, I]),

@@ -2178,6 +2178,25 @@ def gather_transitions(buffer, rows_dev, pass_word=None, p=0, c_done=0, c_timeou
 
 
 @torch.no_grad()
+def gather_slices(buffer, plan_dev, length, pre_pairs, pass_word=None, p=0, c_done=0, c_timeout=-1):
+    """Slice batch [batch, length + 1, W] from the device ring `buffer` [capacity, W] and the int32 plan `plan_dev` [passes, batch, 2] =
+    (ring row of the slice's first transition, valid rows): slot 0 is the pre-step row (zero but for the int32 [npairs, 2] (dst, src)
+    column pairs `pre_pairs`), slots 1 .. n the ring rows with done 0 where timeout > 0, the rest zero.  The pass is `p`, or the int32
+    device word `pass_word` when given.  See include/resel_hip.h `resel_gather_slices`."""
+    _need_cuda('gather_slices', buffer, plan_dev, pre_pairs, *(() if pass_word is None else (pass_word,)))
+    assert buffer.dtype == torch.float32 and buffer.dim() == 2 and buffer.is_contiguous()
+    assert plan_dev.dtype == torch.int32 and plan_dev.dim() == 3 and plan_dev.shape[2] == 2 and plan_dev.is_contiguous()
+    assert pre_pairs.dtype == torch.int32 and pre_pairs.dim() == 2 and pre_pairs.shape[1] == 2 and pre_pairs.is_contiguous()
+    assert pass_word is None or (pass_word.dtype == torch.int32 and pass_word.numel() >= 1)
+    W = buffer.shape[1]
+    passes, batch = plan_dev.shape[:2]
+    out = torch.empty(batch, int(length) + 1, W, dtype=torch.float32, device=buffer.device)
+    check(lib().resel_gather_slices(_p(buffer), W, buffer.shape[0], _p(plan_dev), int(passes), int(batch), int(length), int(p), _p(pass_word),
+                                    int(c_done), int(c_timeout), _p(pre_pairs), pre_pairs.shape[0], _p(out), _stream()), 'gather_slices')
+    return out
+
+
+@torch.no_grad()
 def atb(wide, narrow, transposed=False):
     """wide [K, Wd] (column stride 1, Wd % 4 == 0), narrow [K, Nd <= 96] -> wide^T narrow [Wd, Nd] (or [Nd, Wd] if transposed):
     the long-reduction weight-gradient GEMMs of the narrow Mamba projections on a hand-written fp32 MFMA kernel."""

@@ -1,9 +1,11 @@
 """alg_name -> trainer class (reference offpolicy_rnn/utility/alg_init.py:16-47).
 
-The full-trajectory recurrent family and the memoryless baseline it is compared against,
-`sac_mlp_redq_ensemble_q`, are in scope of this build; the remaining reference names raise NotImplementedError with an explicit
-message instead of silently mapping to something else."""
+The full-trajectory recurrent family and the two baselines it is compared against - the memoryless
+`sac_mlp_redq_ensemble_q` and the slice trainer `sac_rnn_slice` (with `rnn_slice_length > 0`) - are in scope of this build; the
+remaining reference names raise NotImplementedError with an explicit message instead of silently mapping to something else."""
 
+# `sac_rnn_slice` stays in this tuple for the flag set the reference asserts against (`rnn_slice_length == 0`, the parser's default):
+# without a slice length there is no slice trainer to build, and the name raises like the other three
 _OUT_OF_SCOPE = ('sac_no_train', 'sac_mlp', 'sac_mlp_redq', 'sac_rnn_slice')
 
 
@@ -27,6 +29,9 @@ def alg_init(parameter):
         'td3_rnn_full_horizon_redQ_sep_optim': (TD3FullLengthRNNREDQ_SEP_OPTIM, 'td3'),
     }
     name = parameter.alg_name
+    if name == 'sac_rnn_slice' and parameter.rnn_slice_length > 0:
+        from ..algorithm.sac_rnn_slice import SACRNNSlice
+        return SACRNNSlice(parameter)
     if name in table:
         cls, base = table[name]
         if base == 'td3':
